@@ -4,6 +4,8 @@ One "step" = one fit iteration (reference optimize_to_joints.py:147-175): LBS ->
 silhouette -> six loss terms -> backward -> Adam, over the whole synthetic batch held by a rank.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full                    (everything below, not just the headline)
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR       (also the last step's outputs as DIR/<name>.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...          (no launcher: starts the line above as a child process and relays it)
@@ -12,8 +14,10 @@ Default workload: cfg2b (STICK, 4096 frames x 1 view @256^2), the configuration 
 roofline target is stated on; ``--workload`` selects the other BASELINE configs.
 
 Rank 0 prints ONE JSON line (contract in the task statement) with ``roofline`` (dominant kernel = the fused
-tile rasteriser, timed live with HIP events on its launch stream) and ``cpu_baseline`` (the CPU oracle timed on
-the host cores on a bounded sample of the same workload, rank 0 at N=1 only).
+tile rasteriser, timed live with HIP events on its launch stream, inside the timed steps).  A plain run does nothing
+else: set up, warm up, time ``--steps`` steps, print.  ``--full`` adds what the headline does not need: the
+self-check against the CPU oracle (``parity_check``), ``cpu_baseline`` (the CPU oracle timed on the host cores on a
+bounded sample of the same workload, rank 0 at N=1 only) and ``other_workloads`` (default workload, one GPU).
 """
 import argparse
 import json
@@ -302,6 +306,31 @@ def time_smal_call(key, dev, frames=4096, reps=30):
     return out
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6
+DUMP_PARAMS = ("betas", "log_beta_scales", "betas_trans", "global_rotation", "joint_rotations", "trans", "fov")
+
+
+def dump_outputs(out_dir, objs, fitter):
+    """What a caller of ``fit_step`` holds after the last timed step: the loss terms it returned (``objs``) and the parameters
+    its Adam step left (this rank's frames), as float32 ``out_dir/<name>.npy``.  Arrays over an even share of DUMP_MAX_BYTES keep
+    a fixed sample of their rows (seeded by name and shape only, so that two builds keep the same rows)."""
+    import zlib
+
+    import numpy as np
+
+    arrays = {"objs": objs}
+    arrays.update({n: getattr(fitter, n) for n in DUMP_PARAMS})
+    arrays = {n: t.detach().float().cpu().numpy() for n, t in arrays.items()}
+    share = DUMP_MAX_BYTES // len(arrays) - 4096  # (room for the .npy headers)
+    os.makedirs(out_dir, exist_ok=True)
+    for n, a in arrays.items():
+        if a.nbytes > share:
+            keep = max(1, share // (a.nbytes // a.shape[0]))
+            rng = np.random.default_rng(zlib.crc32(f"{n}{a.shape}".encode()))
+            a = a[np.sort(rng.choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, n + ".npy"), np.ascontiguousarray(a))
+
+
 def relaunch_multi_gpu(args) -> int:
     """``python bench.py --gpus N`` without a launcher: start one rank per GPU with torch.distributed.run as a CHILD
     process (never exec: nothing here has touched the GPU yet, and it stays that way in this process), relay its output
@@ -327,6 +356,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="cfg2b", choices=sorted(WORKLOADS))
     ap.add_argument("--frames", type=int, default=0, help="override the workload's frames per GPU (tests, rehearsals)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the self-check against the CPU oracle, the CPU baseline and the short runs of the other "
+                         "BASELINE configurations (--cpu-frames, --no-parity and --no-others apply to this mode only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (its loss terms, the parameters after its Adam "
+                         "step) as DIR/<name>.npy")
     ap.add_argument("--cpu-frames", type=int, default=-1, help="frames of the CPU baseline sample (0 = skip; default: about 8 images)")
     ap.add_argument("--no-parity", action="store_true", help="skip the self-check against the CPU oracle (it needs --cpu-frames > 0)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -338,6 +373,8 @@ def main():
     ap.add_argument("--no-others", action="store_true",
                     help="skip the short runs of the other BASELINE configurations behind the headline region (default workload, one GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -382,7 +419,7 @@ def main():
     if args.tie_rule != "depth_face_id":
         fitter.renderer.raster_settings = engine.raster_settings(tie_rule=args.tie_rule)
     n_cpu = 0
-    if rank == 0 and world == 1 and args.cpu_frames != 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_frames != 0:
         n_cpu = min(frames, args.cpu_frames if args.cpu_frames > 0 else max(1, 8 // views))
         sample = cpu_sample(fitter, n_cpu)
     parity = cpu_base = None
@@ -425,6 +462,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
     loss = float(objs[:9].sum().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, objs, fitter)
 
     if rank == 0:
         ms = 1000.0 * dt / args.steps
@@ -509,7 +548,7 @@ def main():
             out["parity_check"] = parity
         if cpu_base is not None:
             out["cpu_baseline"] = cpu_base
-        if world == 1 and args.workload == "cfg2b" and not args.frames and not args.no_others:
+        if args.full and world == 1 and args.workload == "cfg2b" and not args.frames and not args.no_others:
             # the other BASELINE configurations as the driver sees them: five steps each, after the headline's timed region and
             # outside it (headline metric / config / dtype unchanged); the one-frame iteration is the only shape the unmodified
             # reference can run

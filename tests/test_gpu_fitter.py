@@ -225,7 +225,10 @@ def test_graph_captured_step_equals_eager_step(key, radius, tie_rule, tables):
         o, par = runs[mode]
         np.testing.assert_allclose(o.numpy(), ref_objs.numpy(), rtol=2e-4, atol=1e-6)
         for n in PARAMS:  # float atomics make the gradient sums order dependent: compare to Adam-step resolution
-            np.testing.assert_allclose(par[n].numpy(), ref_par[n].numpy(), atol=2e-4, err_msg=f"{mode}: {n}")
+            # (2e-4 = 4 % of one step at lr 5e-3.  fov steps at lr 1 - begin_stage's fov_lr - so the same gradient noise moves it 200 x
+            # as far: two eager runs of the mouse case alone differ by up to ~5e-5 in fov.  Its bound, 5e-3, is 0.5 % of one of its steps)
+            atol = 5e-3 if n == "fov" else 2e-4
+            np.testing.assert_allclose(par[n].numpy(), ref_par[n].numpy(), atol=atol, err_msg=f"{mode}: {n}")
     assert float(ref_objs[-1].sum()) < float(ref_objs[0].sum())
 
 
