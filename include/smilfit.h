@@ -289,6 +289,22 @@ int smil_silhouette_l1_fused(const SmilModel *m, const float *verts_ndc, int32_t
                              const float *target_sum, const float *pix_scale, float *loss_img, float *d_ndc,
                              float *sil_out, float *d_ndc_scale, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Colour (HardPhong) rendering.  Replaces the reference Renderer's colour branch (p3d_renderer.py:54-70,148-150: MeshRasterizer with
+ * blur_radius 0, faces_per_pixel 1, bin_size 0 on the same cameras + HardPhongShader with PointLights(location [[0, 0, 3]]), default
+ * Materials / BlendParams, TexturesVertex of one colour), used by render_texture=True (p3d_renderer.py:127-150) and by
+ * SMALFitter.generate_visualization (fitter.py:462-480).  Lights and materials are the reference's constants; the mesh colour is the
+ * only input.  No gradient.
+ * ---------------------------------------------------------------------------------------- */
+/* Caller-owned scratch for N images of side S (per-face tile boxes / depth ranges, binned tile lists, work items, clip tables of the
+ * faces cut at z_clip, vertex normals): about 12 F + 8 x LIST entries of 8 B per image - no per-workgroup pair-record streams. */
+size_t smil_colour_workspace_bytes(const SmilModel *m, int32_t N, int32_t S);
+/* verts_world (frames,V,3) world-space vertices, verts_ndc (N,V,3) = smil_project(cam, verts_world) (N = cam->N = frames * views,
+ * S = cam->S), rgb[3] a HOST array (MESH_COLOR / 255) -> image (N,3,S,S) planar RGB, background (1,1,1); pix_to_face (N,S,S) the
+ * original face id of every pixel (-1: background) or NULL.  z_clip = znear / 2 as on the silhouette path; faces cut there are drawn
+ * as pytorch3d's clip_faces cuts them and reported as their original face.  A pixel shows the smallest (depth, face, part). */
+int smil_render_colour(const SmilModel *m, const SmilCameras *cam, const float *verts_world, const float *verts_ndc,
+                       const float rgb[3], float *image, int32_t *pix_to_face, void *workspace, void *stream);
 /* Measurement hook (bench.py): when enabled, every launch of the tile kernel is bracketed by HIP events on its
  * launch stream; smil_profile_read synchronises those events and returns their summed duration + count. */
 int smil_profile_enable(int32_t on);

@@ -20,7 +20,7 @@ EXPORTS = [
     "smil_raster_workspace_bytes", "smil_raster_stats", "smil_silhouette_forward", "smil_silhouette_backward",
     "smil_silhouette_l1_fused", "smil_prior_losses", "smil_mask_rows", "smil_joint_loss", "smil_pix_scale",
     "smil_image_abs_sum", "smil_sil_objective", "smil_window_terms", "smil_adam_step", "smil_adam_step_multi", "smil_adam_step_dev", "smil_profile_enable",
-    "smil_profile_read",
+    "smil_profile_read", "smil_colour_workspace_bytes", "smil_render_colour",
 ]
 
 N_OBJS = 10
@@ -144,6 +144,10 @@ def load():
     lib.smil_adam_step_multi.argtypes = [POINTER(AdamTensor), c_int32, c_float, c_float, c_float, c_void_p]
     lib.smil_adam_step_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float,
                                        c_void_p, c_int32, c_void_p]
+    lib.smil_colour_workspace_bytes.argtypes = [c_void_p, c_int32, c_int32]
+    lib.smil_colour_workspace_bytes.restype = c_size_t
+    lib.smil_render_colour.argtypes = [c_void_p, POINTER(Cameras), c_void_p, c_void_p, POINTER(c_float), c_void_p, c_void_p, c_void_p,
+                                       c_void_p]
     lib.smil_profile_enable.argtypes = [c_int32]
     lib.smil_profile_read.argtypes = [POINTER(c_float), POINTER(c_int32)]
     for name in EXPORTS:

@@ -44,6 +44,8 @@ class FitterConfig:
     MESH_COLOR: List[int] = field(default_factory=lambda: [0, 172, 223])
     OPT_WEIGHTS: List[List[float]] = field(default_factory=lambda: [list(r) for r in DEFAULT_OPT_WEIGHTS])
     JOINT_LIMIT: float = 0.01             # joint_limits_prior.py:8-15 (all non-root joints, +-0.01 rad)
+    RENDER_COLOUR: bool = False           # SMALFitter's Renderer draws the HardPhong colour image (render_texture=True and the
+                                          # render / overlay / view-from-behind panels of generate_visualization); off: silhouettes
 
     @staticmethod
     def from_tables(tables, smal_file: Optional[str] = None, **overrides) -> "FitterConfig":

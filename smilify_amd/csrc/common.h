@@ -70,8 +70,32 @@ struct SmilModel {
                                   // is wave w's k-th bone, -1 behind its last
     int bone_slots = 0;
     float *posedirs = nullptr;    // (9(J-1),3V) or null
+    int *vf_ptr = nullptr;        // (V+1) vertex -> face CSR: the faces of vertex v are vf_face[vf_ptr[v] .. vf_ptr[v+1]), ascending
+    int *vf_face = nullptr;       // (3F)   (per-frame vertex normals of the colour path, shade.hip: a fixed-order gather, no atomics)
     std::vector<void *> allocations;
 };
+
+// What the colour path (shade.hip) takes from the rasteriser's setup kernel (raster.hip), run with blur 0: per-face tile boxes and
+// depth ranges, the binned per-tile face lists, the touched-tile work items and the clip tables of faces cut at z_clip.
+struct ColourSetup {
+    const uint32_t *tbox;     // (N, FT) tile box of every face (4 x u8: tx0, ty0, tx1, ty1; empty when tx0 > tx1)
+    const uint32_t *gbox;     // (N, FT / 64) union of the boxes of 64 consecutive faces (tiles whose list was not binned)
+    const float2 *fzr;        // (N, FT) nearest / farthest vertex depth
+    const uint4 *items;       // work items {image * tiles + tile, first list entry, entries (0xFFFFFFFF: not binned), -}
+    const uint32_t *n_class;  // (n_parts, n_classes) items per partition and cost class (device)
+    uint32_t *ticket;         // dealing counter, zero at the start of the call
+    uint32_t item_cap;        // entries of one item array of one partition
+    const uint2 *lists;       // (N, list_cap) {face id, bits of its nearest vertex depth}
+    uint32_t list_cap;
+    const float *xv;          // (N, clip_vx, 3) new vertices of cut faces (x_ndc, y_ndc, z_clip)
+    const int *xf;            // (N, clip_fx, 3) vertex ids of the front parts (>= V: new vertices)
+    const int2 *xsrc;         // (N, clip_vx) end points of the edge a new vertex lies on
+    const int *xparent;       // (N, clip_fx / 2) the face a cut belongs to
+    int FT, FP, clip_vx, clip_fx, n_parts, n_classes;
+};
+size_t smil_colour_setup_bytes(const SmilModel *m, int N, int S);
+int smil_colour_setup(const SmilModel *m, const float *verts_ndc, int N, int S, float z_clip, void *workspace, hipStream_t stream,
+                      ColourSetup *out);
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 

@@ -60,9 +60,15 @@ extern "C" int smil_model_create(const SmilModelDesc *d, SmilModel **out) {
     for (int i = 0; i < 3 * F; ++i)
         SMIL_REQUIRE(d->faces[i] >= 0 && d->faces[i] < V, "smil_model_create: face index %d out of range", d->faces[i]);
     int max_valence = 0;
+    std::vector<int> vf_ptr(V + 1, 0), vf_face(3 * F);
     {
         std::vector<int> valence(V, 0);
         for (int i = 0; i < 3 * F; ++i) max_valence = std::max(max_valence, ++valence[d->faces[i]]);
+        // vertex -> face CSR (a face listed once per corner, faces ascending)
+        for (int v = 0; v < V; ++v) vf_ptr[v + 1] = vf_ptr[v] + valence[v];
+        std::vector<int> pos(vf_ptr.begin(), vf_ptr.end() - 1);
+        for (int f = 0; f < F; ++f)
+            for (int k = 0; k < 3; ++k) vf_face[pos[d->faces[3 * f + k]]++] = f;
     }
     const int nnz = d->jreg_rowptr[J];
     SMIL_REQUIRE(nnz >= 0 && (nnz == 0 || (d->jreg_col && d->jreg_val)), "smil_model_create: regressor CSR malformed");
@@ -183,6 +189,8 @@ extern "C" int smil_model_create(const SmilModelDesc *d, SmilModel **out) {
     UP(bone_order, bone_order.data(), bone_slots);
     m->bone_slots = bone_slots;
     UP(J_static, d->static_joints ? d->J_static : (const float *)nullptr, 3 * J);
+    UP(vf_ptr, vf_ptr.data(), V + 1);
+    UP(vf_face, vf_face.data(), 3 * F);
     if (d->posedirs) { UP(posedirs, d->posedirs, (size_t)9 * (J - 1) * 3 * V); }
 #undef UP
     *out = m;

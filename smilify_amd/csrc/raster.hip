@@ -168,6 +168,7 @@ struct ClipTables {
     float2 *xcoef;      // (N, CLIP_VX) (c_a, c_b)
     float *xg;          // (N, CLIP_VX, 2) gradient rows of the new vertices (same representation as d_ndc)
     uint32_t *xcount;   // (N) new vertices of the image
+    int *xparent;       // (N, CLIP_CUTS) the face cut c belongs to, or NULL (only the colour path asks: smil_colour_setup)
 };
 __host__ __device__ __forceinline__ int faces_padded(int F) { return (F + WAVE - 1) / WAVE * WAVE; }
 // vertex ids of face f of image n / coordinates of vertex i of image n, through the clip tables
@@ -452,6 +453,7 @@ __global__ void __launch_bounds__(SETUP_THREADS, 8) k_raster_setup(SetupArgs q) 
     const uint32_t n_cut = min(s_ncut, (uint32_t)CLIP_CUTS);
     for (uint32_t c = threadIdx.x; c < n_cut; c += blockDim.x) {
         const int f = s_cut[c];
+        if (q.clip.xparent) q.clip.xparent[(size_t)n * CLIP_CUTS + c] = f;
         const int ii[3] = {q.faces[3 * f], q.faces[3 * f + 1], q.faces[3 * f + 2]};
         float X[3], Y[3], Z[3];
         for (int k = 0; k < 3; ++k) { X[k] = vn[3 * ii[k]]; Y[k] = vn[3 * ii[k] + 1]; Z[k] = vn[3 * ii[k] + 2]; }
@@ -2540,6 +2542,7 @@ static int raster_common(const SmilModel *m, const float *verts_ndc, int N, int 
     clip.xcoef = (float2 *)ws; ws += align256((size_t)N * CLIP_VX * 8);
     clip.xf = (int *)ws; ws += align256((size_t)N * CLIP_FX * 12);
     clip.xcount = (uint32_t *)ws; ws += align256((size_t)N * 4);
+    clip.xparent = nullptr;
     SMIL_HIP(hipMemsetAsync(ctr, 0, sizeof(RasterCounters), stream));
     if (rs->tie_rule) SMIL_HIP(hipMemsetAsync(tie_mask, 0, (size_t)2 * N_PARTS * item_cap * sizeof(unsigned long long), stream));
     const float sqrt_blur = sqrtf(rs->blur_radius);
@@ -2595,6 +2598,63 @@ static int raster_common(const SmilModel *m, const float *verts_ndc, int N, int 
     HOOK_HOST_LAUNCH_SETUP(a, stream)
     a.sil = nullptr; a.grad_sil = nullptr; a.target = nullptr; a.target_u8 = nullptr; a.pix_scale = nullptr; a.loss_img = nullptr;
     a.d_ndc = nullptr;
+    return SMIL_OK;
+}
+
+// ---- the colour path's share of the setup (shade.hip): k_raster_setup with blur 0 (K = 1 needs no blur box), its per-image tables,
+// binned lists, work items and clip tables - none of the tile kernel's per-workgroup scratch ----
+static inline size_t colour_setup_layout(const SmilModel *m, int N, int S, char *ws, ColourSetup *o, SetupArgs *q) {
+    const int tiles_x = ceil_div(S, TILE), FT = face_rows(m);
+    const uint32_t item_cap = (uint32_t)ceil_div(N, N_PARTS) * (uint32_t)(tiles_x * tiles_x);
+    const uint32_t list_cap = list_cap_of(m, S);
+    size_t off = 0;
+    auto take = [&](size_t bytes) -> char * { char *p = ws ? ws + off : nullptr; off += align256(bytes); return p; };
+    char *tbox = take((size_t)N * FT * sizeof(uint32_t));
+    char *ctr = take(sizeof(RasterCounters));
+    char *items = take((size_t)2 * N_PARTS * item_cap * sizeof(uint4));
+    char *fzr = take((size_t)N * FT * sizeof(float2));
+    char *gbox = take((size_t)N * (FT / WAVE) * sizeof(uint32_t));
+    char *lists = take((size_t)N * list_cap * sizeof(uint2));
+    ClipTables clip;
+    clip.xv = (float *)take((size_t)N * CLIP_VX * 12);
+    clip.xsrc = (int2 *)take((size_t)N * CLIP_VX * 8);
+    clip.xcoef = (float2 *)take((size_t)N * CLIP_VX * 8);
+    clip.xf = (int *)take((size_t)N * CLIP_FX * 12);
+    clip.xparent = (int *)take((size_t)N * CLIP_CUTS * 4);
+    clip.xg = nullptr; clip.xcount = nullptr;  // (no gradient rows)
+    if (!ws) return off;
+    RasterCounters *c = (RasterCounters *)ctr;
+    o->tbox = (const uint32_t *)tbox; o->gbox = (const uint32_t *)gbox; o->fzr = (const float2 *)fzr; o->items = (const uint4 *)items;
+    o->n_class = &c->n_class[0][0]; o->ticket = &c->deal[0].next; o->item_cap = item_cap;
+    o->lists = (const uint2 *)lists; o->list_cap = list_cap;
+    o->xv = clip.xv; o->xf = clip.xf; o->xsrc = clip.xsrc; o->xparent = clip.xparent;
+    o->FT = FT; o->FP = faces_padded(m->F); o->clip_vx = CLIP_VX; o->clip_fx = CLIP_FX; o->n_parts = N_PARTS; o->n_classes = N_CLASSES;
+    *q = SetupArgs{};
+    q->clip = clip; q->faces = m->faces; q->tbox = (uint32_t *)tbox; q->gbox = (uint32_t *)gbox; q->items = (uint4 *)items;
+    q->item_cap = item_cap; q->fzr = (float2 *)fzr; q->ctr = c; q->V = m->V; q->F = m->F; q->S = S; q->tiles_x = tiles_x;
+    q->sqrt_blur = 0.f; q->inv_sigma = 1.f; q->lists = (uint2 *)lists; q->list_cap = list_cap;
+    q->copies = tiles_x * tiles_x * 2 * 12 <= 48 * 1024 ? 2 : 1;
+    return off;
+}
+
+size_t smil_colour_setup_bytes(const SmilModel *m, int N, int S) {
+    return (m && N > 0 && S > 0) ? colour_setup_layout(m, N, S, nullptr, nullptr, nullptr) : 0;
+}
+
+int smil_colour_setup(const SmilModel *m, const float *verts_ndc, int N, int S, float z_clip, void *workspace, hipStream_t stream,
+                      ColourSetup *out) {
+    SMIL_REQUIRE(N > 0 && S > 0 && S <= TILE * 256, "smil_render_colour: bad sizes N=%d S=%d", N, S);
+    SMIL_REQUIRE(face_rows(m) + 64 < (1 << 24) && (double)list_cap_of(m, S) * sizeof(uint2) < 4294967296.0,
+                 "smil_render_colour: per-image tables exceed the 24-bit index / 32-bit byte-offset range of at()");
+    const int tiles_x = ceil_div(S, TILE), n_tiles = tiles_x * tiles_x;
+    SMIL_REQUIRE((double)N * n_tiles < 2147483647.0, "smil_render_colour: N * tiles exceeds the work-item index range (2^31)");
+    SetupArgs q;
+    colour_setup_layout(m, N, S, (char *)workspace, out, &q);
+    q.verts_ndc = verts_ndc; q.z_clip = z_clip;
+    SMIL_HIP(hipMemsetAsync(q.ctr, 0, sizeof(RasterCounters), stream));
+    const size_t setup_lds = n_tiles <= COUNT_TILES_MAX ? (size_t)n_tiles * q.copies * 12 : (size_t)((n_tiles + 31) / 32) * sizeof(uint32_t);
+    hipLaunchKernelGGL(k_raster_setup, dim3(N), dim3(SETUP_THREADS), setup_lds, stream, q);
+    SMIL_LAUNCH_CHECK();
     return SMIL_OK;
 }
 

@@ -1,0 +1,327 @@
+// HardPhong colour rendering for gfx950: the reference Renderer's colour branch.
+//
+// Replaces (reference): smal_fitter/p3d_renderer.py:54-70,148-150 - MeshRasterizer(blur_radius=0, faces_per_pixel=1, bin_size=0) on the
+// same FoVPerspectiveCameras + HardPhongShader(lights=PointLights(location=[[0, 0, 3]])) with default Materials and BlendParams, over
+// Meshes(verts, faces, TexturesVertex(MESH_COLOR / 255)).  The arithmetic restates pytorch3d 0.7.x (un-vendored):
+// rasterize_meshes.cu (naive kernel, K = 1), clip.py (clip_faces / convert_clipped_rasterization_to_original_faces),
+// meshes.py (verts_normals_packed), shading.py (phong_shading), lighting.py (diffuse / specular), blending.py (hard_rgb_blend).
+//
+//  * k_vertex_normals   thread per (frame, vertex): the sum of the (2 x area) normals of the vertex's faces, gathered through the
+//                       vertex -> face CSR of smil_model_create in ascending face order (no atomics: bit-reproducible), normalised
+//                       with eps 1e-6.  World space, per frame.
+//  * k_raster_setup     (raster.hip, blur 0) per-face tile boxes and depth ranges, binned per-tile face lists, touched-tile work items
+//                       by cost class, faces that cross z_clip cut into their front parts (smil_colour_setup).
+//  * k_colour_background  the whole output as background (1, 1, 1) / pix_to_face -1.
+//  * k_colour_tiles     one wave per 8x8 tile, lane = pixel.  The tile's list is read 64 entries at a time; a face whose nearest vertex
+//                       is farther than every pixel's current hit is not fetched at all.  The others are gathered in parallel (lane =
+//                       face: vertex ids through the clip tables, affine forms of the three perspective-correct barycentric numerators
+//                       relative to the tile centre) and then evaluated one after the other by all 64 pixels (readlane).  A pixel keeps
+//                       the smallest (depth, parent face, part): the naive kernel's order with clip_faces' numbering.  The winner is
+//                       shaded in registers and written as planar RGB.
+//
+// Semantics: strictly inside (all perspective-corrected barycentrics > 0), unclipped barycentrics, pz >= 0, no
+// culling; barycentrics of a cut face's part mapped back to the original face (each part vertex is a known barycentric point of it).
+// colour = (0.5 + 0.3 relu(n.d)) MESH_COLOR (b0 + b1 + b2) + 0.2 (relu(v.r) [n.d > 0])^64, background (1, 1, 1).  No gradient.
+#include <algorithm>
+
+#include "common.h"
+
+#define CTILE 8
+#define COLOUR_WAVES_PER_CU 28  // single-wave workgroups per CU of the tile kernel's grid (7 per SIMD: what its 67 VGPRs allow)
+#define C_EPS 1e-8f              // pytorch3d kEpsilon of the rasteriser
+#define N_EPS 1e-6f              // F.normalize eps of the normals and the light / view directions
+
+__device__ __forceinline__ float rdl(float x, int j) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), j)); }
+__device__ __forceinline__ int rdl(int x, int j) { return __builtin_amdgcn_readlane(x, j); }
+__device__ __forceinline__ float cpix_to_ndc(int i, int S) { return -1.0f + (2.0f * (float)i + 1.0f) / (float)S; }
+
+// ---------------------------------------------------------------------------------------------
+// per-frame vertex normals (Meshes.verts_normals_packed)
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_vertex_normals(const float *__restrict__ verts, const int *__restrict__ faces,
+                                                        const int *__restrict__ vf_ptr, const int *__restrict__ vf_face, int V,
+                                                        float *__restrict__ normals) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= V) return;
+    const float *X = verts + (size_t)blockIdx.y * V * 3;
+    float nx = 0.f, ny = 0.f, nz = 0.f;
+    for (int e = vf_ptr[v]; e < vf_ptr[v + 1]; ++e) {
+        const int f = vf_face[e];
+        const float *a = X + 3 * faces[3 * f], *b = X + 3 * faces[3 * f + 1], *c = X + 3 * faces[3 * f + 2];
+        // cross(v2 - v1, v0 - v1), as meshes.py forms it
+        const float ux = c[0] - b[0], uy = c[1] - b[1], uz = c[2] - b[2];
+        const float wx = a[0] - b[0], wy = a[1] - b[1], wz = a[2] - b[2];
+        nx += uy * wz - uz * wy;
+        ny += uz * wx - ux * wz;
+        nz += ux * wy - uy * wx;
+    }
+    const float inv = 1.0f / fmaxf(sqrtf(nx * nx + ny * ny + nz * nz), N_EPS);
+    float *o = normals + ((size_t)blockIdx.y * V + v) * 3;
+    o[0] = nx * inv; o[1] = ny * inv; o[2] = nz * inv;
+}
+
+// ---------------------------------------------------------------------------------------------
+// background
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_colour_background(float *__restrict__ image, size_t n_image, int *__restrict__ p2f, size_t n_p2f) {
+    // (plain 4-byte stores: a slice of a batch need not start on a 16-byte boundary)
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_image; i += stride) image[i] = 1.0f;
+    if (p2f)
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_p2f; i += stride) p2f[i] = -1;
+}
+
+// ---------------------------------------------------------------------------------------------
+// rasterise (K = 1) + HardPhong
+// ---------------------------------------------------------------------------------------------
+struct ColourArgs {
+    ColourSetup cs;
+    const float *verts_ndc;    // (N,V,3)
+    const float *verts_world;  // (frames,V,3)
+    const float *normals;      // (frames,V,3)
+    const int *faces;          // (F,3)
+    SmilCameras cam;
+    float rgb[3];
+    float *image;              // (N,3,S,S)
+    int *pix_to_face;          // (N,S,S) or NULL
+    int N, V, F, S, tiles_x, views;
+    float z_clip;
+};
+
+// corner of face (P0, P1, P2) that holds vertex id v (the first one: a face with a repeated vertex has no area and is never drawn)
+__device__ __forceinline__ int corner_of(int v, int P0, int P1, int P2) { return v == P0 ? 0 : (v == P1 ? 1 : 2); }
+
+__global__ void __launch_bounds__(64) k_colour_tiles(ColourArgs a) {
+    const ColourSetup &cs = a.cs;
+    const int lane = threadIdx.x;
+    const int S = a.S, V = a.V, F = a.F, tiles_x = a.tiles_x, n_tiles = tiles_x * tiles_x;
+    // work items, heaviest class first: order index k = class * n_parts + part, the counts' inclusive prefix in lane k
+    const int nk = cs.n_parts * cs.n_classes;
+    uint32_t cnt = 0u;
+    if (lane < nk) cnt = cs.n_class[(lane % cs.n_parts) * cs.n_classes + lane / cs.n_parts];
+    uint32_t incl = cnt;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t u = (uint32_t)__shfl_up((int)incl, o, 64);
+        if (lane >= o) incl += u;
+    }
+    const uint32_t total = (uint32_t)__shfl((int)incl, nk - 1, 64);
+    const uint32_t excl = incl - cnt;
+    if (lane >= nk) incl = 0xFFFFFFFFu;
+
+    const int xl = lane & (CTILE - 1), yl = lane >> 3;
+    for (uint32_t t = blockIdx.x; t < total; t += gridDim.x) {
+        const int k = __popcll(__ballot(incl <= t));  // (lanes >= nk never count)
+        const uint32_t slot = t - (uint32_t)rdl((int)excl, k);
+        const int part = k % cs.n_parts, cls = k / cs.n_parts;
+        const size_t idx = (size_t)(2 * part + (cls >> 1)) * cs.item_cap + ((cls & 1) ? cs.item_cap - 1u - slot : slot);
+        const uint4 it = cs.items[idx];
+        const int img = (int)(it.x / (uint32_t)n_tiles), tile = (int)(it.x % (uint32_t)n_tiles);
+        const int tx = tile % tiles_x, ty = tile / tiles_x;
+        const int xo = tx * CTILE + xl, yo = ty * CTILE + yl;
+        const bool in_img = xo < S && yo < S;
+        // pixel centre relative to the tile's centre (column xo holds image x index S - 1 - xo, as on the silhouette path)
+        const float cx = cpix_to_ndc(S - 1 - (tx * CTILE + CTILE / 2), S), cy = cpix_to_ndc(S - 1 - (ty * CTILE + CTILE / 2), S);
+        const float dx = cpix_to_ndc(S - 1 - xo, S) - cx, dy = cpix_to_ndc(S - 1 - yo, S) - cy;
+
+        const float *vn = a.verts_ndc + (size_t)img * V * 3;
+        const float *xv_n = cs.xv + (size_t)img * cs.clip_vx * 3;
+        const int *xf_n = cs.xf + (size_t)img * cs.clip_fx * 3;
+        const int *xpar_n = cs.xparent + (size_t)img * (cs.clip_fx / 2);
+        float bz = __builtin_inff(), bw0 = 0.f, bw1 = 0.f, bw2 = 0.f;
+        uint32_t bkey = 0xFFFFFFFFu;
+        int bfid = -1;
+        float tile_far = __builtin_inff();  // largest current depth over the tile's pixels (inf while one has no hit)
+
+        // one batch of up to 64 candidate faces, face f / nearest vertex depth zmin in lane j
+        auto batch = [&](bool valid, int f, float zmin) {
+            const bool keep = valid && zmin <= tile_far;
+            unsigned long long mask = __ballot(keep);
+            if (!mask) return;
+            float A0 = 0.f, B0 = 0.f, C0 = 0.f, A1 = 0.f, B1 = 0.f, C1 = 0.f, A2 = 0.f, B2 = 0.f, C2 = 0.f, z0 = 0.f, z1 = 0.f, z2 = 0.f;
+            uint32_t key = 0u;
+            if (keep) {
+                int id[3];
+                float X[3], Y[3], Z[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    id[c] = f < F ? a.faces[3 * f + c] : xf_n[3 * (f - cs.FP) + c];
+                    const float *p = id[c] < V ? vn + 3 * id[c] : xv_n + 3 * (id[c] - V);
+                    X[c] = p[0] - cx; Y[c] = p[1] - cy; Z[c] = p[2];
+                }
+                key = f < F ? 2u * (uint32_t)f : 2u * (uint32_t)xpar_n[(f - cs.FP) >> 1] + (uint32_t)((f - cs.FP) & 1);
+                // b_i = edge_i(p) / area, area = edge(v2; v0, v1) + eps; w_i = b_i z_j z_k (perspective-correct numerators)
+                const float area = (X[2] - X[0]) * (Y[1] - Y[0]) - (Y[2] - Y[0]) * (X[1] - X[0]) + C_EPS;
+                const float ia = 1.0f / area;
+                const float s0 = Z[1] * Z[2] * ia, s1 = Z[0] * Z[2] * ia, s2 = Z[0] * Z[1] * ia;
+                // edge(p; a, b) = (px - ax)(by - ay) - (py - ay)(bx - ax)
+                A0 = (Y[2] - Y[1]) * s0; B0 = -(X[2] - X[1]) * s0; C0 = (-X[1] * (Y[2] - Y[1]) + Y[1] * (X[2] - X[1])) * s0;
+                A1 = (Y[0] - Y[2]) * s1; B1 = -(X[0] - X[2]) * s1; C1 = (-X[2] * (Y[0] - Y[2]) + Y[2] * (X[0] - X[2])) * s1;
+                A2 = (Y[1] - Y[0]) * s2; B2 = -(X[1] - X[0]) * s2; C2 = (-X[0] * (Y[1] - Y[0]) + Y[0] * (X[1] - X[0])) * s2;
+                z0 = Z[0]; z1 = Z[1]; z2 = Z[2];
+            }
+            while (mask) {
+                const int j = __builtin_ctzll(mask);
+                mask &= mask - 1ull;
+                const float w0 = fmaf(rdl(A0, j), dx, fmaf(rdl(B0, j), dy, rdl(C0, j)));
+                const float w1 = fmaf(rdl(A1, j), dx, fmaf(rdl(B1, j), dy, rdl(C1, j)));
+                const float w2 = fmaf(rdl(A2, j), dx, fmaf(rdl(B2, j), dy, rdl(C2, j)));
+                if (w0 > 0.f && w1 > 0.f && w2 > 0.f) {
+                    const float den = fmaxf(w0 + w1 + w2, C_EPS);
+                    const float pz = (w0 * rdl(z0, j) + w1 * rdl(z1, j) + w2 * rdl(z2, j)) / den;
+                    const uint32_t kj = (uint32_t)rdl((int)key, j);
+                    if (pz >= 0.f && (pz < bz || (pz == bz && kj < bkey))) {
+                        bz = pz; bkey = kj; bfid = rdl(f, j); bw0 = w0; bw1 = w1; bw2 = w2;
+                    }
+                }
+            }
+            tile_far = wave_max(in_img ? bz : 0.f);
+        };
+
+        if (it.z != 0xFFFFFFFFu) {  // binned list
+            const uint2 *lst = cs.lists + (size_t)img * cs.list_cap + it.y;
+            for (uint32_t base = 0; base < it.z; base += 64u) {
+                const bool valid = base + (uint32_t)lane < it.z;
+                const uint2 e = valid ? lst[base + lane] : make_uint2(0u, 0u);
+                batch(valid, (int)e.x, __uint_as_float(e.y));
+            }
+        } else {  // the image's lists did not fit: the faces whose tile box holds the tile, 64-face group by group
+            const int n_groups = cs.FT / WAVE;
+            for (int g = 0; g < n_groups; ++g) {
+                const uint32_t gb = cs.gbox[(size_t)img * n_groups + g];
+                if (!((int)(gb & 0xFF) <= tx && tx <= (int)((gb >> 16) & 0xFF) && (int)((gb >> 8) & 0xFF) <= ty && ty <= (int)(gb >> 24))) continue;
+                const int f = g * WAVE + lane;
+                const uint32_t tb = cs.tbox[(size_t)img * cs.FT + f];
+                const bool valid = (int)(tb & 0xFF) <= tx && tx <= (int)((tb >> 16) & 0xFF) && (int)((tb >> 8) & 0xFF) <= ty && ty <= (int)(tb >> 24);
+                batch(valid, f, valid ? cs.fzr[(size_t)img * cs.FT + f].x : 0.f);
+            }
+        }
+
+        if (!in_img) continue;
+        const size_t pix = (size_t)yo * S + xo;
+        if (bfid < 0) {  // (the background pass has written this pixel)
+            continue;
+        }
+        // barycentrics of the winner (unclipped, perspective-corrected), mapped to the original face
+        const float iden = 1.0f / fmaxf(bw0 + bw1 + bw2, C_EPS);
+        const float p[3] = {bw0 * iden, bw1 * iden, bw2 * iden};
+        int orig;
+        float b[3];
+        int P0, P1, P2;
+        if (bfid < F) {
+            orig = bfid;
+            P0 = a.faces[3 * orig]; P1 = a.faces[3 * orig + 1]; P2 = a.faces[3 * orig + 2];
+            b[0] = p[0]; b[1] = p[1]; b[2] = p[2];
+        } else {
+            const int r = bfid - cs.FP;
+            orig = xpar_n[r >> 1];
+            P0 = a.faces[3 * orig]; P1 = a.faces[3 * orig + 1]; P2 = a.faces[3 * orig + 2];
+            b[0] = 0.f; b[1] = 0.f; b[2] = 0.f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int s = xf_n[3 * r + c];
+                if (s < V) {
+                    b[corner_of(s, P0, P1, P2)] += p[c];
+                } else {  // new vertex on edge (u, w): view-space point (1 - t) X_u + t X_w, t = (z_u - z_clip) / (z_u - z_w)
+                    const int2 e = cs.xsrc[(size_t)img * cs.clip_vx + (s - V)];
+                    const float zu = vn[3 * e.x + 2], zw = vn[3 * e.y + 2];
+                    const float tw = (zu - a.z_clip) / (zu - zw);
+                    b[corner_of(e.x, P0, P1, P2)] += p[c] * (1.0f - tw);
+                    b[corner_of(e.y, P0, P1, P2)] += p[c] * tw;
+                }
+            }
+        }
+        const int frame = img / a.views;
+        const float *Xw = a.verts_world + (size_t)frame * V * 3;
+        const float *Nw = a.normals + (size_t)frame * V * 3;
+        const int Pi[3] = {P0, P1, P2};
+        float X[3] = {0.f, 0.f, 0.f}, Nn[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                X[q] = fmaf(b[c], Xw[3 * Pi[c] + q], X[q]);
+                Nn[q] = fmaf(b[c], Nw[3 * Pi[c] + q], Nn[q]);
+            }
+        const float bsum = b[0] + b[1] + b[2];
+        // camera centre C = -T R^T (X_view = X_world R + T)
+        const float *R = a.cam.R + (size_t)(img % a.cam.nR) * 9;
+        const float *T = a.cam.T + (size_t)(img % a.cam.nT) * 3;
+        float C[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) C[q] = -(T[0] * R[3 * q] + T[1] * R[3 * q + 1] + T[2] * R[3 * q + 2]);
+        const float L[3] = {0.f, 0.f, 3.f};
+        float d[3], v[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) { d[q] = L[q] - X[q]; v[q] = C[q] - X[q]; }
+        const float in_ = 1.0f / fmaxf(sqrtf(Nn[0] * Nn[0] + Nn[1] * Nn[1] + Nn[2] * Nn[2]), N_EPS);
+        const float id_ = 1.0f / fmaxf(sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]), N_EPS);
+        const float iv_ = 1.0f / fmaxf(sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]), N_EPS);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) { Nn[q] *= in_; d[q] *= id_; v[q] *= iv_; }
+        const float cosang = Nn[0] * d[0] + Nn[1] * d[1] + Nn[2] * d[2];
+        const float diffuse = 0.3f * fmaxf(cosang, 0.f);
+        float vr = 0.f;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) vr += v[q] * (-d[q] + 2.0f * cosang * Nn[q]);
+        float al = cosang > 0.f ? fmaxf(vr, 0.f) : 0.f;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) al *= al;  // ^64
+        const float spec = 0.2f * al;
+        const float amb_diff = (0.5f + diffuse) * bsum;
+        float *o = a.image + (size_t)img * 3 * S * S + pix;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[(size_t)c * S * S] = amb_diff * a.rgb[c] + spec;
+        if (a.pix_to_face) a.pix_to_face[(size_t)img * S * S + pix] = orig;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------
+static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+extern "C" size_t smil_colour_workspace_bytes(const SmilModel *m, int32_t N, int32_t S) {
+    if (!m || N <= 0 || S <= 0) return 0;
+    // the setup's tables + vertex normals of up to N frames
+    return al256(smil_colour_setup_bytes(m, N, S)) + al256((size_t)N * m->V * 3 * sizeof(float));
+}
+
+extern "C" int smil_render_colour(const SmilModel *m, const SmilCameras *cam, const float *verts_world, const float *verts_ndc,
+                                  const float rgb[3], float *image, int32_t *pix_to_face, void *workspace, void *stream_) {
+    SMIL_REQUIRE(m && cam && verts_world && verts_ndc && rgb && image && workspace, "smil_render_colour: null argument");
+    SMIL_REQUIRE(cam->N > 0 && cam->views > 0 && cam->N % cam->views == 0 && cam->S > 0, "smil_render_colour: bad sizes N=%d views=%d S=%d",
+                 cam->N, cam->views, cam->S);
+    SMIL_REQUIRE(cam->R && cam->T && cam->nR > 0 && cam->nT > 0, "smil_render_colour: camera tables missing");
+    for (int k : {cam->nR, cam->nT})
+        SMIL_REQUIRE(k == 1 || k == cam->views || k == cam->N, "smil_render_colour: camera table of %d rows for %d images, %d views", k, cam->N,
+                     cam->views);
+    hipStream_t stream = (hipStream_t)stream_;
+    const int N = cam->N, S = cam->S, V = m->V, frames = N / cam->views;
+    ColourArgs a;
+    char *ws = (char *)workspace;
+    int rc = smil_colour_setup(m, verts_ndc, N, S, 0.5f * SMIL_ZNEAR, ws, stream, &a.cs);
+    if (rc) return rc;
+    float *normals = (float *)(ws + al256(smil_colour_setup_bytes(m, N, S)));
+    hipLaunchKernelGGL(k_vertex_normals, dim3(ceil_div(V, 256), frames), dim3(256), 0, stream, verts_world, m->faces, m->vf_ptr, m->vf_face, V,
+                       normals);
+    SMIL_LAUNCH_CHECK();
+    {
+        const size_t n_img = (size_t)N * 3 * S * S, n_p2f = (size_t)N * S * S;
+        const unsigned int grid = (unsigned int)std::min<size_t>((n_img + 255) / 256, (size_t)256 * 64);
+        hipLaunchKernelGGL(k_colour_background, dim3(grid), dim3(256), 0, stream, image, n_img, (int *)pix_to_face, pix_to_face ? n_p2f : 0);
+        SMIL_LAUNCH_CHECK();
+    }
+    a.verts_ndc = verts_ndc; a.verts_world = verts_world; a.normals = normals; a.faces = m->faces; a.cam = *cam;
+    a.rgb[0] = rgb[0]; a.rgb[1] = rgb[1]; a.rgb[2] = rgb[2];
+    a.image = image; a.pix_to_face = pix_to_face;
+    a.N = N; a.V = V; a.F = m->F; a.S = S; a.tiles_x = ceil_div(S, CTILE); a.views = cam->views; a.z_clip = 0.5f * SMIL_ZNEAR;
+    static int cus = 0;  // (compute units of the device, asked once)
+    if (cus == 0) {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        cus = n;
+    }
+    hipLaunchKernelGGL(k_colour_tiles, dim3((unsigned int)cus * COLOUR_WAVES_PER_CU), dim3(64), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    return SMIL_OK;
+}

@@ -547,6 +547,59 @@ def silhouette_l1_fused(model: DeviceModel, verts_ndc, S, target, target_sum, pi
     return (loss_img, d_ndc, sil, scale) if packed_out else (loss_img, d_ndc, sil)
 
 
+# ----------------------------------------------------------------------------------------------
+# colour (HardPhong)
+# ----------------------------------------------------------------------------------------------
+_COLOUR_WS: Dict = {}  # (device type, index) -> the device's colour workspace (tables only: no per-workgroup streams)
+MAX_COLOUR_WORKSPACE_BYTES = 8 << 30  # frames per colour launch shrink until the workspace fits this
+
+
+def _colour_workspace(model: DeviceModel, N: int, S: int) -> torch.Tensor:
+    need = int(_lib.load().smil_colour_workspace_bytes(model.handle, N, S))
+    key = model._ws_key()
+    ws = _COLOUR_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _COLOUR_WS[key] = torch.empty(need, dtype=torch.uint8, device=model.device)
+    return ws
+
+
+def render_colour(model: DeviceModel, cams: CameraSet, verts: torch.Tensor, mesh_color, verts_ndc: Optional[torch.Tensor] = None,
+                  want_pix_to_face: bool = False):
+    """HardPhong colour image of the reference Renderer's colour branch (p3d_renderer.py:54-70,148-150): ``verts`` (frames,V,3) world
+    space, ``mesh_color`` three floats in [0, 1] -> (N,3,S,S) float32 with N = frames * views (background 1.0), and with
+    ``want_pix_to_face`` also the (N,S,S) int32 original face id per pixel (-1: background).  ``verts_ndc``: the projection of ``verts``
+    through ``cams`` when the caller has it.  No gradient (visualisation only).  Large batches are cut into launches of whole frames."""
+    verts = verts.detach().float().contiguous()
+    frames, V = verts.shape[0], verts.shape[1]
+    views, S = cams.views, cams.S
+    N = frames * views
+    dev = verts.device
+    if verts_ndc is None:
+        verts_ndc, _ = project(cams, verts, want_yx=False)
+    verts_ndc = verts_ndc.detach().float().contiguous()
+    image = torch.empty(N, 3, S, S, dtype=torch.float32, device=dev)
+    p2f = torch.empty(N, S, S, dtype=torch.int32, device=dev) if want_pix_to_face else None
+    rgb = (ctypes.c_float * 3)(*[float(c) for c in mesh_color])
+    lib = _lib.load()
+    step = frames  # frames per launch
+    while step > 1 and int(lib.smil_colour_workspace_bytes(model.handle, step * views, S)) > MAX_COLOUR_WORKSPACE_BYTES:
+        step = (step + 1) // 2
+    ws = _colour_workspace(model, step * views, S)
+    for f0 in range(0, frames, step):
+        f1 = min(frames, f0 + step)
+        n0, n1 = f0 * views, f1 * views
+
+        def rows(t):  # camera tables with one row per image follow the slice; shared / per-view ones stay
+            return t if t is None or t.shape[0] != N or n1 - n0 == N else t[n0:n1].contiguous()
+        part = CameraSet(rows(cams.R), rows(cams.T), rows(cams.fov.reshape(-1)), rows(None if cams.aspect is None else cams.aspect.reshape(-1)),
+                         views, S)
+        c = part.struct(n1 - n0)
+        _lib.check(lib.smil_render_colour(model.handle, ctypes.byref(c), _ptr(verts[f0:f1]), _ptr(verts_ndc[n0:n1]), rgb,
+                                          _ptr(image[n0:n1]), _ptr(None if p2f is None else p2f[n0:n1]), _ptr(ws), _stream()),
+                   "smil_render_colour")
+    return (image, p2f) if want_pix_to_face else image
+
+
 def image_abs_sum(images: torch.Tensor) -> torch.Tensor:
     N = images.shape[0]
     pixels = images[0].numel()

@@ -220,8 +220,9 @@ class SMALFitter(nn.Module):
         self.rotation_mask = torch.ones(J - 1, 3, device=dev)
 
         self.smal_model = SMAL(dev, tables=tables, config=cfg)
-        self.renderer = Renderer(self.image_size, dev, views=self.views)
+        self.renderer = Renderer(self.image_size, dev, views=self.views, colour=bool(getattr(cfg, "RENDER_COLOUR", False)))
         self.renderer.bind_model(self.smal_model.device_model)
+        self.renderer.mesh_color = torch.tensor(list(cfg.MESH_COLOR), dtype=torch.float32, device=dev)[None, None, :] / 255.0
         self.fov = nn.Parameter(self.renderer.cameras.fov.clone())  # (1,) = 60 deg
 
         # device-resident targets (the reference re-uploads them every forward, fitter.py:263-266)
@@ -625,9 +626,10 @@ class SMALFitter(nn.Module):
         global_id, img_parameters, verts, faces, img_idx, epoch=epoch)`` with the SAME per-frame parameter dict (what the reference
         pickles as ``st{S}_ep{E}.pkl`` and ``load_checkpoint`` reads back), the same posed vertices (the ``.ply``) and a collage of the
         same layout (target | render | overlay | silhouette agreement | view from behind).  The reference's driver calls this
-        every ``VIS_FREQUENCY`` epochs (optimize_to_joints.py:177-178), so the unchanged loop needs it to work.  What differs: the
-        colour / HardPhong shading (p3d_renderer.py render_texture=True) and the joint markers (SMALJointDrawer, cv2) are
-        visualisation code outside this build - the "render" panels show the soft silhouette in the mesh colour, without markers.
+        every ``VIS_FREQUENCY`` epochs (optimize_to_joints.py:177-178), so the unchanged loop needs it to work.  With
+        ``FitterConfig.RENDER_COLOUR`` the render, overlay and view-from-behind panels come from the HardPhong colour image
+        (``Renderer.render_colour``, as the reference's render_texture=True); by default they show the soft silhouette in the mesh
+        colour.  The joint markers (SMALJointDrawer, cv2) are visualisation code outside this build and are not drawn.
         Frames are posed and rendered by the HIP kernels; the collage is assembled on the host."""
         cfg, dev, views, S = self.config, self.device, self.views, self.image_size
         J = self.smal_model.tables.J
@@ -666,18 +668,24 @@ class SMALFitter(nn.Module):
                     self.renderer.cameras = FoVCameras(table(cam_all.R, 9), table(cam_all.T, 3), table(fov, 1),
                                                        table(cam_all.aspect_ratio, 1), cam_all.znear, cam_all.zfar)
                     faces_b = self.smal_model.faces[None].expand(n, -1, -1)
-                    sil, _ = self.renderer(verts.contiguous(), canon, faces_b)
+                    colour = self.renderer.colour
+                    out = self.renderer(verts.contiguous(), canon, faces_b, render_texture=colour)
                     centre = verts.mean(1, keepdim=True)
-                    sil_rev, _ = self.renderer(((verts - centre) @ rot.T).contiguous(), ((canon - centre) @ rot.T).contiguous(), faces_b)
+                    out_rev = self.renderer(((verts - centre) @ rot.T).contiguous(), ((canon - centre) @ rot.T).contiguous(), faces_b,
+                                            render_texture=colour)
                     first = torch.arange(n, device=dev) * views  # a frame's first view stands for it
-                    sil = sil.reshape(n * views, 1, S, S).index_select(0, first).cpu()
-                    sil_rev = sil_rev.reshape(n * views, 1, S, S).index_select(0, first).cpu()
+                    sil = out[0].reshape(n * views, 1, S, S).index_select(0, first).cpu()
+                    sil_rev = out_rev[0].reshape(n * views, 1, S, S).index_select(0, first).cpu()
                     take = (idx * views).cpu()
                     rgb = self.rgb_imgs[take].float().cpu()
                     target_sil = torch.zeros_like(sil) if (self.rgb_only or self.sil_imgs is None) else self.sil_imgs[take].float().cpu().reshape(n, 1, S, S)
-                    rendered = sil * color
+                    if colour:  # the reference's panels (fitter.py:462-480): colour render, its overlay, colour view from behind
+                        rendered = out[2].index_select(0, first).cpu()
+                        rendered_rev = out_rev[2].index_select(0, first).cpu()
+                    else:
+                        rendered, rendered_rev = sil * color, sil_rev * color
                     agreement = (1.0 - (target_sil - sil).abs()).expand_as(rgb)
-                    collage = torch.cat([rgb, rendered, 0.5 * rendered + 0.5 * rgb, agreement, sil_rev * color], dim=3).clamp(0.0, 1.0)
+                    collage = torch.cat([rgb, rendered, 0.5 * rendered + 0.5 * rgb, agreement, rendered_rev], dim=3).clamp(0.0, 1.0)
                     for batch_id, global_id in enumerate(rows):
                         image_exporter.export((collage[batch_id].permute(1, 2, 0).numpy() * 255.0).astype(np.uint8), batch_id, global_id,
                                               self.export_parameters(global_id), verts, faces_np, img_idx, epoch=epoch)

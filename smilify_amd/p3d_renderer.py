@@ -2,8 +2,10 @@
 ``smal_fitter.p3d_renderer.Renderer`` (reference smal_fitter/p3d_renderer.py:21-152), without pytorch3d.
 
 ``forward(vertices, points, faces)`` returns ``(silhouettes (B,1,S,S), projected points (B,P,2) in (y,x) px)``.
-Gradients flow to ``vertices``, ``points`` and ``cameras.fov``.  The colour (HardPhong) branch of the
-reference is visualisation only and is not part of this build: ``render_texture=True`` raises.
+Gradients flow to ``vertices``, ``points`` and ``cameras.fov``.  The colour (HardPhong) branch of the reference is opt-in:
+``Renderer(S, device, colour=True)`` makes ``forward(..., render_texture=True)`` return ``(sil, proj, colour (B,3,S,S))`` as the
+reference does; with the default ``colour=False`` that call raises, as it always has.  ``render_colour(vertices, faces)`` is always
+available.  The colour image carries no gradient (the reference uses it under ``no_grad`` for visualisation only).
 """
 from __future__ import annotations
 
@@ -14,6 +16,7 @@ from typing import Optional
 import numpy as np
 import torch
 
+from . import config as _config
 from . import engine, model_io
 from .cameras import FoVCameras, look_at_view_transform
 
@@ -75,11 +78,14 @@ class Renderer(torch.nn.Module):
     DEFAULT_ZNEAR = 0.001  # reference p3d_renderer.py:24-25
     DEFAULT_ZFAR = 1000.0
 
-    def __init__(self, image_size, device, views: int = 1):
+    def __init__(self, image_size, device, views: int = 1, colour: bool = False):
         super().__init__()
         self.image_size = int(image_size)
         self.device = engine.require_gpu(device)
         self.views = int(views)
+        self.colour = bool(colour)
+        mesh_color = _config.current.MESH_COLOR if _config.current is not None else [0, 172, 223]  # reference :29 (config.MESH_COLOR)
+        self.mesh_color = torch.tensor(mesh_color, dtype=torch.float32, device=self.device)[None, None, :] / 255.0
         R, T = look_at_view_transform(2.7, 0, 0, device=self.device)  # reference :34
         self.cameras = FoVCameras(R, T, torch.tensor([60.0], device=self.device), None, self.DEFAULT_ZNEAR, self.DEFAULT_ZFAR)
         self.raster_settings = engine.raster_settings()
@@ -140,9 +146,23 @@ class Renderer(torch.nn.Module):
         self._bound_faces_ok[skey] = (weakref.ref(owner), found)
         return found
 
+    def _camera_set(self) -> engine.CameraSet:
+        cam = self.cameras
+        return engine.CameraSet(cam.R.contiguous(), cam.T.contiguous(), cam.fov.detach().float().reshape(-1).contiguous(),
+                                None if cam.aspect_ratio is None else cam.aspect_ratio.contiguous(), self.views, self.image_size)
+
+    def render_colour(self, vertices, faces) -> torch.Tensor:
+        """The reference's colour branch (p3d_renderer.py:54-70,148-150: hard rasteriser, K = 1, + HardPhongShader, point light at
+        (0, 0, 3), the mesh in ``mesh_color``): (B * views, 3, S, S) float32, background 1.0, image n = frame * views + view.  No
+        gradient."""
+        dm = self._device_model(faces, vertices.shape[1])
+        with torch.no_grad():
+            return engine.render_colour(dm, self._camera_set(), vertices.detach().float().contiguous(), self.mesh_color.reshape(3).tolist())
+
     def forward(self, vertices, points, faces, render_texture=False, joints_only=False):
-        if render_texture:
-            raise NotImplementedError("the colour / HardPhong branch is visualisation only and not part of this build")
+        if render_texture and not self.colour:
+            raise NotImplementedError("colour output is opt-in: construct Renderer(image_size, device, colour=True) "
+                                      "(SMALFitter: FitterConfig.RENDER_COLOUR = True), or call render_colour()")
         cam = self.cameras
         B = vertices.shape[0]
         views = self.views
@@ -156,4 +176,6 @@ class Renderer(torch.nn.Module):
         sil, proj = _RenderFunction.apply(dm, cs, self.image_size, self.raster_settings, bool(joints_only), vertices, points, cam.fov)
         if joints_only:
             return None, proj
+        if render_texture:
+            return sil, proj, self.render_colour(vertices, faces)
         return sil, proj
