@@ -402,6 +402,49 @@ int smil_adam_step_dev(float *param, const float *grad, float *exp_avg, float *e
                        float lr, float beta1, float beta2, float eps, const int32_t *step_dev, int32_t step_offset,
                        void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 3-D scan registration losses (smilify_amd/csrc/mesh3d.hip).  Replace the pytorch3d 0.7.8 ops that the reference's
+ * fitter_3d/trainer.py:3-9 imports and Stage.forward (:368-388) calls: sample_points_from_meshes, chamfer_distance,
+ * mesh_edge_loss, mesh_normal_consistency, mesh_laplacian_smoothing(method="uniform").  Deterministic: two calls on the same
+ * inputs give the same bits (no float atomics).
+ * ---------------------------------------------------------------------------------------- */
+/* sample_points_from_meshes (trainer.py:376): S points per mesh of N packed meshes.  verts (n_verts,3); faces (F_total,3) indices
+ * into the packed verts; face_off (N+1) the first face of every mesh; cum_area (F_total) float64, the mesh's inclusive cumulative
+ * face areas divided by its total (last entry 1; a mesh of zero area gives zero points).  Face ~ area, barycentrics of pytorch3d's
+ * _rand_barycentric_coords, random numbers from Philox4x32-10 keyed by (seed, mesh, sample).  out (N,S,3); out_face (N,S) the
+ * face index within its mesh, or NULL. */
+int smil_sample_points(const float *verts, int32_t n_verts, const int32_t *faces, const int32_t *face_off, const double *cum_area,
+                       int32_t N, int32_t S, uint64_t seed, float *out, int32_t *out_face, void *stream);
+
+/* chamfer_distance(x, y) (trainer.py:379) with norm=2, no lengths or normals: x (N,P1,3), y (N,P2,3) ->
+ * loss[0] = red_n [ red_i min_j |x_i - y_j|^2 + red_j min_i |y_j - x_i|^2 ], red = mean (or sum with point_sum / batch_sum); the
+ * second half is dropped when single_directional.  idx_x (N,P1) / idx_y (N,P2): the argmin (smallest index on a tie) or NULL.
+ * d_x (N,P1,3), d_y (N,P2,3): dloss/dx, dloss/dy (both or neither).  workspace: smil_chamfer_workspace_bytes. */
+size_t smil_chamfer_workspace_bytes(int32_t N, int32_t P1, int32_t P2);
+int smil_chamfer(const float *x, const float *y, int32_t N, int32_t P1, int32_t P2, int32_t single_directional, int32_t point_sum,
+                 int32_t batch_sum, float *loss, int32_t *idx_x, int32_t *idx_y, float *d_x, float *d_y, void *workspace, void *stream);
+
+/* Topology tables of one face array, built once by the caller and shared by B meshes (device pointers). */
+typedef struct {
+    int32_t V, E, Q;            /* vertices, unique edges, normal-consistency face pairs */
+    const int32_t *edges;       /* (E,2) v0 < v1 (Meshes.edges_packed) */
+    const int32_t *pairs;       /* (Q,4) (v0, v1, a, b): edge v0 v1 and the opposite vertices of two faces sharing it */
+    const int32_t *nbr_ptr;     /* (V+1) Laplacian neighbour CSR: the edge neighbours of every vertex */
+    const int32_t *nbr;         /* (2E) */
+    const float *inv_deg;       /* (V) 1/deg, 0 for an isolated vertex */
+    const int32_t *vpair_ptr;   /* (V+1) vertex -> pair incidence CSR */
+    const int32_t *vpair;       /* (4Q) pair * 4 + role (0: v0, 1: v1, 2: a, 3: b) */
+} SmilMeshTopology;
+#define SMIL_REG_EDGE 1
+#define SMIL_REG_NORMAL 2
+#define SMIL_REG_LAPLACIAN 4
+/* mesh_edge_loss / mesh_normal_consistency / mesh_laplacian_smoothing("uniform") (trainer.py:383-396) of B meshes verts (B,V,3) on one
+ * topology: out3 = {edge, normal, laplacian} (each: per-mesh mean, then mean over meshes; terms not in the mask are 0).  d_edge,
+ * d_normal, d_lap (B,V,3): the gradients of out3[0..2], or NULL.  workspace: smil_mesh_reg_workspace_bytes. */
+size_t smil_mesh_reg_workspace_bytes(const SmilMeshTopology *t, int32_t B);
+int smil_mesh_regularisers(const SmilMeshTopology *t, const float *verts, int32_t B, int32_t terms, float *out3, float *d_edge,
+                           float *d_normal, float *d_lap, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

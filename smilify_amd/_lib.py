@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SMILFIT_LIB: load another build of the same library (instrumented builds under tools/dbg); never a CPU path
@@ -21,6 +21,7 @@ EXPORTS = [
     "smil_silhouette_l1_fused", "smil_prior_losses", "smil_mask_rows", "smil_joint_loss", "smil_pix_scale",
     "smil_image_abs_sum", "smil_sil_objective", "smil_window_terms", "smil_adam_step", "smil_adam_step_multi", "smil_adam_step_dev", "smil_profile_enable",
     "smil_profile_read", "smil_colour_workspace_bytes", "smil_render_colour",
+    "smil_sample_points", "smil_chamfer_workspace_bytes", "smil_chamfer", "smil_mesh_reg_workspace_bytes", "smil_mesh_regularisers",
 ]
 
 N_OBJS = 10
@@ -86,6 +87,13 @@ class FitConfig(Structure):
                 ("limit", c_float), ("train_global", c_int32), ("train_joints", c_int32), ("train_trans", c_int32)]
 
 
+class MeshTopology(Structure):
+    _fields_ = [("V", c_int32), ("E", c_int32), ("Q", c_int32)] + [
+        (n, c_void_p) for n in ("edges", "pairs", "nbr_ptr", "nbr", "inv_deg", "vpair_ptr", "vpair")]
+
+
+REG_EDGE, REG_NORMAL, REG_LAPLACIAN = 1, 2, 4
+
 _lib = None
 
 
@@ -148,6 +156,14 @@ def load():
     lib.smil_colour_workspace_bytes.restype = c_size_t
     lib.smil_render_colour.argtypes = [c_void_p, POINTER(Cameras), c_void_p, c_void_p, POINTER(c_float), c_void_p, c_void_p, c_void_p,
                                        c_void_p]
+    lib.smil_sample_points.argtypes = [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_void_p, c_void_p,
+                                       c_void_p]
+    lib.smil_chamfer_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
+    lib.smil_chamfer_workspace_bytes.restype = c_size_t
+    lib.smil_chamfer.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 7
+    lib.smil_mesh_reg_workspace_bytes.argtypes = [POINTER(MeshTopology), c_int32]
+    lib.smil_mesh_reg_workspace_bytes.restype = c_size_t
+    lib.smil_mesh_regularisers.argtypes = [POINTER(MeshTopology), c_void_p, c_int32, c_int32] + [c_void_p] * 6
     lib.smil_profile_enable.argtypes = [c_int32]
     lib.smil_profile_read.argtypes = [POINTER(c_float), POINTER(c_int32)]
     for name in EXPORTS:

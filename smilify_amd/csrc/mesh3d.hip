@@ -1,0 +1,474 @@
+// 3-D scan registration losses for gfx950: the loss half of the reference's fitter_3d/trainer.py Stage.forward (:368-388).
+//
+// Replaces (reference): pytorch3d 0.7.8 (un-vendored) ops.sample_points_from_meshes, loss.chamfer_distance, loss.mesh_edge_loss,
+// loss.mesh_normal_consistency and loss.mesh_laplacian_smoothing(method="uniform"), as fitter_3d/trainer.py:3-9 imports them.
+//
+//  * k_sample_points     lane per sample: a counter-based Philox4x32-10 draw keyed by (seed, mesh, sample), the face by binary search
+//                        in the mesh's normalised cumulative-area table (float64, built once on the host), barycentrics
+//                        w0 = 1 - sqrt(u), w1 = sqrt(u)(1 - v), w2 = sqrt(u) v (pytorch3d _rand_barycentric_coords).
+//  * k_chamfer_nn        lane = CH_QPT query points, both directions in one launch; candidates stream through LDS as float4 and every
+//                        lane reads the same one (a broadcast).  Direct form sum (q - c)^2, running min with a strict <.  Candidate
+//                        ranges may be split across workgroups; the splits merge through a 64-bit atomicMin of (distance bits, index),
+//                        which is order independent (distances are >= 0, so their bits order like the values; ties go to the
+//                        smaller index, as a sequential scan with < gives).
+//  * k_chamfer_owned     thread per query: argmin out, the owned gradient 2 w (q - c*), and the scattered side (c* - q) added to the
+//                        candidate's int64 fixed-point accumulator (2^-32 units: integer sums do not depend on the order).
+//  * k_chamfer_scatter   thread per point: the scattered sum converted and added to the owned gradient.
+//  * k_chamfer_reduce    per (mesh, direction) sums of the minima in a fixed order, then the batch in a fixed order.
+//  * k_mesh_reg          edge, normal consistency and uniform Laplacian terms and their gradients in one pass: thread t evaluates edge
+//                        term t, normal pair t and Laplacian row t for the loss, and gathers vertex t's gradient from its neighbour and
+//                        pair incidence lists (recomputing the few terms it touches: no atomics).  Per-block partials, then
+//                        k_mesh_reg_reduce in a fixed order.
+#include <algorithm>
+
+#include "common.h"
+
+#define CH_BLOCK 256
+#define CH_QPT 4                      // query points per lane of k_chamfer_nn
+#define CH_TILE 256                   // candidates staged in LDS per step
+#define CH_FIX 4294967296.0           // fixed-point scale of the scattered gradient sums (2^32)
+#define REG_BLOCK 256
+
+// ---------------------------------------------------------------------------------------------
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC 2011)
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t lo0 = 0xD2511F53u * c.x, hi0 = __umulhi(0xD2511F53u, c.x);
+        const uint32_t lo1 = 0xCD9E8D57u * c.z, hi1 = __umulhi(0xCD9E8D57u, c.z);
+        c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
+        k.x += 0x9E3779B9u;
+        k.y += 0xBB67AE85u;
+    }
+    return c;
+}
+
+// ---------------------------------------------------------------------------------------------
+// surface sampling
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_sample_points(const float *__restrict__ verts, const int *__restrict__ faces,
+                                                       const int *__restrict__ face_off, const double *__restrict__ cum, int S,
+                                                       uint32_t seed_lo, uint32_t seed_hi, float *__restrict__ out,
+                                                       int *__restrict__ out_face) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    const int n = blockIdx.y;
+    if (s >= S) return;
+    const size_t o = (size_t)n * S + s;
+    const int f0 = face_off[n], f1 = face_off[n + 1];
+    if (f1 <= f0 || !(cum[f1 - 1] > 0.0)) {  // no faces / no area: zeros (pytorch3d leaves empty meshes' samples at 0)
+        out[3 * o] = 0.f; out[3 * o + 1] = 0.f; out[3 * o + 2] = 0.f;
+        if (out_face) out_face[o] = -1;
+        return;
+    }
+    const uint4 r = philox4x32_10(make_uint4((uint32_t)s, (uint32_t)n, 0u, 0u), make_uint2(seed_lo, seed_hi));
+    const double uf = (double)(((uint64_t)r.x << 21) ^ (uint64_t)(r.y >> 11)) * (1.0 / 9007199254740992.0);  // [0, 1), 53 bits
+    // first face whose cumulative (normalised) area exceeds uf: zero-area faces are never chosen
+    int lo = f0, hi = f1 - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (cum[mid] > uf) hi = mid;
+        else lo = mid + 1;
+    }
+    const float u = (float)(r.z >> 8) * (1.0f / 16777216.0f), v = (float)(r.w >> 8) * (1.0f / 16777216.0f);
+    const float su = sqrtf(u);
+    const float w0 = 1.0f - su, w1 = su * (1.0f - v), w2 = su * v;
+    const float *a = verts + 3 * (size_t)faces[3 * lo], *b = verts + 3 * (size_t)faces[3 * lo + 1], *c = verts + 3 * (size_t)faces[3 * lo + 2];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[3 * o + k] = w0 * a[k] + w1 * b[k] + w2 * c[k];
+    if (out_face) out_face[o] = lo - f0;
+}
+
+extern "C" int smil_sample_points(const float *verts, int32_t n_verts, const int32_t *faces, const int32_t *face_off, const double *cum_area,
+                                  int32_t N, int32_t S, uint64_t seed, float *out, int32_t *out_face, void *stream_) {
+    SMIL_REQUIRE(verts && faces && face_off && cum_area && out, "smil_sample_points: null argument");
+    SMIL_REQUIRE(N > 0 && S > 0 && n_verts > 0, "smil_sample_points: bad sizes N=%d S=%d V=%d", N, S, n_verts);
+    SMIL_REQUIRE(N <= 65535, "smil_sample_points: N=%d meshes exceeds one launch (65535)", N);
+    hipStream_t stream = (hipStream_t)stream_;
+    hipLaunchKernelGGL(k_sample_points, dim3(ceil_div(S, 256), N), dim3(256), 0, stream, verts, (const int *)faces, (const int *)face_off,
+                       cum_area, S, (uint32_t)seed, (uint32_t)(seed >> 32), out, (int *)out_face);
+    SMIL_LAUNCH_CHECK();
+    return SMIL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// chamfer distance
+// ---------------------------------------------------------------------------------------------
+struct ChamferArgs {
+    const float *pts[2];      // (N, P[d], 3): direction d's queries are pts[d], its candidates pts[1 - d]
+    int P[2];
+    int N, dirs, splits;
+    float w[2];               // loss weight of one term of direction d (1/P and/or 1/N as reduced)
+    unsigned long long *key;  // (N, P[0] + P[1]) {distance bits, candidate index}: direction 0's queries first
+    float *dist;              // (N, P[0] + P[1])
+    long long *acc;           // (N, P[0] + P[1], 3) fixed-point scattered sums, per point of either cloud
+    int *idx[2];              // (N, P[d]) or NULL
+    float *grad[2];           // (N, P[d], 3) or NULL
+    float *part;              // (N, dirs)
+    float *loss;              // (1)
+};
+
+__device__ __forceinline__ size_t ch_row(const ChamferArgs &a, int n, int d) { return (size_t)n * (a.P[0] + a.P[1]) + (d ? a.P[0] : 0); }
+
+__global__ void __launch_bounds__(CH_BLOCK) k_chamfer_nn(ChamferArgs a) {
+    __shared__ float4 tile[CH_TILE];
+    const int d = blockIdx.z % a.dirs, n = blockIdx.z / a.dirs;
+    const int Pq = a.P[d], Pc = a.P[1 - d];
+    const int q0 = blockIdx.x * (CH_BLOCK * CH_QPT);
+    if (q0 >= Pq) return;  // (block-uniform)
+    const int chunk = ((Pc + a.splits - 1) / a.splits + CH_TILE - 1) / CH_TILE * CH_TILE;
+    const int c_begin = blockIdx.y * chunk, c_end = min(Pc, c_begin + chunk);
+    if (c_begin >= c_end) return;
+    const float *Q = a.pts[d] + (size_t)n * Pq * 3;
+    const float *C = a.pts[1 - d] + (size_t)n * Pc * 3;
+    float qx[CH_QPT], qy[CH_QPT], qz[CH_QPT], best[CH_QPT];
+    int bi[CH_QPT];
+#pragma unroll
+    for (int k = 0; k < CH_QPT; ++k) {
+        const int q = q0 + k * CH_BLOCK + threadIdx.x;
+        const int qc = q < Pq ? q : Pq - 1;
+        qx[k] = Q[3 * qc]; qy[k] = Q[3 * qc + 1]; qz[k] = Q[3 * qc + 2];
+        best[k] = __builtin_inff();
+        bi[k] = 0x7FFFFFFF;
+    }
+    for (int c0 = c_begin; c0 < c_end; c0 += CH_TILE) {
+        const int cnt = min(CH_TILE, c_end - c0);
+        __syncthreads();
+        if ((int)threadIdx.x < cnt) {
+            const float *p = C + 3 * (size_t)(c0 + threadIdx.x);
+            tile[threadIdx.x] = make_float4(p[0], p[1], p[2], 0.f);
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int j = 0; j < cnt; ++j) {
+            const float4 c = tile[j];
+#pragma unroll
+            for (int k = 0; k < CH_QPT; ++k) {
+                const float dx = qx[k] - c.x, dy = qy[k] - c.y, dz = qz[k] - c.z;
+                const float dd = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+                if (dd < best[k]) { best[k] = dd; bi[k] = c0 + j; }
+            }
+        }
+    }
+    unsigned long long *key = a.key + ch_row(a, n, d);
+#pragma unroll
+    for (int k = 0; k < CH_QPT; ++k) {
+        const int q = q0 + k * CH_BLOCK + threadIdx.x;
+        if (q < Pq) {
+            const unsigned long long kv = ((unsigned long long)__float_as_uint(best[k]) << 32) | (unsigned long long)(uint32_t)bi[k];
+            if (a.splits == 1) key[q] = kv;
+            else atomicMin(&key[q], kv);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_chamfer_owned(ChamferArgs a) {
+    const int d = blockIdx.z % a.dirs, n = blockIdx.z / a.dirs;
+    const int Pq = a.P[d], Pc = a.P[1 - d];
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= Pq) return;
+    const size_t r = ch_row(a, n, d) + q;
+    const unsigned long long kv = a.key[r];
+    const int j = (int)(uint32_t)(kv & 0xFFFFFFFFull);
+    a.dist[r] = __uint_as_float((uint32_t)(kv >> 32));
+    if (a.idx[d]) a.idx[d][(size_t)n * Pq + q] = j;
+    if (!a.grad[0]) return;
+    if (j < 0 || j >= Pc) return;  // (every query sees at least one candidate: P >= 1 is checked on the host)
+    const float *Q = a.pts[d] + ((size_t)n * Pq + q) * 3;
+    const float *Cp = a.pts[1 - d] + ((size_t)n * Pc + j) * 3;
+    const float e[3] = {Q[0] - Cp[0], Q[1] - Cp[1], Q[2] - Cp[2]};
+    if (a.grad[d]) {
+        float *g = a.grad[d] + ((size_t)n * Pq + q) * 3;
+        const float s = 2.0f * a.w[d];
+        g[0] = s * e[0]; g[1] = s * e[1]; g[2] = s * e[2];
+    }
+    if (a.grad[1 - d]) {  // candidate j receives 2 w_d (c - q): accumulated as integers, so the order of the additions does not matter
+        long long *acc = a.acc + (ch_row(a, n, 1 - d) + j) * 3;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            atomicAdd((unsigned long long *)&acc[k], (unsigned long long)__double2ll_rn(-(double)e[k] * CH_FIX));
+    }
+}
+
+// both clouds' points: the scattered sums of direction 1 - s land on cloud s's points, weighted by w[1 - s]
+__global__ void __launch_bounds__(256) k_chamfer_scatter(ChamferArgs a) {
+    const int side = blockIdx.z & 1, n = blockIdx.z >> 1;
+    const int P = a.P[side];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P || !a.grad[side]) return;
+    const bool has_owned = side < a.dirs;  // (single_directional: cloud 1 owns no term)
+    const bool receives = 1 - side < a.dirs;
+    float *g = a.grad[side] + ((size_t)n * P + i) * 3;
+    const long long *acc = a.acc + (ch_row(a, n, side) + i) * 3;
+    const float s = receives ? 2.0f * a.w[1 - side] : 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float sc = receives ? (float)((double)acc[k] * (1.0 / CH_FIX)) * s : 0.f;
+        g[k] = (has_owned ? g[k] : 0.f) + sc;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_chamfer_reduce(ChamferArgs a) {
+    __shared__ float red[16];
+    const int d = blockIdx.x % a.dirs, n = blockIdx.x / a.dirs;
+    const int P = a.P[d];
+    const float *dist = a.dist + ch_row(a, n, d);
+    float s = 0.f;
+    for (int i = threadIdx.x; i < P; i += blockDim.x) s += dist[i];
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) a.part[blockIdx.x] = s * a.w[d];
+}
+
+__global__ void __launch_bounds__(64) k_chamfer_total(const float *__restrict__ part, int n, float *__restrict__ loss) {
+    float s = 0.f;
+    for (int i = threadIdx.x; i < n; i += 64) s += part[i];
+    s = wave_sum(s);
+    if (threadIdx.x == 0) loss[0] = s;
+}
+
+static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+extern "C" size_t smil_chamfer_workspace_bytes(int32_t N, int32_t P1, int32_t P2) {
+    if (N <= 0 || P1 <= 0 || P2 <= 0) return 0;
+    const size_t pts = (size_t)N * ((size_t)P1 + P2);
+    return al256(pts * 8) + al256(pts * 4) + al256(pts * 3 * 8) + al256((size_t)N * 2 * 4);
+}
+
+extern "C" int smil_chamfer(const float *x, const float *y, int32_t N, int32_t P1, int32_t P2, int32_t single_directional,
+                            int32_t point_sum, int32_t batch_sum, float *loss, int32_t *idx_x, int32_t *idx_y, float *d_x, float *d_y,
+                            void *workspace, void *stream_) {
+    SMIL_REQUIRE(x && y && loss && workspace, "smil_chamfer: null argument");
+    SMIL_REQUIRE(N > 0 && P1 > 0 && P2 > 0, "smil_chamfer: bad sizes N=%d P1=%d P2=%d", N, P1, P2);
+    SMIL_REQUIRE(N <= 32767, "smil_chamfer: N=%d exceeds one launch (32767)", N);
+    SMIL_REQUIRE((d_x == nullptr) == (d_y == nullptr), "smil_chamfer: d_x and d_y are given together or not at all");
+    SMIL_REQUIRE(!(single_directional && idx_y), "smil_chamfer: idx_y has no meaning when single_directional");
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t pts = (size_t)N * ((size_t)P1 + P2);
+    ChamferArgs a;
+    char *ws = (char *)workspace;
+    a.key = (unsigned long long *)ws;
+    a.dist = (float *)(ws + al256(pts * 8));
+    a.acc = (long long *)(ws + al256(pts * 8) + al256(pts * 4));
+    a.part = (float *)(ws + al256(pts * 8) + al256(pts * 4) + al256(pts * 3 * 8));
+    a.pts[0] = x; a.pts[1] = y;
+    a.P[0] = P1; a.P[1] = P2;
+    a.N = N; a.dirs = single_directional ? 1 : 2;
+    const float bw = batch_sum ? 1.0f : 1.0f / (float)N;
+    a.w[0] = (point_sum ? 1.0f : 1.0f / (float)P1) * bw;
+    a.w[1] = (point_sum ? 1.0f : 1.0f / (float)P2) * bw;
+    a.idx[0] = idx_x; a.idx[1] = idx_y;
+    a.grad[0] = d_x; a.grad[1] = d_y;
+    a.loss = loss;
+    // candidate splits: enough workgroups for the whole GPU (>= 2048) while every split still streams >= 4 tiles
+    const int qblocks = ceil_div(std::max(P1, P2), CH_BLOCK * CH_QPT);
+    const int base = qblocks * N * a.dirs;
+    const int max_split = std::max(1, std::min(P1, P2) / (4 * CH_TILE));
+    a.splits = std::max(1, std::min(max_split, ceil_div(2048, base)));
+    SMIL_HIP(hipMemsetAsync(a.key, 0xFF, pts * 8, stream));
+    if (d_x) SMIL_HIP(hipMemsetAsync(a.acc, 0, pts * 3 * 8, stream));
+    hipLaunchKernelGGL(k_chamfer_nn, dim3(qblocks, a.splits, N * a.dirs), dim3(CH_BLOCK), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_chamfer_owned, dim3(ceil_div(std::max(P1, P2), 256), 1, N * a.dirs), dim3(256), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    if (d_x) {
+        hipLaunchKernelGGL(k_chamfer_scatter, dim3(ceil_div(std::max(P1, P2), 256), 1, N * 2), dim3(256), 0, stream, a);
+        SMIL_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_chamfer_reduce, dim3(N * a.dirs), dim3(256), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_chamfer_total, dim3(1), dim3(64), 0, stream, (const float *)a.part, N * a.dirs, loss);
+    SMIL_LAUNCH_CHECK();
+    return SMIL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// mesh regularisers (shared topology of B meshes)
+// ---------------------------------------------------------------------------------------------
+struct RegArgs {
+    SmilMeshTopology t;
+    const float *verts;  // (B, V, 3)
+    int B, terms;
+    float *d_edge, *d_normal, *d_lap;  // (B, V, 3) or NULL
+    float *part;                       // (B, nblk, 3)
+    float *out;                        // (3): edge, normal, laplacian
+    float *per_mesh;                   // (B, 3)
+};
+
+__device__ __forceinline__ void ld3(const float *X, int v, float (&p)[3]) { p[0] = X[3 * v]; p[1] = X[3 * v + 1]; p[2] = X[3 * v + 2]; }
+__device__ __forceinline__ void cross3(const float (&a)[3], const float (&b)[3], float (&c)[3]) {
+    c[0] = a[1] * b[2] - a[2] * b[1];
+    c[1] = a[2] * b[0] - a[0] * b[2];
+    c[2] = a[0] * b[1] - a[1] * b[0];
+}
+__device__ __forceinline__ float dot3(const float (&a)[3], const float (&b)[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+
+// one normal-consistency pair (v0, v1, a, b): n0 = e x (a - v0), n1 = -e x (b - v0), term 1 - cos(n0, n1) (torch.cosine_similarity: each
+// vector divided by max(|n|, 1e-8)).  With gd != NULL, the gradient of the term at the pair's four vertices (v0, v1, a, b).
+__device__ __forceinline__ float normal_pair(const float *X, int4 p, float (*gd)[3]) {
+    float P0[3], P1[3], A[3], Bv[3];
+    ld3(X, p.x, P0); ld3(X, p.y, P1); ld3(X, p.z, A); ld3(X, p.w, Bv);
+    float e[3], u[3], w[3];
+    for (int k = 0; k < 3; ++k) { e[k] = P1[k] - P0[k]; u[k] = A[k] - P0[k]; w[k] = Bv[k] - P0[k]; }
+    float n0[3], n1[3];
+    cross3(e, u, n0);
+    cross3(e, w, n1);
+    for (int k = 0; k < 3; ++k) n1[k] = -n1[k];
+    const float l0 = fmaxf(sqrtf(dot3(n0, n0)), 1e-8f), l1 = fmaxf(sqrtf(dot3(n1, n1)), 1e-8f);
+    float h0[3], h1[3];
+    for (int k = 0; k < 3; ++k) { h0[k] = n0[k] / l0; h1[k] = n1[k] / l1; }
+    const float c = dot3(h0, h1);
+    if (gd) {
+        // d(-cos)/dn0 = -(h1 - c h0) / l0, d(-cos)/dn1 = -(h0 - c h1) / l1
+        float g0[3], g1[3];
+        for (int k = 0; k < 3; ++k) { g0[k] = -(h1[k] - c * h0[k]) / l0; g1[k] = (h0[k] - c * h1[k]) / l1; }  // g1: through n1 = -(e x w)
+        // n = e x u: de += u x g, du += g x e
+        float ue[3], uu[3], we[3], ww[3];
+        cross3(u, g0, ue); cross3(g0, e, uu);
+        cross3(w, g1, we); cross3(g1, e, ww);
+        for (int k = 0; k < 3; ++k) {
+            const float de = ue[k] + we[k];
+            gd[0][k] = -de - uu[k] - ww[k];
+            gd[1][k] = de;
+            gd[2][k] = uu[k];
+            gd[3][k] = ww[k];
+        }
+    }
+    return 1.0f - c;
+}
+
+// Laplacian residual of row i: (1/deg) sum_{j in N(i)} v_j - v_i, summed as (1/deg) sum (v_j - v_i): the neighbour differences are
+// small and exact where the coordinates are not, so a short residual keeps its direction (which is its gradient).  Isolated: -v_i.
+__device__ __forceinline__ void lap_row(const SmilMeshTopology &t, const float *X, int i, float (&r)[3]) {
+    const int e0 = t.nbr_ptr[i], e1 = t.nbr_ptr[i + 1];
+    if (e0 == e1) {
+        for (int k = 0; k < 3; ++k) r[k] = -X[3 * i + k];
+        return;
+    }
+    float s[3] = {0.f, 0.f, 0.f};
+    for (int e = e0; e < e1; ++e) {
+        const int j = t.nbr[e];
+        for (int k = 0; k < 3; ++k) s[k] += X[3 * j + k] - X[3 * i + k];
+    }
+    const float id = t.inv_deg[i];
+    for (int k = 0; k < 3; ++k) r[k] = s[k] * id;
+}
+
+__global__ void __launch_bounds__(REG_BLOCK) k_mesh_reg(RegArgs a) {
+    __shared__ float red[16];
+    const SmilMeshTopology &t = a.t;
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const float *X = a.verts + (size_t)b * t.V * 3;
+    const float invB = 1.0f / (float)a.B;
+    float le = 0.f, ln = 0.f, ll = 0.f;
+    if ((a.terms & SMIL_REG_EDGE) && i < t.E) {
+        const int2 e = make_int2(t.edges[2 * i], t.edges[2 * i + 1]);
+        float d[3];
+        for (int k = 0; k < 3; ++k) d[k] = X[3 * e.x + k] - X[3 * e.y + k];
+        le = dot3(d, d);
+    }
+    if ((a.terms & SMIL_REG_NORMAL) && i < t.Q) {
+        const int4 p = make_int4(t.pairs[4 * i], t.pairs[4 * i + 1], t.pairs[4 * i + 2], t.pairs[4 * i + 3]);
+        ln = normal_pair(X, p, nullptr);
+    }
+    if (i < t.V) {
+        const size_t o = ((size_t)b * t.V + i) * 3;
+        float r[3];
+        if (a.terms & SMIL_REG_LAPLACIAN) {
+            lap_row(t, X, i, r);
+            ll = sqrtf(dot3(r, r));
+        }
+        if ((a.terms & SMIL_REG_EDGE) && a.d_edge) {  // sum over the edges at i of 2 (v_i - v_j) / E
+            float g[3] = {0.f, 0.f, 0.f};
+            for (int e = t.nbr_ptr[i]; e < t.nbr_ptr[i + 1]; ++e) {
+                const int j = t.nbr[e];
+                for (int k = 0; k < 3; ++k) g[k] += X[3 * i + k] - X[3 * j + k];
+            }
+            const float s = t.E > 0 ? 2.0f / (float)t.E * invB : 0.f;
+            for (int k = 0; k < 3; ++k) a.d_edge[o + k] = g[k] * s;
+        }
+        if ((a.terms & SMIL_REG_LAPLACIAN) && a.d_lap) {  // -ghat_i + sum_{j in N(i)} ghat_j / deg_j, ghat = r / |r| (0 at |r| = 0)
+            float g[3];
+            const float inv = ll > 0.f ? 1.0f / ll : 0.f;
+            for (int k = 0; k < 3; ++k) g[k] = -r[k] * inv;
+            for (int e = t.nbr_ptr[i]; e < t.nbr_ptr[i + 1]; ++e) {
+                const int j = t.nbr[e];
+                float rj[3];
+                lap_row(t, X, j, rj);
+                const float nj = sqrtf(dot3(rj, rj));
+                const float sj = nj > 0.f ? t.inv_deg[j] / nj : 0.f;
+                for (int k = 0; k < 3; ++k) g[k] += rj[k] * sj;
+            }
+            const float s = 1.0f / (float)t.V * invB;
+            for (int k = 0; k < 3; ++k) a.d_lap[o + k] = g[k] * s;
+        }
+        if ((a.terms & SMIL_REG_NORMAL) && a.d_normal) {
+            float g[3] = {0.f, 0.f, 0.f};
+            for (int e = t.vpair_ptr[i]; e < t.vpair_ptr[i + 1]; ++e) {
+                const int code = t.vpair[e], q = code >> 2, role = code & 3;
+                const int4 p = make_int4(t.pairs[4 * q], t.pairs[4 * q + 1], t.pairs[4 * q + 2], t.pairs[4 * q + 3]);
+                float gd[4][3];
+                normal_pair(X, p, gd);
+                for (int k = 0; k < 3; ++k) g[k] += gd[role][k];
+            }
+            const float s = t.Q > 0 ? 1.0f / (float)t.Q * invB : 0.f;
+            for (int k = 0; k < 3; ++k) a.d_normal[o + k] = g[k] * s;
+        }
+    }
+    le = block_sum(le, red);
+    ln = block_sum(ln, red);
+    ll = block_sum(ll, red);
+    if (threadIdx.x == 0) {
+        float *p = a.part + ((size_t)b * gridDim.x + blockIdx.x) * 3;
+        p[0] = le; p[1] = ln; p[2] = ll;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_mesh_reg_reduce(RegArgs a, int nblk) {
+    const SmilMeshTopology &t = a.t;
+    const float cnt[3] = {(float)t.E, (float)t.Q, (float)t.V};
+    for (int w = threadIdx.x; w < a.B * 3; w += blockDim.x) {
+        const int b = w / 3, k = w % 3;
+        float s = 0.f;
+        for (int j = 0; j < nblk; ++j) s += a.part[((size_t)b * nblk + j) * 3 + k];
+        a.per_mesh[w] = cnt[k] > 0.f ? s / cnt[k] : 0.f;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        float s = 0.f;
+        for (int b = 0; b < a.B; ++b) s += a.per_mesh[b * 3 + threadIdx.x];
+        a.out[threadIdx.x] = s / (float)a.B;
+    }
+}
+
+extern "C" size_t smil_mesh_reg_workspace_bytes(const SmilMeshTopology *t, int32_t B) {
+    if (!t || B <= 0 || t->V <= 0) return 0;
+    const int nblk = ceil_div(std::max(std::max(t->V, t->E), std::max(t->Q, 1)), REG_BLOCK);
+    return al256((size_t)B * nblk * 3 * 4) + al256((size_t)B * 3 * 4);
+}
+
+extern "C" int smil_mesh_regularisers(const SmilMeshTopology *t, const float *verts, int32_t B, int32_t terms, float *out3, float *d_edge,
+                                      float *d_normal, float *d_lap, void *workspace, void *stream_) {
+    SMIL_REQUIRE(t && verts && out3 && workspace, "smil_mesh_regularisers: null argument");
+    SMIL_REQUIRE(B > 0 && B <= 65535 && t->V > 0 && t->E >= 0 && t->Q >= 0, "smil_mesh_regularisers: bad sizes B=%d V=%d E=%d Q=%d", B, t->V,
+                 t->E, t->Q);
+    SMIL_REQUIRE(terms > 0 && (terms & ~(SMIL_REG_EDGE | SMIL_REG_NORMAL | SMIL_REG_LAPLACIAN)) == 0, "smil_mesh_regularisers: bad terms mask %d",
+                 terms);
+    SMIL_REQUIRE(t->nbr_ptr && t->inv_deg && (t->E == 0 || (t->edges && t->nbr)) && (t->Q == 0 || (t->pairs && t->vpair && t->vpair_ptr)),
+                 "smil_mesh_regularisers: topology tables missing");
+    SMIL_REQUIRE(t->vpair_ptr || !(terms & SMIL_REG_NORMAL) || !d_normal, "smil_mesh_regularisers: vertex -> pair table missing");
+    hipStream_t stream = (hipStream_t)stream_;
+    RegArgs a;
+    a.t = *t;
+    a.verts = verts; a.B = B; a.terms = terms;
+    a.d_edge = d_edge; a.d_normal = d_normal; a.d_lap = d_lap;
+    const int nblk = ceil_div(std::max(std::max(t->V, t->E), std::max(t->Q, 1)), REG_BLOCK);
+    a.part = (float *)workspace;
+    a.per_mesh = (float *)((char *)workspace + al256((size_t)B * nblk * 3 * 4));
+    a.out = out3;
+    hipLaunchKernelGGL(k_mesh_reg, dim3(nblk, B), dim3(REG_BLOCK), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_mesh_reg_reduce, dim3(1), dim3(256), 0, stream, a, nblk);
+    SMIL_LAUNCH_CHECK();
+    return SMIL_OK;
+}

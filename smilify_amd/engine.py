@@ -699,3 +699,62 @@ def profile_read():
     ms, n = ctypes.c_float(), ctypes.c_int32()
     _lib.check(_lib.load().smil_profile_read(ctypes.byref(ms), ctypes.byref(n)), "smil_profile_read")
     return float(ms.value), int(n.value)
+
+
+# ---- 3-D scan registration losses (mesh3d.hip) ------------------------------------------------------------------------------
+def sample_points(verts_packed: torch.Tensor, faces_packed: torch.Tensor, face_off: torch.Tensor, cum_area: torch.Tensor, n_meshes: int,
+                  num_samples: int, seed: int, want_faces: bool = False):
+    """(N, S, 3) surface samples of N packed meshes; faces_packed (F,3) int32 into the packed verts, face_off (N+1) int32,
+    cum_area (F) float64 per-mesh normalised cumulative areas.  With want_faces also the (N, S) face index within each mesh."""
+    dev = verts_packed.device
+    out = torch.empty(n_meshes, num_samples, 3, device=dev, dtype=torch.float32)
+    fidx = torch.empty(n_meshes, num_samples, device=dev, dtype=torch.int32) if want_faces else None
+    _lib.check(_lib.load().smil_sample_points(_ptr(verts_packed), int(verts_packed.shape[0]), _ptr(faces_packed), _ptr(face_off),
+                                              _ptr(cum_area), int(n_meshes), int(num_samples), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out),
+                                              _ptr(fidx), _stream()), "smil_sample_points")
+    return out, fidx
+
+
+def chamfer(x: torch.Tensor, y: torch.Tensor, single_directional=False, point_sum=False, batch_sum=False, want_grad=True):
+    """Chamfer loss of x (N,P1,3) and y (N,P2,3): (loss (1,), idx_x (N,P1), idx_y (N,P2) or None, d_x, d_y or None)."""
+    N, P1, P2 = int(x.shape[0]), int(x.shape[1]), int(y.shape[1])
+    dev = x.device
+    lib = _lib.load()
+    ws = torch.empty(int(lib.smil_chamfer_workspace_bytes(N, P1, P2)), dtype=torch.uint8, device=dev)
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    idx_x = torch.empty(N, P1, device=dev, dtype=torch.int32)
+    idx_y = None if single_directional else torch.empty(N, P2, device=dev, dtype=torch.int32)
+    d_x = torch.empty_like(x) if want_grad else None
+    d_y = torch.empty_like(y) if want_grad else None
+    _lib.check(lib.smil_chamfer(_ptr(x), _ptr(y), N, P1, P2, int(bool(single_directional)), int(bool(point_sum)), int(bool(batch_sum)),
+                                _ptr(loss), _ptr(idx_x), _ptr(idx_y), _ptr(d_x), _ptr(d_y), _ptr(ws), _stream()), "smil_chamfer")
+    return loss, idx_x, idx_y, d_x, d_y
+
+
+class DeviceTopology:
+    """The regulariser tables of one face array (``mesh3d.Topology``) resident on one GPU (``SmilMeshTopology``)."""
+
+    def __init__(self, topo, device):
+        self.device = require_gpu(device)
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.int32).reshape(-1)).to(self.device)  # noqa: E731
+        self.tensors = dict(edges=i32(topo.edges), pairs=i32(topo.pairs), nbr_ptr=i32(topo.nbr_ptr), nbr=i32(topo.nbr),
+                            inv_deg=torch.from_numpy(np.ascontiguousarray(topo.inv_deg, np.float32)).to(self.device),
+                            vpair_ptr=i32(topo.vpair_ptr), vpair=i32(topo.vpair))
+        s = _lib.MeshTopology()
+        s.V, s.E, s.Q = int(topo.V), int(topo.E), int(topo.Q)
+        for k, t in self.tensors.items():
+            setattr(s, k, t.data_ptr() if t.numel() else None)
+        self.struct = s
+        self.V = topo.V
+
+
+def mesh_regularisers(topo: DeviceTopology, verts: torch.Tensor, terms: int, want_grad=True):
+    """verts (B,V,3) on ``topo`` -> (out3 (3,) = edge, normal, laplacian losses, d_edge, d_normal, d_lap (B,V,3) or None)."""
+    B = int(verts.shape[0])
+    lib = _lib.load()
+    ws = torch.empty(int(lib.smil_mesh_reg_workspace_bytes(ctypes.byref(topo.struct), B)), dtype=torch.uint8, device=verts.device)
+    out = torch.empty(3, device=verts.device, dtype=torch.float32)
+    g = [torch.empty_like(verts) if (want_grad and terms & bit) else None for bit in (_lib.REG_EDGE, _lib.REG_NORMAL, _lib.REG_LAPLACIAN)]
+    _lib.check(lib.smil_mesh_regularisers(ctypes.byref(topo.struct), _ptr(verts), B, int(terms), _ptr(out), _ptr(g[0]), _ptr(g[1]),
+                                          _ptr(g[2]), _ptr(ws), _stream()), "smil_mesh_regularisers")
+    return out, g[0], g[1], g[2]
