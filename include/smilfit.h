@@ -252,7 +252,7 @@ typedef struct {
  * buffer once and reuse it).  Meshes with more than 65536 faces are rejected (SMIL_E_INVALID). */
 size_t smil_raster_workspace_bytes(const SmilModel *m, int32_t N, int32_t S);
 
-/* Counters of the most recent rasteriser call that used `workspace` with the same N, copied to out4[4] (synchronises the
+/* Counters of the most recent rasteriser call that used `workspace`, whatever its N, copied to out4[4] (synchronises the
  * stream): [0] faces that cross z_clip (one or two vertices nearer than znear / 2): cut at the plane like pytorch3d's
  * clip_faces, which p3d_renderer.py:36-47 leaves on - the front part is rendered as one or two extra triangles whose new
  * vertices hand their gradient back to the cut edge's end points: to their xy through d_ndc, to their DEPTHS - the crossing
@@ -260,7 +260,7 @@ size_t smil_raster_workspace_bytes(const SmilModel *m, int32_t N, int32_t S);
  * image, each with up to two front-part triangles and two new vertices: rendered whole, or not at all when a vertex is nearer than 1e-8 - the one case in which a call still deviates.
  * [3] pixels whose tie group at the K-th depth was cut by K and that were therefore replayed through the reference's queue
  * (tie_rule = SMIL_TIE_REFERENCE_QUEUE only; 0 otherwise). */
-int smil_raster_stats(const SmilModel *m, int32_t N, const void *workspace, void *stream, uint32_t *out4);
+int smil_raster_stats(const SmilModel *m, const void *workspace, void *stream, uint32_t *out4);
 
 /* verts_ndc (N,V,3) -> sil (N,S,S) */
 int smil_silhouette_forward(const SmilModel *m, const float *verts_ndc, int32_t N, int32_t S,

@@ -132,7 +132,7 @@ def load():
                                                                                  c_void_p, c_void_p, c_void_p]
     lib.smil_raster_workspace_bytes.argtypes = [c_void_p, c_int32, c_int32]
     lib.smil_raster_workspace_bytes.restype = c_size_t
-    lib.smil_raster_stats.argtypes = [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]
+    lib.smil_raster_stats.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
     lib.smil_silhouette_forward.argtypes = [c_void_p, c_void_p, c_int32, c_int32, POINTER(RasterSettings), c_void_p,
                                             c_void_p, c_void_p]
     lib.smil_silhouette_backward.argtypes = [c_void_p, c_void_p, c_int32, c_int32, POINTER(RasterSettings), c_void_p,

@@ -99,6 +99,26 @@ int smil_colour_setup(const SmilModel *m, const float *verts_ndc, int N, int S, 
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// ---- caller-owned workspaces: every region starts on a 256-byte boundary ----
+static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Bump allocator over a workspace.  An entry point's ONE layout function takes its regions in order from it: with a null base it
+// only adds up their sizes (the *_workspace_bytes functions), with the caller's buffer it carves them.
+struct Workspace {
+    char *base;       // null: size only
+    size_t used = 0;  // bytes taken so far: the total once the layout is done
+    template <class T> T *take(size_t count) {
+        T *p = base ? reinterpret_cast<T *>(base + used) : nullptr;
+        used += align256(count * sizeof(T));
+        return p;
+    }
+};
+
+// Compute units and LDS per workgroup (on MI355X all 160 KB of a CU) of the current device, asked once per device (lbs.hip: one
+// mutex-guarded table).  256 CUs and 64 KB when the device cannot be asked.
+struct DeviceLimits { int cus; size_t lds_block; };
+DeviceLimits smil_device_limits();
+
 // ---- wave-level helpers (wave64) --------------------------------------------------------------
 // Sum over the 64 lanes using DPP within rows of 16 and readlane across rows; result valid in all lanes.
 __device__ __forceinline__ float wave_sum(float v) {

@@ -568,35 +568,31 @@ __global__ void __launch_bounds__(NT, FWD_MIN_WAVES) k_skin_project_fwd(SkinProj
 
 #define FWD_REG_LDS_MAX 4096  // regressor non-zeros staged in LDS (32 KB)
 static int fwd_fused_nnz_lds(const SmilModel *m) { return (!m->static_joints && m->jreg_nnz <= FWD_REG_LDS_MAX) ? m->jreg_nnz : 0; }
-// CUs and LDS of the current device, asked once per device (the grids of the per-frame persistent kernels; what a workgroup may
-// take of the CU's LDS).  Thread-safe: one mutex-guarded table.
 #define SMIL_MAX_DEVICES 16
-struct DeviceLimits { int cus; size_t lds_block, lds_cu; };
 static int current_device_slot() {  // index of the current device into per-device tables (0 when it cannot be told)
     int dev = 0;
     return (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < SMIL_MAX_DEVICES) ? dev : 0;
 }
-static DeviceLimits device_limits() {
+// (common.h) the grids of the persistent kernels of every file; what a workgroup may take of the CU's LDS
+DeviceLimits smil_device_limits() {
     static std::mutex mu;
-    static DeviceLimits table[16];
-    static bool known[16] = {};
+    static DeviceLimits table[SMIL_MAX_DEVICES];
+    static bool known[SMIL_MAX_DEVICES] = {};
     int dev = 0;
-    DeviceLimits q = {0, 64 * 1024, 64 * 1024};
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return q;
+    DeviceLimits q = {256, 64 * 1024};
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SMIL_MAX_DEVICES) return q;
     std::lock_guard<std::mutex> lock(mu);
     if (!known[dev]) {
         int cus = 0, lds = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) q.cus = cus;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) q.cus = cus;
         if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess && lds > 0) q.lds_block = (size_t)lds;
-        q.lds_cu = q.lds_block;  // (MI355X: a workgroup may take all 160 KB of its CU)
         table[dev] = q;
         known[dev] = true;
     }
     return table[dev];
 }
-static int device_cu_count() { return device_limits().cus; }
 // LDS a fused per-frame kernel may ask for so that TWO workgroups fit a CU: meshes beyond it take the separate kernels
-static size_t fused_lds_limit() { return device_limits().lds_cu / 2; }
+static size_t fused_lds_limit() { return smil_device_limits().lds_block / 2; }
 
 static size_t fwd_fused_lds_bytes(const SmilModel *m, int views) {
     return ((size_t)(m->static_joints ? 0 : 3 * m->V) + 4 + 12 * m->J + 16 * views + m->J + 1 + 2 * fwd_fused_nnz_lds(m)) * sizeof(float);
@@ -637,7 +633,7 @@ static int lbs_forward_impl(const SmilModel *m, const SmilLbsInputs *in, const S
         // tiles of the 3V-vector on x, frames strided over y: as many blocks as keep every CU busy eight deep, no more (each block
         // first loads its tile's rows of shapedirs)
         const int tiles = ceil_div(3 * V, 256 * SB_EPT);
-        const dim3 grid(tiles, std::max(1, std::min(nS, ceil_div(device_cu_count() * 8, tiles))));
+        const dim3 grid(tiles, std::max(1, std::min(nS, ceil_div(smil_device_limits().cus * 8, tiles))));
         const int bstride = in->shared_beta ? 0 : in->nB_used;
 #define SB_LAUNCH(NB) hipLaunchKernelGGL(k_shape_blend<NB>, grid, dim3(256), 0, stream, vt, m->shapedirs, in->beta, in->del_v, out->v_shaped, 3 * V, in->nB_used, bstride, nS)
         if (in->nB_used <= 8) SB_LAUNCH(8);
@@ -695,8 +691,8 @@ static int lbs_forward_impl(const SmilModel *m, const SmilLbsInputs *in, const S
         a.B = B; a.V = V; a.J = J; a.nS = nS_skin; a.regress = m->static_joints ? 0 : 1;
         a.nnz_lds = fwd_fused_nnz_lds(m);
         const size_t lds = fwd_fused_lds_bytes(m, cam->views);
-        const int cus = device_cu_count();
-        const int per_cu = std::max(1, std::min(FWD_MIN_WAVES / 2, (int)(device_limits().lds_cu / lds)));
+        const int cus = smil_device_limits().cus;
+        const int per_cu = std::max(1, std::min(FWD_MIN_WAVES / 2, (int)(smil_device_limits().lds_block / lds)));
         if (B <= std::max(1, cus))  // at most a frame per CU: 1024 threads per frame, fewer vertices (and round trips) per thread
             hipLaunchKernelGGL(k_skin_project_fwd<2 * FWD_FUSED_THREADS>, dim3(B), dim3(2 * FWD_FUSED_THREADS), lds, stream, a);
         else
@@ -1516,7 +1512,7 @@ static size_t ndc_bwd_lds_bytes(const SmilModel *m, int views, bool vp_lds, int 
 // (meshes up to ~13 000 vertices on the 160 KB of an MI355X CU); 0: the separate kernels
 static int ndc_bwd_form(const SmilModel *m, int views) {
     if (ndc_bwd_lds_bytes(m, views, true) <= fused_lds_limit()) return 1;
-    if (ndc_bwd_lds_bytes(m, views, false) <= device_limits().lds_block) return 2;
+    if (ndc_bwd_lds_bytes(m, views, false) <= smil_device_limits().lds_block) return 2;
     return 0;
 }
 
@@ -1605,12 +1601,12 @@ static int lbs_backward_impl(const SmilModel *m, const SmilLbsInputs *in, const 
         const int form = ndc_bwd_form(m, up->cam->views);
         SMIL_REQUIRE(form != 0, "smil_lbs_backward_ndc: V=%d does not fit the fused kernel's LDS (ask smil_lbs_backward_ndc_supported first)", V);
         const bool wide = form == 2;
-        const int cus = device_cu_count();
+        const int cus = smil_device_limits().cus;
         // a batch that leaves CUs idle anyway (at most a frame per CU) takes 1024 threads per frame: fewer vertices per thread, fewer
         // dependent memory round trips per phase (round 4: 25 us for one frame were ~11 round trips)
         const bool few = !wide && B <= std::max(1, cus);
         const size_t lds = ndc_bwd_lds_bytes(m, up->cam->views, !wide, few ? NDC_BWD_THREADS_WIDE : 0);
-        const int per_cu = (wide || few) ? 1 : std::max(1, std::min(2, (int)(device_limits().lds_cu / lds)));
+        const int per_cu = (wide || few) ? 1 : std::max(1, std::min(2, (int)(smil_device_limits().lds_block / lds)));
         const int grid = std::min(B, std::max(1, cus) * per_cu);
         a.beta = bsum;
         if (beta_shared) { a.beta.rows = g->beta_rows; rows_used = grid; a.beta.clear_ctr = beta_ctr; }

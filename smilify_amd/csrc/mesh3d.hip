@@ -226,12 +226,19 @@ __global__ void __launch_bounds__(64) k_chamfer_total(const float *__restrict__ 
     if (threadIdx.x == 0) loss[0] = s;
 }
 
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+static size_t chamfer_layout(int N, int P1, int P2, char *base, ChamferArgs &a) {
+    const size_t pts = (size_t)N * ((size_t)P1 + P2);
+    Workspace w{base};
+    a.key = w.take<unsigned long long>(pts);
+    a.dist = w.take<float>(pts);
+    a.acc = w.take<long long>(pts * 3);
+    a.part = w.take<float>((size_t)N * 2);
+    return w.used;
+}
 
 extern "C" size_t smil_chamfer_workspace_bytes(int32_t N, int32_t P1, int32_t P2) {
-    if (N <= 0 || P1 <= 0 || P2 <= 0) return 0;
-    const size_t pts = (size_t)N * ((size_t)P1 + P2);
-    return al256(pts * 8) + al256(pts * 4) + al256(pts * 3 * 8) + al256((size_t)N * 2 * 4);
+    ChamferArgs a;
+    return (N > 0 && P1 > 0 && P2 > 0) ? chamfer_layout(N, P1, P2, nullptr, a) : 0;
 }
 
 extern "C" int smil_chamfer(const float *x, const float *y, int32_t N, int32_t P1, int32_t P2, int32_t single_directional,
@@ -245,11 +252,7 @@ extern "C" int smil_chamfer(const float *x, const float *y, int32_t N, int32_t P
     hipStream_t stream = (hipStream_t)stream_;
     const size_t pts = (size_t)N * ((size_t)P1 + P2);
     ChamferArgs a;
-    char *ws = (char *)workspace;
-    a.key = (unsigned long long *)ws;
-    a.dist = (float *)(ws + al256(pts * 8));
-    a.acc = (long long *)(ws + al256(pts * 8) + al256(pts * 4));
-    a.part = (float *)(ws + al256(pts * 8) + al256(pts * 4) + al256(pts * 3 * 8));
+    chamfer_layout(N, P1, P2, (char *)workspace, a);
     a.pts[0] = x; a.pts[1] = y;
     a.P[0] = P1; a.P[1] = P2;
     a.N = N; a.dirs = single_directional ? 1 : 2;
@@ -441,10 +444,18 @@ __global__ void __launch_bounds__(256) k_mesh_reg_reduce(RegArgs a, int nblk) {
     }
 }
 
+static int reg_blocks(const SmilMeshTopology *t) { return ceil_div(std::max(std::max(t->V, t->E), std::max(t->Q, 1)), REG_BLOCK); }
+
+static size_t reg_layout(const SmilMeshTopology *t, int B, char *base, RegArgs &a) {
+    Workspace w{base};
+    a.part = w.take<float>((size_t)B * reg_blocks(t) * 3);
+    a.per_mesh = w.take<float>((size_t)B * 3);
+    return w.used;
+}
+
 extern "C" size_t smil_mesh_reg_workspace_bytes(const SmilMeshTopology *t, int32_t B) {
-    if (!t || B <= 0 || t->V <= 0) return 0;
-    const int nblk = ceil_div(std::max(std::max(t->V, t->E), std::max(t->Q, 1)), REG_BLOCK);
-    return al256((size_t)B * nblk * 3 * 4) + al256((size_t)B * 3 * 4);
+    RegArgs a;
+    return (t && B > 0 && t->V > 0) ? reg_layout(t, B, nullptr, a) : 0;
 }
 
 extern "C" int smil_mesh_regularisers(const SmilMeshTopology *t, const float *verts, int32_t B, int32_t terms, float *out3, float *d_edge,
@@ -462,9 +473,8 @@ extern "C" int smil_mesh_regularisers(const SmilMeshTopology *t, const float *ve
     a.t = *t;
     a.verts = verts; a.B = B; a.terms = terms;
     a.d_edge = d_edge; a.d_normal = d_normal; a.d_lap = d_lap;
-    const int nblk = ceil_div(std::max(std::max(t->V, t->E), std::max(t->Q, 1)), REG_BLOCK);
-    a.part = (float *)workspace;
-    a.per_mesh = (float *)((char *)workspace + al256((size_t)B * nblk * 3 * 4));
+    const int nblk = reg_blocks(t);
+    reg_layout(t, B, (char *)workspace, a);
     a.out = out3;
     hipLaunchKernelGGL(k_mesh_reg, dim3(nblk, B), dim3(REG_BLOCK), 0, stream, a);
     SMIL_LAUNCH_CHECK();

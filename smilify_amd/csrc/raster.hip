@@ -2409,19 +2409,8 @@ __global__ void __launch_bounds__(64, TIE_WAVES_PER_SIMD) k_raster_tie_replay(Ra
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// Compute units of the current device (256 on MI355X), asked once: the persistent grid is sized to fill them.
-static int device_cus() {
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-        cus = n;
-    }
-    return cus;
-}
+// Compute units of the current device (256 on MI355X): the persistent grids are sized to fill them.
+static int device_cus() { return smil_device_limits().cus; }
 
 // resident workgroup slots of the device: what the tile kernel's dealing policy (pieces per tile) is tuned against
 static long long tile_slots() {
@@ -2448,15 +2437,6 @@ static int tile_grid(int N, int tiles_x) {
     return (int)(best < slots ? best : slots);
 }
 
-// per resident workgroup: F x {face id, nearest depth} in id order (tiles of images that are not binned), F face ids in walking order,
-// F x {projected vertices (24 B), vertex ids (12 B)} by list position, F / DCHUNK + 2 chunk starts,
-// (REC_CAP + REC_PAD) x (one 12-byte record + one 12-byte compact record)
-#define N_STREAMS 6
-static inline size_t scratch_bytes(int grid, int F) {
-    return (size_t)grid * (12 * align256((size_t)F * sizeof(uint32_t)) + align256((size_t)(F / DCHUNK + 2) * sizeof(uint32_t)) +
-                           (size_t)(REC_CAP + REC_PAD) * N_STREAMS * sizeof(uint32_t));
-}
-
 // binned tile lists: LIST_CAP_PER_FACE entries per face and image (8 bytes each) + one depth range per tile; images with more than
 // COUNT_TILES_MAX tiles are never binned
 static inline uint32_t list_cap_of(const SmilModel *m, int S) {
@@ -2464,31 +2444,60 @@ static inline uint32_t list_cap_of(const SmilModel *m, int S) {
 }
 
 static inline int face_rows(const SmilModel *m) { return faces_padded(m->F) + CLIP_FX; }
-// per-image clip tables: new vertices (12 B) + their gradient rows (8 B) + end points (8 B) + coefficients (8 B), front-part faces (12 B), count
-static inline size_t clip_bytes(int N) {
-    return align256((size_t)N * CLIP_VX * 12) + 3 * align256((size_t)N * CLIP_VX * 8) + align256((size_t)N * CLIP_FX * 12) + align256((size_t)N * 4);
+// THE layout of a rasteriser workspace (smil_raster_workspace_bytes sizes it, raster_common carves it; tools/raster_probe.py reads the
+// counters and tile boxes).  The counters come first, so that smil_raster_stats finds them without knowing N.  Fills the regions' pointers
+// and capacities in q (setup kernel) and a (tile kernel).
+static size_t raster_layout(const SmilModel *m, int N, int S, char *base, SetupArgs &q, RasterArgs &a) {
+    const int tiles_x = ceil_div(S, TILE), FT = face_rows(m);
+    Workspace w{base};
+    a.ctr = q.ctr = w.take<RasterCounters>(1);
+    a.tbox = q.tbox = w.take<uint32_t>((size_t)N * FT);
+    a.item_cap = q.item_cap = (uint32_t)ceil_div(N, N_PARTS) * (uint32_t)(tiles_x * tiles_x);
+    a.items = q.items = w.take<uint4>((size_t)2 * N_PARTS * q.item_cap);  // work lists (2, N, tiles)
+    a.tie_mask = w.take<unsigned long long>((size_t)2 * N_PARTS * q.item_cap);  // (tie_rule 1)
+    a.fzr = q.fzr = w.take<float2>((size_t)N * FT);
+    a.gbox = q.gbox = w.take<uint32_t>((size_t)N * (FT / WAVE));
+    a.img_bound = q.img_bound = w.take<float>(N);
+    a.loss_acc = q.loss_acc = w.take<unsigned long long>(N);
+    a.list_cap = q.list_cap = list_cap_of(m, S);
+    a.lists = q.lists = w.take<uint2>((size_t)N * q.list_cap);
+    // per-image clip tables: new vertices, their gradient rows, end points and coefficients, front-part faces, count
+    ClipTables &c = q.clip;
+    c.xv = w.take<float>((size_t)N * CLIP_VX * 3);
+    c.xg = w.take<float>((size_t)N * CLIP_VX * 2);
+    c.xsrc = w.take<int2>((size_t)N * CLIP_VX);
+    c.xcoef = w.take<float2>((size_t)N * CLIP_VX);
+    c.xf = w.take<int>((size_t)N * CLIP_FX * 3);
+    c.xcount = w.take<uint32_t>(N);
+    c.xparent = nullptr;
+    a.clip = c;
+    w.take<char>(256);  // (slack ahead of the scratch that the sizes have always carried)
+    // per resident workgroup: F x {face id, nearest depth} in id order (tiles of images that are not binned), F face ids in walking
+    // order, F / DCHUNK + 2 chunk starts, F x {projected vertices, vertex ids} by list position, the two record streams
+    const size_t grid = (size_t)tile_grid(N, tiles_x);
+    a.list_stride = (int)(align256((size_t)FT * sizeof(uint32_t)) / sizeof(uint32_t));
+    a.n_cf = (int)(align256((size_t)(FT / DCHUNK + 2) * sizeof(uint32_t)) / sizeof(uint32_t));
+    a.slist = w.take<uint2>(grid * a.list_stride);
+    a.slist2 = w.take<uint32_t>(grid * a.list_stride);
+    a.scfirst = w.take<uint32_t>(grid * a.n_cf);
+    a.sxy = w.take<float2>(grid * a.list_stride * 3);
+    a.sid = w.take<TriIds>(grid * a.list_stride);
+    a.srec = w.take<Rec3>(grid * (REC_CAP + REC_PAD));
+    a.crec = w.take<Rec3>(grid * (REC_CAP + REC_PAD));
+    return w.used;
 }
 
 extern "C" size_t smil_raster_workspace_bytes(const SmilModel *m, int32_t N, int32_t S) {
-    if (!m || N <= 0 || S <= 0) return 0;
-    const size_t tiles = (size_t)ceil_div(S, TILE) * ceil_div(S, TILE);
-    const size_t FT = (size_t)face_rows(m);
-    // tile boxes (N,FT), counters, work lists (2, N, tiles), per-face depth ranges (N,FT), binned lists, clip tables, per-workgroup scratch
-    return align256((size_t)N * FT * sizeof(uint32_t)) + align256(sizeof(RasterCounters)) +
-           align256((size_t)2 * N_PARTS * ceil_div(N, N_PARTS) * tiles * sizeof(uint4)) +
-           align256((size_t)2 * N_PARTS * ceil_div(N, N_PARTS) * tiles * sizeof(unsigned long long)) +  // tie masks (tie_rule 1)
-           align256((size_t)N * FT * sizeof(float2)) + align256((size_t)N * (FT / WAVE) * sizeof(uint32_t)) +
-           align256((size_t)N * sizeof(float)) + align256((size_t)N * sizeof(unsigned long long)) + align256((size_t)N * list_cap_of(m, S) * sizeof(uint2)) +
-           clip_bytes(N) + 256 +
-           scratch_bytes(tile_grid(N, ceil_div(S, TILE)), face_rows(m));
+    SetupArgs q;
+    RasterArgs a;
+    return (m && N > 0 && S > 0) ? raster_layout(m, N, S, nullptr, q, a) : 0;
 }
 
-// Counters of the most recent rasteriser call that used `workspace` with this N (device -> host copy: synchronises the stream).
-extern "C" int smil_raster_stats(const SmilModel *m, int32_t N, const void *workspace, void *stream_, uint32_t *out4) {
-    SMIL_REQUIRE(m && workspace && out4 && N > 0, "smil_raster_stats: bad argument");
-    const RasterCounters *ctr = (const RasterCounters *)((const char *)workspace + align256((size_t)N * face_rows(m) * sizeof(uint32_t)));
+// Counters of the most recent rasteriser call that used `workspace` (device -> host copy: synchronises the stream).
+extern "C" int smil_raster_stats(const SmilModel *m, const void *workspace, void *stream_, uint32_t *out4) {
+    SMIL_REQUIRE(m && workspace && out4, "smil_raster_stats: bad argument");
     RasterCounters h;
-    SMIL_HIP(hipMemcpyAsync(&h, ctr, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)stream_));
+    SMIL_HIP(hipMemcpyAsync(&h, workspace, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)stream_));
     SMIL_HIP(hipStreamSynchronize((hipStream_t)stream_));
     unsigned int tiles = 0;
     for (int q = 0; q < N_PARTS; ++q)
@@ -2497,104 +2506,60 @@ extern "C" int smil_raster_stats(const SmilModel *m, int32_t N, const void *work
     return SMIL_OK;
 }
 
-static int raster_common(const SmilModel *m, const float *verts_ndc, int N, int S, const SmilRasterSettings *rs,
-                         void *workspace, hipStream_t stream, RasterArgs &a, float *d_ndc_zero = nullptr,
-                         const float *loss_src = nullptr, float *loss_dst = nullptr, float *dndc_scale = nullptr,
-                         const float *pix_scale = nullptr, int packed = 0, bool grads = false) {
+// the size and index-range checks of every call that runs the setup kernel
+static int check_sizes(const SmilModel *m, int N, int S, const char *who) {
+    SMIL_REQUIRE(N > 0 && S > 0 && S <= TILE * 256, "%s: bad sizes N=%d S=%d", who, N, S);
+    const int tiles_x = ceil_div(S, TILE);
+    SMIL_REQUIRE((double)N * tiles_x * tiles_x < 2147483647.0, "%s: N * tiles exceeds the work-item index range (2^31); launch in slices", who);
+    SMIL_REQUIRE(face_rows(m) + 64 < (1 << 24) && (double)list_cap_of(m, S) * sizeof(uint2) < 4294967296.0,
+                 "%s: per-workgroup / per-image tables exceed the 24-bit index / 32-bit byte-offset range of at()", who);
+    return SMIL_OK;
+}
+
+// zero the counters and run k_raster_setup, one workgroup per image
+static int launch_setup(SetupArgs &q, int N, hipStream_t stream) {
+    SMIL_HIP(hipMemsetAsync(q.ctr, 0, sizeof(RasterCounters), stream));
+    const int n_tiles = q.tiles_x * q.tiles_x;
+    // per tile and copy: 8 bytes of counts + 4 bytes of list cursor (as many copies as fit 48 KB: two workgroups per CU), or one bit
+    q.copies = n_tiles * 2 * 12 <= 48 * 1024 ? 2 : 1;  // (measured: two copies -10 % STICK / -17 % mouse at 256^2, four copies -5 % / -6 %)
+#ifdef SETUP_COPIES
+    q.copies = SETUP_COPIES;
+#endif
+    const size_t setup_lds = n_tiles <= COUNT_TILES_MAX ? (size_t)n_tiles * q.copies * 12 : (size_t)((n_tiles + 31) / 32) * sizeof(uint32_t);
+    hipLaunchKernelGGL(k_raster_setup, dim3(N), dim3(SETUP_THREADS), setup_lds, stream, q);
+    SMIL_LAUNCH_CHECK();
+    return SMIL_OK;
+}
+
+// Carves the workspace and runs the setup kernel.  q: the caller has set the fields it owns (the gradient calls' d_ndc_zero, loss
+// sums, packing and decode scale), everything else is set here; a: the per-mode outputs are the caller's to set afterwards.
+static int raster_common(const SmilModel *m, const float *verts_ndc, int N, int S, const SmilRasterSettings *rs, void *workspace,
+                         hipStream_t stream, bool grads, SetupArgs &q, RasterArgs &a) {
     SMIL_REQUIRE(m && verts_ndc && rs && workspace, "raster: null argument");
-    SMIL_REQUIRE(N > 0 && S > 0 && S <= TILE * 256, "raster: bad sizes N=%d S=%d", N, S);
+    if (int rc = check_sizes(m, N, S, "raster")) return rc;
     SMIL_REQUIRE(rs->faces_per_pixel > 0 && rs->faces_per_pixel <= SMIL_MAX_FACES_PER_PIXEL,
                  "raster: faces_per_pixel=%d outside 1..%d", rs->faces_per_pixel, SMIL_MAX_FACES_PER_PIXEL);
     SMIL_REQUIRE(rs->sigma > 0.f && rs->blur_radius >= 0.f, "raster: bad blend settings");
     SMIL_REQUIRE(rs->tie_rule == SMIL_TIE_DEPTH_FACE_ID || rs->tie_rule == SMIL_TIE_REFERENCE_QUEUE, "raster: tie_rule=%d is neither 0 nor 1", rs->tie_rule);
     SMIL_REQUIRE(face_rows(m) <= REC_CAP, "raster: %d faces exceed the %d a single pixel's records may hold", m->F, REC_CAP - CLIP_FX - WAVE);
-    const int tiles_x = ceil_div(S, TILE);
-    SMIL_REQUIRE((double)N * tiles_x * tiles_x < 2147483647.0, "raster: N * tiles exceeds the work-item index range (2^31); launch in slices");
     static_assert(REC_CAP + REC_PAD < (1 << 24), "at<12-byte>() multiplies 24-bit indices");
-    SMIL_REQUIRE(face_rows(m) + 64 < (1 << 24) && (double)list_cap_of(m, S) * sizeof(uint2) < 4294967296.0,
-                 "raster: per-workgroup / per-image tables exceed the 24-bit index / 32-bit byte-offset range of at()");
-    char *ws = (char *)workspace;
-    const int FT = face_rows(m);
-    uint32_t *tbox = (uint32_t *)ws;
-    ws += align256((size_t)N * FT * sizeof(uint32_t));
-    RasterCounters *ctr = (RasterCounters *)ws;  // (the probe tool reads the counters right behind the tile boxes)
-    ws += align256(sizeof(RasterCounters));
-    uint4 *items = (uint4 *)ws;
-    const uint32_t item_cap = (uint32_t)ceil_div(N, N_PARTS) * (uint32_t)(tiles_x * tiles_x);
-    ws += align256((size_t)2 * N_PARTS * item_cap * sizeof(uint4));
-    unsigned long long *tie_mask = (unsigned long long *)ws;
-    ws += align256((size_t)2 * N_PARTS * item_cap * sizeof(unsigned long long));
-    float2 *fzr = (float2 *)ws;
-    ws += align256((size_t)N * FT * sizeof(float2));
-    uint32_t *gbox = (uint32_t *)ws;
-    ws += align256((size_t)N * (FT / WAVE) * sizeof(uint32_t));
-    float *img_bound = (float *)ws;
-    ws += align256((size_t)N * sizeof(float));
-    unsigned long long *loss_acc = (unsigned long long *)ws;
-    ws += align256((size_t)N * sizeof(unsigned long long));
-    const uint32_t list_cap = list_cap_of(m, S);
-    uint2 *lists = (uint2 *)ws;
-    ws += align256((size_t)N * list_cap * sizeof(uint2));
-    ClipTables clip;
-    clip.xv = (float *)ws; ws += align256((size_t)N * CLIP_VX * 12);
-    clip.xg = (float *)ws; ws += align256((size_t)N * CLIP_VX * 8);
-    clip.xsrc = (int2 *)ws; ws += align256((size_t)N * CLIP_VX * 8);
-    clip.xcoef = (float2 *)ws; ws += align256((size_t)N * CLIP_VX * 8);
-    clip.xf = (int *)ws; ws += align256((size_t)N * CLIP_FX * 12);
-    clip.xcount = (uint32_t *)ws; ws += align256((size_t)N * 4);
-    clip.xparent = nullptr;
-    SMIL_HIP(hipMemsetAsync(ctr, 0, sizeof(RasterCounters), stream));
-    if (rs->tie_rule) SMIL_HIP(hipMemsetAsync(tie_mask, 0, (size_t)2 * N_PARTS * item_cap * sizeof(unsigned long long), stream));
-    const float sqrt_blur = sqrtf(rs->blur_radius);
-    const int n_tiles = tiles_x * tiles_x;
-    {
-        SetupArgs q;
-        q.verts_ndc = verts_ndc; q.faces = m->faces; q.tbox = tbox; q.gbox = gbox; q.items = items; q.item_cap = item_cap; q.fzr = fzr;
-        q.ctr = ctr; q.V = m->V; q.F = m->F; q.S = S; q.tiles_x = tiles_x; q.sqrt_blur = sqrt_blur; q.z_clip = rs->z_clip;
-        q.d_ndc_zero = d_ndc_zero; q.loss_src = loss_src; q.loss_dst = loss_dst; q.loss_acc = loss_acc; q.img_bound = img_bound; q.max_valence = m->max_valence;
-        q.dndc_scale = dndc_scale; q.pix_scale = pix_scale; q.inv_sigma = 1.0f / rs->sigma; q.packed = packed;
-        q.lists = lists; q.list_cap = list_cap; q.clip = clip;
-        q.cd_counter = (grads && rs->clip_depth && rs->image0 == 0) ? rs->clip_depth->counter : nullptr;
-        // per tile and copy: 8 bytes of counts + 4 bytes of list cursor (as many copies as fit 48 KB: two workgroups per CU), or one bit
-        q.copies = n_tiles * 2 * 12 <= 48 * 1024 ? 2 : 1;  // (measured: two copies -10 % STICK / -17 % mouse at 256^2, four copies -5 % / -6 %)
-#ifdef SETUP_COPIES
-        q.copies = SETUP_COPIES;
-#endif
-        const size_t setup_lds = n_tiles <= COUNT_TILES_MAX ? (size_t)n_tiles * q.copies * 12 : (size_t)((n_tiles + 31) / 32) * sizeof(uint32_t);
-        hipLaunchKernelGGL(k_raster_setup, dim3(N), dim3(SETUP_THREADS), setup_lds, stream, q);
-        SMIL_LAUNCH_CHECK();
-    }
-    {
-        const size_t grid = (size_t)tile_grid(N, tiles_x);
-        a.list_stride = (int)(align256((size_t)FT * sizeof(uint32_t)) / sizeof(uint32_t));
-        a.n_cf = (int)(align256((size_t)(FT / DCHUNK + 2) * sizeof(uint32_t)) / sizeof(uint32_t));
-        ws += 256;
-        a.slist = (uint2 *)ws;
-        ws += grid * (size_t)a.list_stride * sizeof(uint2);
-        a.slist2 = (uint32_t *)ws;
-        ws += grid * (size_t)a.list_stride * sizeof(uint32_t);
-        a.scfirst = (uint32_t *)ws;
-        ws += grid * (size_t)a.n_cf * sizeof(uint32_t);
-        a.sxy = (float2 *)ws;
-        ws += grid * (size_t)a.list_stride * 3 * sizeof(float2);
-        a.sid = (TriIds *)ws;
-        ws += grid * (size_t)a.list_stride * sizeof(TriIds);
-        const size_t stream = grid * (size_t)(REC_CAP + REC_PAD) * sizeof(Rec3);
-        a.srec = (Rec3 *)ws; ws += stream;
-        a.crec = (Rec3 *)ws;
-    }
-    a.lists = lists; a.list_cap = list_cap; a.clip = clip; a.FT = FT; a.slots = (unsigned int)tile_slots();
-    a.tie_rule = rs->tie_rule; a.tie_mask = tie_mask; a.loss_acc = loss_acc;
-    a.cd = SmilClipDepth{nullptr, nullptr, nullptr, nullptr, 0};
-    a.image0 = rs->image0;
-    if (grads && rs->clip_depth) {
+    if (grads && rs->clip_depth)
         SMIL_REQUIRE(rs->clip_depth->vertex && rs->clip_depth->dz && rs->clip_depth->range && rs->clip_depth->counter && rs->clip_depth->capacity >= 0 &&
                      rs->image0 >= 0, "raster: incomplete SmilClipDepth");
-        a.cd = *rs->clip_depth;
-    }
-    a.verts_ndc = verts_ndc; a.faces = m->faces; a.tbox = tbox; a.gbox = gbox; a.items = items; a.item_cap = item_cap; a.fzr = fzr; a.ctr = ctr; a.img_bound = img_bound; a.packed = 0;
-    a.N = N; a.V = m->V; a.F = m->F; a.S = S; a.tiles_x = tiles_x; a.K = rs->faces_per_pixel;
-    a.blur = rs->blur_radius; a.sqrt_blur = sqrt_blur; a.inv_sigma = 1.0f / rs->sigma; a.inv_sigma_log2e = (float)(1.4426950408889634 / (double)rs->sigma);
+    raster_layout(m, N, S, (char *)workspace, q, a);
+    const int tiles_x = ceil_div(S, TILE);
+    if (rs->tie_rule) SMIL_HIP(hipMemsetAsync(a.tie_mask, 0, (size_t)2 * N_PARTS * a.item_cap * sizeof(unsigned long long), stream));
+    q.verts_ndc = a.verts_ndc = verts_ndc; q.faces = a.faces = m->faces;
+    q.V = a.V = m->V; q.F = a.F = m->F; q.S = a.S = S; q.tiles_x = a.tiles_x = tiles_x;
+    q.sqrt_blur = a.sqrt_blur = sqrtf(rs->blur_radius); q.z_clip = rs->z_clip; q.max_valence = m->max_valence;
+    q.inv_sigma = a.inv_sigma = 1.0f / rs->sigma;
+    q.cd_counter = (grads && rs->clip_depth && rs->image0 == 0) ? rs->clip_depth->counter : nullptr;
+    if (int rc = launch_setup(q, N, stream)) return rc;
+    a.FT = face_rows(m); a.slots = (unsigned int)tile_slots();
+    a.tie_rule = rs->tie_rule; a.image0 = rs->image0;
+    a.cd = (grads && rs->clip_depth) ? *rs->clip_depth : SmilClipDepth{nullptr, nullptr, nullptr, nullptr, 0};
+    a.N = N; a.K = rs->faces_per_pixel; a.packed = 0;
+    a.blur = rs->blur_radius; a.inv_sigma_log2e = (float)(1.4426950408889634 / (double)rs->sigma);
     HOOK_HOST_LAUNCH_SETUP(a, stream)
     a.sil = nullptr; a.grad_sil = nullptr; a.target = nullptr; a.target_u8 = nullptr; a.pix_scale = nullptr; a.loss_img = nullptr;
     a.d_ndc = nullptr;
@@ -2603,38 +2568,35 @@ static int raster_common(const SmilModel *m, const float *verts_ndc, int N, int 
 
 // ---- the colour path's share of the setup (shade.hip): k_raster_setup with blur 0 (K = 1 needs no blur box), its per-image tables,
 // binned lists, work items and clip tables - none of the tile kernel's per-workgroup scratch ----
-static inline size_t colour_setup_layout(const SmilModel *m, int N, int S, char *ws, ColourSetup *o, SetupArgs *q) {
+static size_t colour_setup_layout(const SmilModel *m, int N, int S, char *base, ColourSetup *o, SetupArgs *q) {
     const int tiles_x = ceil_div(S, TILE), FT = face_rows(m);
     const uint32_t item_cap = (uint32_t)ceil_div(N, N_PARTS) * (uint32_t)(tiles_x * tiles_x);
     const uint32_t list_cap = list_cap_of(m, S);
-    size_t off = 0;
-    auto take = [&](size_t bytes) -> char * { char *p = ws ? ws + off : nullptr; off += align256(bytes); return p; };
-    char *tbox = take((size_t)N * FT * sizeof(uint32_t));
-    char *ctr = take(sizeof(RasterCounters));
-    char *items = take((size_t)2 * N_PARTS * item_cap * sizeof(uint4));
-    char *fzr = take((size_t)N * FT * sizeof(float2));
-    char *gbox = take((size_t)N * (FT / WAVE) * sizeof(uint32_t));
-    char *lists = take((size_t)N * list_cap * sizeof(uint2));
+    Workspace w{base};
+    uint32_t *tbox = w.take<uint32_t>((size_t)N * FT);
+    RasterCounters *c = w.take<RasterCounters>(1);
+    uint4 *items = w.take<uint4>((size_t)2 * N_PARTS * item_cap);
+    float2 *fzr = w.take<float2>((size_t)N * FT);
+    uint32_t *gbox = w.take<uint32_t>((size_t)N * (FT / WAVE));
+    uint2 *lists = w.take<uint2>((size_t)N * list_cap);
     ClipTables clip;
-    clip.xv = (float *)take((size_t)N * CLIP_VX * 12);
-    clip.xsrc = (int2 *)take((size_t)N * CLIP_VX * 8);
-    clip.xcoef = (float2 *)take((size_t)N * CLIP_VX * 8);
-    clip.xf = (int *)take((size_t)N * CLIP_FX * 12);
-    clip.xparent = (int *)take((size_t)N * CLIP_CUTS * 4);
+    clip.xv = w.take<float>((size_t)N * CLIP_VX * 3);
+    clip.xsrc = w.take<int2>((size_t)N * CLIP_VX);
+    clip.xcoef = w.take<float2>((size_t)N * CLIP_VX);
+    clip.xf = w.take<int>((size_t)N * CLIP_FX * 3);
+    clip.xparent = w.take<int>((size_t)N * CLIP_CUTS);
     clip.xg = nullptr; clip.xcount = nullptr;  // (no gradient rows)
-    if (!ws) return off;
-    RasterCounters *c = (RasterCounters *)ctr;
-    o->tbox = (const uint32_t *)tbox; o->gbox = (const uint32_t *)gbox; o->fzr = (const float2 *)fzr; o->items = (const uint4 *)items;
+    if (!base) return w.used;
+    o->tbox = tbox; o->gbox = gbox; o->fzr = fzr; o->items = items;
     o->n_class = &c->n_class[0][0]; o->ticket = &c->deal[0].next; o->item_cap = item_cap;
-    o->lists = (const uint2 *)lists; o->list_cap = list_cap;
+    o->lists = lists; o->list_cap = list_cap;
     o->xv = clip.xv; o->xf = clip.xf; o->xsrc = clip.xsrc; o->xparent = clip.xparent;
     o->FT = FT; o->FP = faces_padded(m->F); o->clip_vx = CLIP_VX; o->clip_fx = CLIP_FX; o->n_parts = N_PARTS; o->n_classes = N_CLASSES;
     *q = SetupArgs{};
-    q->clip = clip; q->faces = m->faces; q->tbox = (uint32_t *)tbox; q->gbox = (uint32_t *)gbox; q->items = (uint4 *)items;
-    q->item_cap = item_cap; q->fzr = (float2 *)fzr; q->ctr = c; q->V = m->V; q->F = m->F; q->S = S; q->tiles_x = tiles_x;
-    q->sqrt_blur = 0.f; q->inv_sigma = 1.f; q->lists = (uint2 *)lists; q->list_cap = list_cap;
-    q->copies = tiles_x * tiles_x * 2 * 12 <= 48 * 1024 ? 2 : 1;
-    return off;
+    q->clip = clip; q->faces = m->faces; q->tbox = tbox; q->gbox = gbox; q->items = items;
+    q->item_cap = item_cap; q->fzr = fzr; q->ctr = c; q->V = m->V; q->F = m->F; q->S = S; q->tiles_x = tiles_x;
+    q->sqrt_blur = 0.f; q->inv_sigma = 1.f; q->lists = lists; q->list_cap = list_cap;
+    return w.used;
 }
 
 size_t smil_colour_setup_bytes(const SmilModel *m, int N, int S) {
@@ -2643,19 +2605,11 @@ size_t smil_colour_setup_bytes(const SmilModel *m, int N, int S) {
 
 int smil_colour_setup(const SmilModel *m, const float *verts_ndc, int N, int S, float z_clip, void *workspace, hipStream_t stream,
                       ColourSetup *out) {
-    SMIL_REQUIRE(N > 0 && S > 0 && S <= TILE * 256, "smil_render_colour: bad sizes N=%d S=%d", N, S);
-    SMIL_REQUIRE(face_rows(m) + 64 < (1 << 24) && (double)list_cap_of(m, S) * sizeof(uint2) < 4294967296.0,
-                 "smil_render_colour: per-image tables exceed the 24-bit index / 32-bit byte-offset range of at()");
-    const int tiles_x = ceil_div(S, TILE), n_tiles = tiles_x * tiles_x;
-    SMIL_REQUIRE((double)N * n_tiles < 2147483647.0, "smil_render_colour: N * tiles exceeds the work-item index range (2^31)");
+    if (int rc = check_sizes(m, N, S, "smil_render_colour")) return rc;
     SetupArgs q;
     colour_setup_layout(m, N, S, (char *)workspace, out, &q);
     q.verts_ndc = verts_ndc; q.z_clip = z_clip;
-    SMIL_HIP(hipMemsetAsync(q.ctr, 0, sizeof(RasterCounters), stream));
-    const size_t setup_lds = n_tiles <= COUNT_TILES_MAX ? (size_t)n_tiles * q.copies * 12 : (size_t)((n_tiles + 31) / 32) * sizeof(uint32_t);
-    hipLaunchKernelGGL(k_raster_setup, dim3(N), dim3(SETUP_THREADS), setup_lds, stream, q);
-    SMIL_LAUNCH_CHECK();
-    return SMIL_OK;
+    return launch_setup(q, N, stream);
 }
 
 // ---- optional in-process timing of the tile kernel (bench.py): HIP events recorded on the launch stream ----
@@ -2701,10 +2655,6 @@ extern "C" int smil_profile_read(float *total_ms, int32_t *launches) {
 #define PROF_END(stream) \
     if (_slot >= 0) (void)hipEventRecord(g_prof_ev[_slot][1], stream)
 
-template <int MODE>
-static void launch_tiles(const RasterArgs &a, int N, hipStream_t stream) {
-    hipLaunchKernelGGL((k_raster_dense<MODE>), dim3(tile_grid(N, a.tiles_x)), dim3(64), 0, stream, a);
-}
 // (tie_rule 1) the pixels the tile kernel left out: the reference's queue replayed, one wave per pixel
 template <int MODE>
 static void launch_tie_replay(const RasterArgs &a, hipStream_t stream) {
@@ -2713,39 +2663,42 @@ static void launch_tie_replay(const RasterArgs &a, hipStream_t stream) {
     // (as many waves as the registers let a CU hold - the ~6 KB of LDS per wave allow more; they take tickets until none is left)
     if (a.tie_rule) hipLaunchKernelGGL((k_raster_tie_replay<MODE>), dim3((unsigned int)device_cus() * 4u * TIE_WAVES_PER_SIMD), dim3(64), lds, stream, a);
 }
+// the tile kernel (timed when profiling is on), then the tie replay
+template <int MODE>
+static int launch_raster(const RasterArgs &a, hipStream_t stream) {
+    PROF_BEGIN(stream);
+    hipLaunchKernelGGL((k_raster_dense<MODE>), dim3(tile_grid(a.N, a.tiles_x)), dim3(64), 0, stream, a);
+    PROF_END(stream);
+    launch_tie_replay<MODE>(a, stream);
+    SMIL_LAUNCH_CHECK();
+    return SMIL_OK;
+}
 
 extern "C" int smil_silhouette_forward(const SmilModel *m, const float *verts_ndc, int32_t N, int32_t S,
                                        const SmilRasterSettings *rs, float *sil, void *workspace, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
+    SetupArgs q{};
     RasterArgs a;
-    int rc = raster_common(m, verts_ndc, N, S, rs, workspace, stream, a);
+    int rc = raster_common(m, verts_ndc, N, S, rs, workspace, stream, false, q, a);
     if (rc) return rc;
     SMIL_REQUIRE(sil, "smil_silhouette_forward: null output");
     SMIL_HIP(hipMemsetAsync(sil, 0, (size_t)N * S * S * sizeof(float), stream));
     a.sil = sil;
-    PROF_BEGIN(stream);
-    launch_tiles<MODE_FWD>(a, N, stream);
-    PROF_END(stream);
-    launch_tie_replay<MODE_FWD>(a, stream);
-    SMIL_LAUNCH_CHECK();
-    return SMIL_OK;
+    return launch_raster<MODE_FWD>(a, stream);
 }
 
 extern "C" int smil_silhouette_backward(const SmilModel *m, const float *verts_ndc, int32_t N, int32_t S,
                                         const SmilRasterSettings *rs, const float *grad_sil, float *d_ndc,
                                         void *workspace, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
+    SetupArgs q{};
     RasterArgs a;
-    int rc = raster_common(m, verts_ndc, N, S, rs, workspace, stream, a, nullptr, nullptr, nullptr, nullptr, nullptr, 0, true);
+    int rc = raster_common(m, verts_ndc, N, S, rs, workspace, stream, true, q, a);
     if (rc) return rc;
     SMIL_REQUIRE(grad_sil && d_ndc, "smil_silhouette_backward: null argument");
     SMIL_HIP(hipMemsetAsync(d_ndc, 0, (size_t)N * m->V * 2 * sizeof(float), stream));
     a.grad_sil = grad_sil; a.d_ndc = d_ndc;
-    PROF_BEGIN(stream);
-    launch_tiles<MODE_BWD>(a, N, stream);
-    PROF_END(stream);
-    launch_tie_replay<MODE_BWD>(a, stream);
-    SMIL_LAUNCH_CHECK();
+    if ((rc = launch_raster<MODE_BWD>(a, stream))) return rc;
     hipLaunchKernelGGL(k_clip_backward, dim3(N), dim3(64), 0, stream, a.clip, d_ndc, m->V, (float *)nullptr, (const unsigned long long *)nullptr, verts_ndc, rs->z_clip, a.cd, a.image0);  // (new vertices of cut faces -> their edges' end points)
     SMIL_LAUNCH_CHECK();
     return SMIL_OK;
@@ -2756,22 +2709,20 @@ extern "C" int smil_silhouette_l1_fused(const SmilModel *m, const float *verts_n
                                         const float *target_sum, const float *pix_scale, float *loss_img, float *d_ndc,
                                         float *sil_out, float *d_ndc_scale, void *workspace, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    RasterArgs a;
     SMIL_REQUIRE(target && target_sum && pix_scale && loss_img && d_ndc, "smil_silhouette_l1_fused: null argument");
+    SetupArgs q{};
+    RasterArgs a;
     // large launches accumulate the vertex gradients as packed fixed point (half the memory-side atomics); small ones keep float
     // atomics.  The packed rows are decoded in place afterwards, unless the caller takes them as they are (d_ndc_scale).
-    const int packed = (N >= PACKED_MIN_IMAGES && (reinterpret_cast<uintptr_t>(d_ndc) & 7u) == 0u) ? 1 : 0;  // (64-bit atomics need 8-byte alignment)
-    int rc = raster_common(m, verts_ndc, N, S, rs, workspace, stream, a, d_ndc, target_sum, loss_img, d_ndc_scale, pix_scale, packed, true);
+    q.packed = (N >= PACKED_MIN_IMAGES && (reinterpret_cast<uintptr_t>(d_ndc) & 7u) == 0u) ? 1 : 0;  // (64-bit atomics need 8-byte alignment)
+    q.d_ndc_zero = d_ndc; q.loss_src = target_sum; q.loss_dst = loss_img; q.dndc_scale = d_ndc_scale; q.pix_scale = pix_scale;
+    int rc = raster_common(m, verts_ndc, N, S, rs, workspace, stream, true, q, a);
     if (rc) return rc;
     if (sil_out) SMIL_HIP(hipMemsetAsync(sil_out, 0, (size_t)N * S * S * sizeof(float), stream));
     if (target_is_u8) a.target_u8 = (const uint8_t *)target; else a.target = (const float *)target;
     a.pix_scale = pix_scale; a.loss_img = loss_img; a.d_ndc = d_ndc; a.sil = sil_out;
-    a.packed = packed;
-    PROF_BEGIN(stream);
-    launch_tiles<MODE_FUSED>(a, N, stream);
-    PROF_END(stream);
-    launch_tie_replay<MODE_FUSED>(a, stream);
-    SMIL_LAUNCH_CHECK();
+    a.packed = q.packed;
+    if ((rc = launch_raster<MODE_FUSED>(a, stream))) return rc;
     hipLaunchKernelGGL(k_clip_backward, dim3(N), dim3(64), 0, stream, a.clip, d_ndc, m->V, loss_img, (const unsigned long long *)a.loss_acc, verts_ndc, rs->z_clip, a.cd, a.image0);  // (new vertices of cut faces -> their edges' end points; the images' loss sums)
     SMIL_LAUNCH_CHECK();
     if (a.packed && !d_ndc_scale) {

@@ -278,12 +278,17 @@ __global__ void __launch_bounds__(64) k_colour_tiles(ColourArgs a) {
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+// the setup's tables (raster.hip), then vertex normals of up to N frames
+static size_t colour_layout(const SmilModel *m, int N, int S, char *base, float **normals) {
+    Workspace w{base};
+    w.take<char>(smil_colour_setup_bytes(m, N, S));
+    *normals = w.take<float>((size_t)N * m->V * 3);
+    return w.used;
+}
 
 extern "C" size_t smil_colour_workspace_bytes(const SmilModel *m, int32_t N, int32_t S) {
-    if (!m || N <= 0 || S <= 0) return 0;
-    // the setup's tables + vertex normals of up to N frames
-    return al256(smil_colour_setup_bytes(m, N, S)) + al256((size_t)N * m->V * 3 * sizeof(float));
+    float *normals;
+    return (m && N > 0 && S > 0) ? colour_layout(m, N, S, nullptr, &normals) : 0;
 }
 
 extern "C" int smil_render_colour(const SmilModel *m, const SmilCameras *cam, const float *verts_world, const float *verts_ndc,
@@ -298,10 +303,10 @@ extern "C" int smil_render_colour(const SmilModel *m, const SmilCameras *cam, co
     hipStream_t stream = (hipStream_t)stream_;
     const int N = cam->N, S = cam->S, V = m->V, frames = N / cam->views;
     ColourArgs a;
-    char *ws = (char *)workspace;
-    int rc = smil_colour_setup(m, verts_ndc, N, S, 0.5f * SMIL_ZNEAR, ws, stream, &a.cs);
+    int rc = smil_colour_setup(m, verts_ndc, N, S, 0.5f * SMIL_ZNEAR, workspace, stream, &a.cs);
     if (rc) return rc;
-    float *normals = (float *)(ws + al256(smil_colour_setup_bytes(m, N, S)));
+    float *normals;
+    colour_layout(m, N, S, (char *)workspace, &normals);
     hipLaunchKernelGGL(k_vertex_normals, dim3(ceil_div(V, 256), frames), dim3(256), 0, stream, verts_world, m->faces, m->vf_ptr, m->vf_face, V,
                        normals);
     SMIL_LAUNCH_CHECK();
@@ -315,13 +320,7 @@ extern "C" int smil_render_colour(const SmilModel *m, const SmilCameras *cam, co
     a.rgb[0] = rgb[0]; a.rgb[1] = rgb[1]; a.rgb[2] = rgb[2];
     a.image = image; a.pix_to_face = pix_to_face;
     a.N = N; a.V = V; a.F = m->F; a.S = S; a.tiles_x = ceil_div(S, CTILE); a.views = cam->views; a.z_clip = 0.5f * SMIL_ZNEAR;
-    static int cus = 0;  // (compute units of the device, asked once)
-    if (cus == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cus = n;
-    }
-    hipLaunchKernelGGL(k_colour_tiles, dim3((unsigned int)cus * COLOUR_WAVES_PER_CU), dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(k_colour_tiles, dim3((unsigned int)smil_device_limits().cus * COLOUR_WAVES_PER_CU), dim3(64), 0, stream, a);
     SMIL_LAUNCH_CHECK();
     return SMIL_OK;
 }

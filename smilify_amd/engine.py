@@ -120,17 +120,15 @@ class DeviceModel:
         self._ws = ws
         return ws
 
-    def _claim_workspace(self, n_last_slice: int) -> None:
+    def _claim_workspace(self) -> None:
         """Book-keeping of a rasteriser call about to be launched: order it behind the previous user of the shared workspace when that
-        one ran on another stream, and remember who used the workspace last and with which slice size (``raster_stats`` reads the
-        counters at an offset that depends on it)."""
+        one ran on another stream, and remember who used the workspace last (``raster_stats``)."""
         key = self._ws_key()
         cur = torch.cuda.current_stream(self.device)
         prev = _WS_USER.get(key)
         if prev is not None and prev[1] != cur and not torch.cuda.is_current_stream_capturing():
             cur.wait_stream(prev[1])
         _WS_USER[key] = (self, cur)
-        self._last_launch = n_last_slice
 
 
 @dataclass
@@ -477,16 +475,15 @@ def _slices(N: int, step: int = MAX_IMAGES_PER_LAUNCH):
 
 def raster_stats(model: DeviceModel, N: int) -> dict:
     """Counters of the most recent rasteriser call of ``model`` (of its last slice when the batch was cut into several launches):
-    faces straddling z_clip, touched tiles, faces beyond the clip tables, pixels replayed through the reference's queue (``tie_rule``).  ``N`` is ignored (kept for callers of round 3): the slice
-    size is recorded at launch time.  Zeros when the model has not rasterised since the workspace was last used by another model.
-    Synchronises."""
+    faces straddling z_clip, touched tiles, faces beyond the clip tables, pixels replayed through the reference's queue (``tie_rule``).  ``N`` is ignored (kept for callers of round 3): the
+    counters lie at the start of the workspace whatever the slice size.  Zeros when the model has not rasterised since the workspace was
+    last used by another model.  Synchronises."""
     zero = {"straddling_faces": 0, "tiles": 0, "unclipped_faces": 0, "tie_pixels": 0}
     user = _WS_USER.get(model._ws_key())
-    last = model.__dict__.get("_last_launch")
-    if model._ws is None or last is None or user is None or user[0] is not model:
+    if model._ws is None or user is None or user[0] is not model:
         return zero  # this model has not rasterised, or another model / topology has used the shared workspace since
     out = (ctypes.c_uint32 * 4)()
-    _lib.check(_lib.load().smil_raster_stats(model.handle, last, _ptr(model._ws), _stream(), out), "smil_raster_stats")
+    _lib.check(_lib.load().smil_raster_stats(model.handle, _ptr(model._ws), _stream(), out), "smil_raster_stats")
     return {"straddling_faces": int(out[0]), "tiles": int(out[1]), "unclipped_faces": int(out[2]), "tie_pixels": int(out[3])}
 
 
@@ -496,7 +493,7 @@ def silhouette_forward(model: DeviceModel, verts_ndc: torch.Tensor, S: int, rs=N
     sil = torch.empty(N, S, S, dtype=torch.float32, device=verts_ndc.device)
     step = model._last_slice = _slice_images(model, N, S)
     ws = model.workspace(step, S)
-    model._claim_workspace(N - ((N - 1) // step) * step)
+    model._claim_workspace()
     for n0, n1 in _slices(N, step):
         _lib.check(_lib.load().smil_silhouette_forward(model.handle, _ptr(verts_ndc[n0:n1]), n1 - n0, S, ctypes.byref(rs),
                                                        _ptr(sil[n0:n1]), _ptr(ws), _stream()), "smil_silhouette_forward")
@@ -511,7 +508,7 @@ def silhouette_backward(model: DeviceModel, verts_ndc: torch.Tensor, S: int, gra
     d_ndc = torch.empty(N, model.V, 2, dtype=torch.float32, device=verts_ndc.device)
     step = model._last_slice = _slice_images(model, N, S)
     ws = model.workspace(step, S)
-    model._claim_workspace(N - ((N - 1) // step) * step)
+    model._claim_workspace()
     for n0, n1 in _slices(N, step):
         _lib.check(_lib.load().smil_silhouette_backward(model.handle, _ptr(verts_ndc[n0:n1]), n1 - n0, S, ctypes.byref(_rs_for_slice(rs, clip_depth, n0)),
                                                         _ptr(grad_sil[n0:n1]), _ptr(d_ndc[n0:n1]), _ptr(ws), _stream()),
@@ -535,7 +532,7 @@ def silhouette_l1_fused(model: DeviceModel, verts_ndc, S, target, target_sum, pi
     scale = torch.empty(N, dtype=torch.float32, device=dev) if packed_out else None
     step = model._last_slice = _slice_images(model, N, S)
     ws = model.workspace(step, S)
-    model._claim_workspace(N - ((N - 1) // step) * step)
+    model._claim_workspace()
     if target.dtype not in (torch.float32, torch.uint8):
         raise _lib.SmilError(f"target silhouettes must be float32 or uint8, got {target.dtype}")
     for n0, n1 in _slices(N, step):
