@@ -109,7 +109,7 @@ class DeviceModel:
     def workspace(self, N: int, S: int) -> torch.Tensor:
         """Rasteriser workspace: ONE buffer per device, shared by every model and topology on it (most of it is the scratch
         arena of the resident workgroups, whatever the mesh), grown when a call needs more; every model then points at the
-        grown buffer (a captured hipGraph holds the tensor it was captured with itself, ``SMALFitter._capture_step``).
+        grown buffer (a captured hipGraph holds the tensor it was captured with itself, ``fit_graph.capture``).
         Every call rewrites what it reads, so models may take turns - in STREAM ORDER: a call on another stream than the
         previous one first waits for everything submitted to that stream (``_claim_workspace``)."""
         need = int(_lib.load().smil_raster_workspace_bytes(self.handle, N, S))
@@ -232,6 +232,16 @@ def raster_settings(blur=BLUR_RADIUS, sigma=SIGMA, K=FACES_PER_PIXEL, tie_rule="
 # ----------------------------------------------------------------------------------------------
 # LBS
 # ----------------------------------------------------------------------------------------------
+def _lbs_inputs(inp: Dict, fl: Dict) -> _lib.LbsInputs:
+    """The ``LbsInputs`` struct of a call: its input tensors and its flags, as ``lbs_forward`` saves them for ``lbs_backward``."""
+    i = _lib.LbsInputs()
+    for k, v in fl.items():
+        setattr(i, k, int(v))
+    for k, t in inp.items():
+        setattr(i, k, None if t is None else t.data_ptr())
+    return i
+
+
 def lbs_forward(model: DeviceModel, beta, theta, trans=None, logscale=None, btrans=None, del_v=None,
                 v_template=None, Rs_in=None, shared_beta=False, logscale_shared=False, btrans_shared=False,
                 propagate_scaling=False, allow_limb_scaling=True, trans_after_joints=False, theta_mask=None,
@@ -252,13 +262,9 @@ def lbs_forward(model: DeviceModel, beta, theta, trans=None, logscale=None, btra
         out["v_posed"] = f(B, V, 3)
     inp = dict(beta=beta, theta=theta, Rs_in=Rs_in, logscale=logscale, btrans=btrans, trans=trans, del_v=del_v,
                v_template=v_template, theta_mask=theta_mask)
-    i = _lib.LbsInputs()
-    i.B, i.shared_beta, i.nB_used = B, int(shared_beta), nB_used
-    i.logscale_shared, i.btrans_shared = int(logscale_shared), int(btrans_shared)
-    i.propagate_scaling, i.allow_limb_scaling = int(propagate_scaling), int(allow_limb_scaling)
-    i.trans_after_joints = int(trans_after_joints)
-    for k, t in inp.items():
-        setattr(i, k, None if t is None else t.data_ptr())
+    fl = dict(B=B, shared_beta=shared_beta, nB_used=nB_used, logscale_shared=logscale_shared, btrans_shared=btrans_shared,
+              propagate_scaling=propagate_scaling, allow_limb_scaling=allow_limb_scaling, trans_after_joints=trans_after_joints)
+    i = _lbs_inputs(inp, fl)
     o = _lib.LbsOutputs()
     for k, t in out.items():
         setattr(o, k, t.data_ptr())
@@ -278,9 +284,7 @@ def lbs_forward(model: DeviceModel, beta, theta, trans=None, logscale=None, btra
     if yx is not None:
         out["yx"] = yx
     out["_inputs"] = inp
-    out["_flags"] = dict(B=B, shared_beta=shared_beta, nB_used=nB_used, logscale_shared=logscale_shared,
-                         btrans_shared=btrans_shared, propagate_scaling=propagate_scaling,
-                         allow_limb_scaling=allow_limb_scaling, trans_after_joints=trans_after_joints)
+    out["_flags"] = fl
     return out
 
 
@@ -331,13 +335,7 @@ def lbs_backward(model: DeviceModel, saved: Dict, d_verts, d_joints, need_beta=T
     scratch = dict(d_A=f(B, J, 12), d_Jrest=f(B, J, 3), d_Rs=f(B, J, 9))
     if g["d_beta"] is not None and fl["shared_beta"]:
         scratch["beta_rows"] = f(2 * B * fl["nB_used"] + 16)  # per-block partial sums of the shared shape gradient (added in a fixed order) + the call's block counter
-    i = _lib.LbsInputs()
-    i.B, i.shared_beta, i.nB_used = B, int(fl["shared_beta"]), fl["nB_used"]
-    i.logscale_shared, i.btrans_shared = int(fl["logscale_shared"]), int(fl["btrans_shared"])
-    i.propagate_scaling, i.allow_limb_scaling = int(fl["propagate_scaling"]), int(fl["allow_limb_scaling"])
-    i.trans_after_joints = int(fl["trans_after_joints"])
-    for k, t in inp.items():
-        setattr(i, k, None if t is None else t.data_ptr())
+    i = _lbs_inputs(inp, fl)
     o = _lib.LbsOutputs()
     for k in ("v_shaped", "J_rest", "Rs", "G", "A", "new_J", "verts", "joints"):
         setattr(o, k, saved[k].data_ptr())

@@ -276,7 +276,7 @@ def _reference_epoch(model, N, W, weights, w_temp, window_weight=None):
 
 @pytest.mark.parametrize("frames,window,views", [(7, 2, 1), (8, 4, 1), (6, 2, 2)])
 def test_forward_serves_an_epoch_from_one_evaluation(tables, frames, window, views):
-    """The per-window forward() calls of the reference's loop are answered from ONE whole-batch evaluation (SMALFitter._epoch_window):
+    """The per-window forward() calls of the reference's loop are answered from ONE whole-batch evaluation (fit_epoch.FitState.serve):
     same window losses, same terms, same parameter gradients as the window-by-window evaluation - also when the windows are weighted
     differently or one is left out (the correction path of _EpochEval.backward), and a parameter update starts a new epoch."""
     from smilify_amd import synthetic

@@ -1,8 +1,10 @@
 """GPU tests of the fitter's state handling (``pytest -m gpu``): the reference-written per-frame checkpoint
-(optimize_to_joints.py:48-63, fitter.py:352-371), hipGraph invalidation, the renderer's topology cache, batches beyond 65 535
-frames / images."""
+(optimize_to_joints.py:48-63, fitter.py:352-371), hipGraph invalidation, the cached epoch's ownership and invalidation, the
+renderer's topology cache, batches beyond 65 535 frames / images."""
+import gc
 import os
 import pickle
+import weakref
 
 import numpy as np
 import pytest
@@ -100,6 +102,81 @@ def test_graph_replay_is_invalidated_by_camera_mask_and_workspace_changes(tables
         f.renderer.raster_settings = _eng.raster_settings(tie_rule="reference_queue")
     both()
     assert fg._graph["graph"] is not fourth
+
+LOOP_WEIGHTS = [10.0, 500.0, 1.0, 1.0, 100.0, 0.1]
+
+
+def test_a_fitter_that_served_a_cached_epoch_is_freed(tables):
+    """The autograd node of a cached epoch (fit_epoch._EpochEval) holds its fitter weakly: after two epochs of the reference's loop,
+    the second served from the cache, dropping the fitter frees it and everything it held on the device.  (A first fitter of the
+    same size is run and dropped before the measurement: the rasteriser workspace is per device and outlives every fitter.)"""
+    from smilify_amd import synthetic
+
+    t = tables("synthetic")
+    N, W = 6, 2
+
+    def run():
+        f = synthetic.make_problem(t, N, 1, 40, DEV, radius=2.2, seed=5, window=W)
+        opt = torch.optim.Adam(f.parameters(), lr=5e-3, betas=(0.5, 0.999))
+        for _ in range(2):
+            opt.zero_grad()
+            acc = 0
+            for j in range(0, N, W):
+                loss, _ = f(list(range(j, j + W)), LOOP_WEIGHTS, 1)
+                acc = acc + loss.mean()
+            acc.backward()
+            opt.step()
+        assert f._epoch is not None and f._epoch["served"] == N // W
+        return weakref.ref(f)
+
+    run()
+    gc.collect()
+    torch.cuda.synchronize()
+    start = torch.cuda.memory_allocated()
+    ref = run()  # (the fitter itself is a local of run(): gone with its frame)
+    gc.collect()
+    torch.cuda.synchronize()
+    assert ref() is None, "a fitter that served a cached epoch is kept alive"
+    assert torch.cuda.memory_allocated() == start
+
+
+def test_invalidate_targets_drops_the_cached_epoch(tables):
+    """Targets edited through ``.data`` move no version counter; ``invalidate_targets()`` is the documented way to tell the fitter.
+    The next ``forward`` under unchanged parameters must then see the edited targets: loss and gradient of a fresh fitter built
+    with them (all parameters' gradients, concatenated; same kernels on the same inputs: 1e-5 of the largest entry, some 80 fp32 ulps of
+    it, allows for the order of the accumulations that are not fixed-order only), and not the ones the cached epoch holds (the edit moves the joint targets by 3 px and blanks half of every silhouette)."""
+    from smilify_amd import synthetic
+
+    t = tables("synthetic")
+    N, W, S = 6, 2, 40
+    make = lambda: synthetic.make_problem(t, N, 1, S, DEV, radius=2.2, seed=5, window=W)  # noqa: E731
+
+    def window0(f):
+        for p in f.parameters():
+            p.grad = None
+        loss, _ = f(list(range(W)), LOOP_WEIGHTS, 1)
+        loss.backward()
+        return float(loss), np.concatenate([p.grad.detach().cpu().numpy().ravel() for p in f.parameters() if p.grad is not None])
+
+    f = make()
+    for j in range(0, N, W):
+        f(list(range(j, j + W)), LOOP_WEIGHTS, 1)
+    assert f._epoch is not None and f._epoch["served"] >= 1  # the epoch is cached
+    stale_loss, stale_grad = window0(make())
+    f.target_joints.data[..., 0] += 3.0
+    f.sil_imgs.data[..., : S // 2] = 0
+    f.invalidate_targets()
+    loss, grad = window0(f)
+    fresh = make()
+    fresh.target_joints, fresh.sil_imgs = f.target_joints.clone(), f.sil_imgs.clone()
+    want_loss, want_grad = window0(fresh)
+    print(f"loss {loss} fresh {want_loss} stale {stale_loss}; max |grad - fresh| {np.abs(grad - want_grad).max()}, "
+          f"max |grad - stale| {np.abs(grad - stale_grad).max()}, max |fresh| {np.abs(want_grad).max()}")
+    assert abs(loss - want_loss) <= 1e-5 * abs(want_loss)
+    assert np.abs(grad - want_grad).max() <= 1e-5 * np.abs(want_grad).max()
+    assert abs(loss - stale_loss) > 1e-3 * abs(stale_loss)
+    assert np.abs(grad - stale_grad).max() > 1e-3 * np.abs(stale_grad).max()
+
 
 def test_renderer_topology_cache_is_keyed_by_content(tables):
     from smilify_amd.p3d_renderer import Renderer
