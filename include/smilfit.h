@@ -380,9 +380,11 @@ int smil_pix_scale(const SmilFitConfig *cfg, int32_t views, int32_t S, float *pi
 int smil_image_abs_sum(const void *images, int32_t is_u8, int32_t N, int32_t pixels, float *out, void *stream);
 int smil_sil_objective(const float *loss_img, const float *pix_scale, int32_t N, float *objs, void *stream);
 
-/* torch.optim.Adam semantics (no amsgrad, no weight decay). step = 1-based step count. */
+/* torch.optim.Adam semantics (no amsgrad, no weight decay). step = 1-based step count.  The betas are double in all three entry
+ * points: 1 - beta is formed in double from the value the caller wrote (1 - 0.999 = 0.001, as torch does) and then rounded to
+ * float32, where 1.0f - 0.999f would be 1.3e-5 off.  Everything else, the bias corrections included, is float32 arithmetic. */
 int smil_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
-                   float lr, float beta1, float beta2, float eps, int32_t step, void *stream);
+                   float lr, double beta1, double beta2, float eps, int32_t step, void *stream);
 /* The same update for up to SMIL_ADAM_MAX_TENSORS parameter tensors in ONE launch (a fit iteration updates five small
  * tensors; five launches cost more than the arithmetic).  Each tensor has its own learning rate and step count. */
 #define SMIL_ADAM_MAX_TENSORS 8
@@ -394,12 +396,12 @@ typedef struct {
     float lr;
     int32_t step;             /* 1-based */
 } SmilAdamTensor;
-int smil_adam_step_multi(const SmilAdamTensor *tensors, int32_t count, float beta1, float beta2, float eps, void *stream);
+int smil_adam_step_multi(const SmilAdamTensor *tensors, int32_t count, double beta1, double beta2, float eps, void *stream);
 
 /* Same update with the step count read from device memory: step = *step_dev - step_offset.  Lets a whole fit iteration be
  * captured once in a hipGraph and replayed (the host only bumps the counter - or the graph does, with an increment node). */
 int smil_adam_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
-                       float lr, float beta1, float beta2, float eps, const int32_t *step_dev, int32_t step_offset,
+                       float lr, double beta1, double beta2, float eps, const int32_t *step_dev, int32_t step_offset,
                        void *stream);
 
 /* ------------------------------------------------------------------------------------------

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SMILFIT_LIB: load another build of the same library (instrumented builds under tools/dbg); never a CPU path
@@ -147,10 +147,10 @@ def load():
     lib.smil_image_abs_sum.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]
     lib.smil_sil_objective.argtypes = [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]
     lib.smil_window_terms.argtypes = [POINTER(FitConfig), c_int32, c_int32] + [c_void_p] * 10 + [c_int32, c_void_p]
-    lib.smil_adam_step.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float,
+    lib.smil_adam_step.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_double, c_double, c_float,
                                    c_int32, c_void_p]
-    lib.smil_adam_step_multi.argtypes = [POINTER(AdamTensor), c_int32, c_float, c_float, c_float, c_void_p]
-    lib.smil_adam_step_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float,
+    lib.smil_adam_step_multi.argtypes = [POINTER(AdamTensor), c_int32, c_double, c_double, c_float, c_void_p]
+    lib.smil_adam_step_dev.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_double, c_double, c_float,
                                        c_void_p, c_int32, c_void_p]
     lib.smil_colour_workspace_bytes.argtypes = [c_void_p, c_int32, c_int32]
     lib.smil_colour_workspace_bytes.restype = c_size_t

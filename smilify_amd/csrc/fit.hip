@@ -48,7 +48,8 @@ __device__ __forceinline__ void prior_losses_body(const SmilFitConfig &c, const 
                 if (c.w_limit > 0.f) {
                     const float s = c.w_limit / (bw * tnorm);
                     o_limit += s * (fmaxf(cur - c.limit, 0.f) + fmaxf(-c.limit - cur, 0.f));
-                    grad += s * ((cur > c.limit ? 1.f : 0.f) - (cur < -c.limit ? 1.f : 0.f));
+                    // on the kink autograd of torch.max(jrot - lim, zeros) hands each side half the upstream gradient
+                    grad += s * ((cur > c.limit ? 1.f : cur == c.limit ? 0.5f : 0.f) - (cur < -c.limit ? 1.f : cur == -c.limit ? 0.5f : 0.f));
                 }
                 // pose prior (identity precision, root excluded; fitter.py:25-52,310-316): mean over b_w*3J
                 if (c.w_pose > 0.f) {
@@ -438,13 +439,19 @@ extern "C" int smil_image_abs_sum(const void *images, int32_t is_u8, int32_t N, 
 }
 
 // torch.optim.Adam (single tensor path, no amsgrad / weight decay / maximize)
+//
+// The betas cross the C ABI as double.  torch forms 1 - beta in double from the caller's Python float (1 - 0.999 = 0.001) and only then
+// rounds to float32; 1.0f - 0.999f is off from 0.001 by 1.3e-5 relative, a bias of that size in every exp_avg_sq.  beta itself and
+// the bias corrections are float32, as before.
+static float one_minus(double beta) { return (float)(1.0 - beta); }
+
 __global__ void __launch_bounds__(256) k_adam(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
                                               float *__restrict__ v, long long n, float lr, float b1, float b2, float eps,
-                                              float bc1, float bc2_sqrt) {
+                                              float omb1, float omb2, float bc1, float bc2_sqrt) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const float gi = g[i];
-        const float mi = m[i] + (gi - m[i]) * (1.0f - b1);     // exp_avg.lerp_(grad, 1 - beta1)
-        const float vi = v[i] * b2 + (1.0f - b2) * gi * gi;     // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+        const float mi = m[i] + (gi - m[i]) * omb1;     // exp_avg.lerp_(grad, 1 - beta1)
+        const float vi = v[i] * b2 + omb2 * gi * gi;     // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
         m[i] = mi; v[i] = vi;
         const float denom = sqrtf(vi) / bc2_sqrt + eps;
         p[i] = p[i] - (lr / bc1) * (mi / denom);
@@ -456,21 +463,22 @@ struct AdamMulti {
     float bc1[SMIL_ADAM_MAX_TENSORS], bc2_sqrt[SMIL_ADAM_MAX_TENSORS];
 };
 
-__global__ void __launch_bounds__(256) k_adam_multi(AdamMulti a, float b1, float b2, float eps) {
+__global__ void __launch_bounds__(256) k_adam_multi(AdamMulti a, float b1, float b2, float eps, float omb1, float omb2) {
     const SmilAdamTensor &t = a.t[blockIdx.y];
     const float bc1 = a.bc1[blockIdx.y], bc2_sqrt = a.bc2_sqrt[blockIdx.y], lr = t.lr;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < t.n; i += (long long)gridDim.x * blockDim.x) {
         const float gi = t.grad[i];
-        const float mi = t.exp_avg[i] + (gi - t.exp_avg[i]) * (1.0f - b1);
-        const float vi = t.exp_avg_sq[i] * b2 + (1.0f - b2) * gi * gi;
+        const float mi = t.exp_avg[i] + (gi - t.exp_avg[i]) * omb1;
+        const float vi = t.exp_avg_sq[i] * b2 + omb2 * gi * gi;
         t.exp_avg[i] = mi; t.exp_avg_sq[i] = vi;
         const float denom = sqrtf(vi) / bc2_sqrt + eps;
         t.param[i] = t.param[i] - (lr / bc1) * (mi / denom);
     }
 }
 
-extern "C" int smil_adam_step_multi(const SmilAdamTensor *tensors, int32_t count, float beta1, float beta2, float eps,
+extern "C" int smil_adam_step_multi(const SmilAdamTensor *tensors, int32_t count, double beta1_, double beta2_, float eps,
                                     void *stream_) {
+    const float beta1 = (float)beta1_, beta2 = (float)beta2_;
     SMIL_REQUIRE(tensors && count > 0 && count <= SMIL_ADAM_MAX_TENSORS, "smil_adam_step_multi: count=%d outside 1..%d", count,
                  SMIL_ADAM_MAX_TENSORS);
     AdamMulti a;
@@ -484,20 +492,21 @@ extern "C" int smil_adam_step_multi(const SmilAdamTensor *tensors, int32_t count
         n_max = std::max<long long>(n_max, t.n);
     }
     const int gx = (int)std::min<long long>(512, (n_max + 255) / 256);
-    hipLaunchKernelGGL(k_adam_multi, dim3(gx, count), dim3(256), 0, (hipStream_t)stream_, a, beta1, beta2, eps);
+    hipLaunchKernelGGL(k_adam_multi, dim3(gx, count), dim3(256), 0, (hipStream_t)stream_, a, beta1, beta2, eps, one_minus(beta1_),
+                       one_minus(beta2_));
     SMIL_LAUNCH_CHECK();
     return SMIL_OK;
 }
 
 __global__ void __launch_bounds__(256) k_adam_dev(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
                                                   float *__restrict__ v, long long n, float lr, float b1, float b2, float eps,
-                                                  const int *__restrict__ step_dev, int step_offset) {
+                                                  float omb1, float omb2, const int *__restrict__ step_dev, int step_offset) {
     const float t = (float)(*step_dev - step_offset);
     const float bc1 = 1.0f - powf(b1, t), bc2_sqrt = sqrtf(1.0f - powf(b2, t));
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const float gi = g[i];
-        const float mi = m[i] + (gi - m[i]) * (1.0f - b1);
-        const float vi = v[i] * b2 + (1.0f - b2) * gi * gi;
+        const float mi = m[i] + (gi - m[i]) * omb1;
+        const float vi = v[i] * b2 + omb2 * gi * gi;
         m[i] = mi; v[i] = vi;
         const float denom = sqrtf(vi) / bc2_sqrt + eps;
         p[i] = p[i] - (lr / bc1) * (mi / denom);
@@ -505,24 +514,24 @@ __global__ void __launch_bounds__(256) k_adam_dev(float *__restrict__ p, const f
 }
 
 extern "C" int smil_adam_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr,
-                                  float beta1, float beta2, float eps, const int32_t *step_dev, int32_t step_offset,
+                                  double beta1, double beta2, float eps, const int32_t *step_dev, int32_t step_offset,
                                   void *stream_) {
     SMIL_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && step_dev, "smil_adam_step_dev: bad argument");
     const int grid = (int)std::min<long long>(2048, (n + 255) / 256);
     hipLaunchKernelGGL(k_adam_dev, dim3(grid), dim3(256), 0, (hipStream_t)stream_, param, grad, exp_avg, exp_avg_sq, (long long)n,
-                       lr, beta1, beta2, eps, step_dev, step_offset);
+                       lr, (float)beta1, (float)beta2, eps, one_minus(beta1), one_minus(beta2), step_dev, step_offset);
     SMIL_LAUNCH_CHECK();
     return SMIL_OK;
 }
 
 extern "C" int smil_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr,
-                              float beta1, float beta2, float eps, int32_t step, void *stream_) {
+                              double beta1, double beta2, float eps, int32_t step, void *stream_) {
     SMIL_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && step > 0, "smil_adam_step: bad argument");
-    const float bc1 = 1.0f - powf(beta1, (float)step);
-    const float bc2 = 1.0f - powf(beta2, (float)step);
+    const float bc1 = 1.0f - powf((float)beta1, (float)step);
+    const float bc2 = 1.0f - powf((float)beta2, (float)step);
     const int grid = (int)std::min<long long>(2048, (n + 255) / 256);
     hipLaunchKernelGGL(k_adam, dim3(grid), dim3(256), 0, (hipStream_t)stream_, param, grad, exp_avg, exp_avg_sq, (long long)n, lr,
-                       beta1, beta2, eps, bc1, sqrtf(bc2));
+                       (float)beta1, (float)beta2, eps, one_minus(beta1), one_minus(beta2), bc1, sqrtf(bc2));
     SMIL_LAUNCH_CHECK();
     return SMIL_OK;
 }
