@@ -12,7 +12,9 @@
 //                        which is order independent (distances are >= 0, so their bits order like the values; ties go to the
 //                        smaller index, as a sequential scan with < gives).
 //  * k_chamfer_owned     thread per query: argmin out, the owned gradient 2 w (q - c*), and the scattered side (c* - q) added to the
-//                        candidate's int64 fixed-point accumulator (2^-32 units: integer sums do not depend on the order).
+//                        candidate's int64 fixed-point accumulator (integer sums do not depend on the order).  The unit is a
+//                        power of two chosen per (mesh, direction) from the largest minimum found and the number of queries, so
+//                        that the sum uses the 64 bits whatever the clouds' extent (ch_fix_exp).
 //  * k_chamfer_scatter   thread per point: the scattered sum converted and added to the owned gradient.
 //  * k_chamfer_reduce    per (mesh, direction) sums of the minima in a fixed order, then the batch in a fixed order.
 //  * k_mesh_reg          edge, normal consistency and uniform Laplacian terms and their gradients in one pass: thread t evaluates edge
@@ -26,7 +28,6 @@
 #define CH_BLOCK 256
 #define CH_QPT 4                      // query points per lane of k_chamfer_nn
 #define CH_TILE 256                   // candidates staged in LDS per step
-#define CH_FIX 4294967296.0           // fixed-point scale of the scattered gradient sums (2^32)
 #define REG_BLOCK 256
 
 // ---------------------------------------------------------------------------------------------
@@ -102,6 +103,7 @@ struct ChamferArgs {
     unsigned long long *key;  // (N, P[0] + P[1]) {distance bits, candidate index}: direction 0's queries first
     float *dist;              // (N, P[0] + P[1])
     long long *acc;           // (N, P[0] + P[1], 3) fixed-point scattered sums, per point of either cloud
+    unsigned int *dmax;       // (N, 2) bits of the largest per-split minimum of (mesh, direction): bounds every |q - c*|^2
     int *idx[2];              // (N, P[d]) or NULL
     float *grad[2];           // (N, P[d], 3) or NULL
     float *part;              // (N, dirs)
@@ -109,6 +111,17 @@ struct ChamferArgs {
 };
 
 __device__ __forceinline__ size_t ch_row(const ChamferArgs &a, int n, int d) { return (size_t)n * (a.P[0] + a.P[1]) + (d ? a.P[0] : 0); }
+
+// Exponent s of the fixed-point unit 2^-s of direction d's scattered sums in mesh n.  Every component of q - c* is below 2^eb, where
+// 2^(2 eb) >= the largest minimum (one more bit covers the rounding of the distance), and at most P[d] < 2^pb of them meet in one
+// sum: with s = 61 - pb - eb the sum stays below 2^62.  A fixed 2^-32 lost the gradient of clouds whose extent is far below 1.
+__device__ __forceinline__ int ch_fix_exp(const ChamferArgs &a, int n, int d) {
+    int ex;
+    frexpf(fminf(__uint_as_float(a.dmax[n * 2 + d]), 3.0e38f), &ex);  // (non-finite input: any finite unit)
+    const int eb = ((ex + 1) >> 1) + 1;
+    const int pb = 32 - __clz(a.P[d]);
+    return 61 - pb - eb;
+}
 
 __global__ void __launch_bounds__(CH_BLOCK) k_chamfer_nn(ChamferArgs a) {
     __shared__ float4 tile[CH_TILE];
@@ -151,6 +164,7 @@ __global__ void __launch_bounds__(CH_BLOCK) k_chamfer_nn(ChamferArgs a) {
         }
     }
     unsigned long long *key = a.key + ch_row(a, n, d);
+    float bmax = 0.f;
 #pragma unroll
     for (int k = 0; k < CH_QPT; ++k) {
         const int q = q0 + k * CH_BLOCK + threadIdx.x;
@@ -158,7 +172,12 @@ __global__ void __launch_bounds__(CH_BLOCK) k_chamfer_nn(ChamferArgs a) {
             const unsigned long long kv = ((unsigned long long)__float_as_uint(best[k]) << 32) | (unsigned long long)(uint32_t)bi[k];
             if (a.splits == 1) key[q] = kv;
             else atomicMin(&key[q], kv);
+            bmax = fmaxf(bmax, best[k]);
         }
+    }
+    if (a.grad[0]) {  // distances are >= 0: their bits order like the values, and a maximum does not depend on the order
+        bmax = wave_max(bmax);
+        if ((threadIdx.x & 63) == 0) atomicMax(&a.dmax[n * 2 + d], __float_as_uint(bmax));
     }
 }
 
@@ -184,9 +203,10 @@ __global__ void __launch_bounds__(256) k_chamfer_owned(ChamferArgs a) {
     }
     if (a.grad[1 - d]) {  // candidate j receives 2 w_d (c - q): accumulated as integers, so the order of the additions does not matter
         long long *acc = a.acc + (ch_row(a, n, 1 - d) + j) * 3;
+        const int fix = ch_fix_exp(a, n, d);
 #pragma unroll
         for (int k = 0; k < 3; ++k)
-            atomicAdd((unsigned long long *)&acc[k], (unsigned long long)__double2ll_rn(-(double)e[k] * CH_FIX));
+            atomicAdd((unsigned long long *)&acc[k], (unsigned long long)__double2ll_rn(ldexp(-(double)e[k], fix)));
     }
 }
 
@@ -201,9 +221,10 @@ __global__ void __launch_bounds__(256) k_chamfer_scatter(ChamferArgs a) {
     float *g = a.grad[side] + ((size_t)n * P + i) * 3;
     const long long *acc = a.acc + (ch_row(a, n, side) + i) * 3;
     const float s = receives ? 2.0f * a.w[1 - side] : 0.f;
+    const int fix = receives ? ch_fix_exp(a, n, 1 - side) : 0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const float sc = receives ? (float)((double)acc[k] * (1.0 / CH_FIX)) * s : 0.f;
+        const float sc = receives ? (float)ldexp((double)acc[k], -fix) * s : 0.f;
         g[k] = (has_owned ? g[k] : 0.f) + sc;
     }
 }
@@ -233,6 +254,7 @@ static size_t chamfer_layout(int N, int P1, int P2, char *base, ChamferArgs &a) 
     a.dist = w.take<float>(pts);
     a.acc = w.take<long long>(pts * 3);
     a.part = w.take<float>((size_t)N * 2);
+    a.dmax = w.take<unsigned int>((size_t)N * 2);
     return w.used;
 }
 
@@ -268,7 +290,10 @@ extern "C" int smil_chamfer(const float *x, const float *y, int32_t N, int32_t P
     const int max_split = std::max(1, std::min(P1, P2) / (4 * CH_TILE));
     a.splits = std::max(1, std::min(max_split, ceil_div(2048, base)));
     SMIL_HIP(hipMemsetAsync(a.key, 0xFF, pts * 8, stream));
-    if (d_x) SMIL_HIP(hipMemsetAsync(a.acc, 0, pts * 3 * 8, stream));
+    if (d_x) {
+        SMIL_HIP(hipMemsetAsync(a.acc, 0, pts * 3 * 8, stream));
+        SMIL_HIP(hipMemsetAsync(a.dmax, 0, (size_t)N * 2 * sizeof(unsigned int), stream));
+    }
     hipLaunchKernelGGL(k_chamfer_nn, dim3(qblocks, a.splits, N * a.dirs), dim3(CH_BLOCK), 0, stream, a);
     SMIL_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_chamfer_owned, dim3(ceil_div(std::max(P1, P2), 256), 1, N * a.dirs), dim3(256), 0, stream, a);

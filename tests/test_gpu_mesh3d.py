@@ -102,11 +102,11 @@ def test_chamfer_reductions_and_drop_in(tables):
                 assert _rel(float(loss), float(rl)) <= 1e-5, (sd, pr, br)
                 gx, gy = torch.autograd.grad(3.0 * loss, (xg, yg))
                 xr, yr = x.double().requires_grad_(True), y.double().requires_grad_(True)
-                rl2 = ref.chamfer_at(xr, yr, *ref.chamfer(xr.detach(), yr.detach())[1:], single_directional=sd)
-                if pr == "mean" and br == "mean":
-                    wx, wy = torch.autograd.grad(3.0 * rl2, (xr, yr))
-                    assert (gx.double().cpu() - wx).abs().max() <= 1e-5 * wx.abs().max()
-                    assert (gy.double().cpu() - wy).abs().max() <= 1e-5 * wy.abs().max()  # (single_directional: y gets x's argmins)
+                rl2 = ref.chamfer_at(xr, yr, *ref.chamfer(xr.detach(), yr.detach())[1:], single_directional=sd, point_sum=pr == "sum",
+                                     batch_sum=br == "sum")
+                wx, wy = torch.autograd.grad(3.0 * rl2, (xr, yr))
+                assert (gx.double().cpu() - wx).abs().max() <= 1e-5 * wx.abs().max(), (sd, pr, br)
+                assert (gy.double().cpu() - wy).abs().max() <= 1e-5 * wy.abs().max(), (sd, pr, br)  # (single_directional: y gets x's argmins)
 
 
 # ---- sampling -----------------------------------------------------------------------------------------------------------------

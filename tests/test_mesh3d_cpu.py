@@ -164,3 +164,133 @@ def test_python_layer_raises_for_out_of_scope_options():
         raise AssertionError("cot accepted")
     assert set(fit3d.SMALParamGroup.param_map) == {"init", "init_rot_lock", "init_rot_lock_trans", "init_rot_lock_trans_scale", "default",
                                                     "default_with_betas_trans", "shape", "pose", "deform", "all"}
+
+
+# ---- the references of tests/test_gpu_mesh3d_kernels.py, pinned without a GPU ------------------------------------------------------
+def test_philox_known_answers():
+    """The three known-answer vectors of philox4x32-10 published with Random123 (kat_vectors)."""
+    kat = [((0, 0, 0, 0), (0, 0), (0x6627E8D5, 0xE169C58D, 0xBC57AC4C, 0x9B00DBD8)),
+           ((0xFFFFFFFF,) * 4, (0xFFFFFFFF,) * 2, (0x408F276D, 0x41C83B0E, 0xA20BC7C6, 0x6D5451FD)),
+           ((0x243F6A88, 0x85A308D3, 0x13198A2E, 0x03707344), (0xA4093822, 0x299F31D0), (0xD16CFE09, 0x94FDCCEB, 0x5001E420, 0x24126EA1))]
+    for c, k, want in kat:
+        assert tuple(int(v) for v in ref.philox4x32_10(c, k)) == want
+    # arrays give what scalars give, element by element
+    cs = [np.array([c[i] for c, _, _ in kat], np.uint64) for i in range(4)]
+    ks = [np.array([k[i] for _, k, _ in kat], np.uint64) for i in range(2)]
+    out = ref.philox4x32_10(cs, ks)
+    assert [tuple(int(o[j]) for o in out) for j in range(3)] == [w for _, _, w in kat]
+
+
+def test_sampler_restatement_properties():
+    v = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [2, 0, 0], [3, 0, 0], [2, 3, 0], [9, 9, 9]], np.float32)
+    f = np.array([[0, 0, 1], [0, 1, 2], [2, 2, 2], [3, 4, 5], [6, 6, 6], [6, 6, 6]])  # mesh 0: faces 0-3, mesh 1: no area, mesh 2: none
+    off = np.array([0, 4, 6, 6])
+    cum = np.array([0, 0.25, 0.25, 1.0, 0, 0])
+    S = 4000
+    pts, face, fmax = ref.sample_points(v, f, off, cum, S, seed=(5 << 32) | 9)
+    assert (face[1:] == -1).all() and (pts[1:] == 0).all()
+    assert set(np.unique(face[0]).tolist()) == {1, 3}
+    n3 = int((face[0] == 3).sum())
+    assert abs(n3 - 0.75 * S) <= 5 * np.sqrt(S * 0.75 * 0.25), n3
+    assert (fmax[0][face[0] == 1] == 1).all() and (fmax[0][face[0] == 3] == 3).all()
+    # inside the chosen triangle: z = 0, and face 1's points have x, y >= 0, x + y <= 1
+    p1 = pts[0][face[0] == 1]
+    assert (pts[0][:, 2] == 0).all() and (p1 >= 0).all() and (p1[:, 0] + p1[:, 1] <= 1 + 1e-7).all()
+    # the seed's two halves, the mesh index and the sample index all enter the stream
+    uf = [ref.sample_draws(n, 8, seed)[0] for n, seed in ((0, 9), (0, 9 | (1 << 32)), (1, 9), (0, 10))]
+    assert all(not np.array_equal(uf[0], u) for u in uf[1:]) and len(np.unique(uf[0])) == 8
+    uf, u, w = ref.sample_draws(2, 1000, 77)
+    assert uf.dtype == np.float64 and u.dtype == np.float32 and (uf >= 0).all() and (uf < 1).all() and (u < 1).all() and (w < 1).all()
+    assert (np.modf(uf * 2.0 ** 32)[0] != 0).any()  # more than 32 bits in the face uniform
+
+
+def test_dyadic_grid_inputs_are_exact_and_tied():
+    for N, P1, P2, sd, splits in ref.DYADIC_SHAPES:
+        assert ref.chamfer_splits(N, P1, P2, sd) == splits, (N, P1, P2, sd)
+        x, y = ref.dyadic_clouds(N, P1, P2)
+        assert x.dtype == np.float32 and (x * 8 == np.round(x * 8)).all() and np.abs(x).max() <= 1 and np.abs(y).max() <= 1
+        r = ref.dyadic_reference(N, P1, P2)
+        assert (r["dx"] * 64 == np.round(r["dx"] * 64)).all() and (r["dx"].sum() + r["dy"].sum()) * 64 < 2 ** 24
+        if min(P1, P2) >= ref.TIE_QUOTA_MIN_P:
+            assert ref.tie_fraction(r, sd) >= 0.10, (N, P1, P2, ref.tie_fraction(r, sd))
+        # numpy's first-occurrence rule: no smaller index is as near
+        n, q = 0, P1 // 2
+        d = ((x[n, q].astype(np.float64) - y[n].astype(np.float64)) ** 2).sum(-1)
+        assert d[r["ix"][n, q]] == d.min() == r["dx"][n, q] and (d[:r["ix"][n, q]] > d.min()).all()
+        assert (d == d.min()).sum() == r["nx"][n, q]
+    assert ref.chamfer_chunk(4100, 4) == 1280 and ref.chamfer_chunk(5000, 3) == 1792 and ref.chamfer_chunk(1, 1) == 256
+
+
+def test_chamfer_brute_and_chamfer_at_agree_with_chamfer():
+    g = torch.Generator().manual_seed(8)
+    x, y = torch.randn(3, 40, 3, generator=g, dtype=torch.float64), torch.randn(3, 55, 3, generator=g, dtype=torch.float64)
+    r = ref.chamfer_brute(x.numpy(), y.numpy())
+    for sd in (False, True):
+        for ps in (False, True):
+            for bs in (False, True):
+                loss, ix, iy = ref.chamfer(x, y, sd, ps, bs)
+                assert np.array_equal(r["ix"], ix.numpy()) and np.array_equal(r["iy"], iy.numpy())
+                assert abs(ref.chamfer_loss_from(r["dx"], r["dy"], sd, ps, bs) - float(loss)) <= 1e-12 * float(loss)
+                xr, yr = x.clone().requires_grad_(True), y.clone().requires_grad_(True)
+                at = ref.chamfer_at(xr, yr, ix, iy, sd, ps, bs)
+                assert abs(float(at.detach()) - float(loss)) <= 1e-12 * float(loss), (sd, ps, bs)
+                gx, gy = torch.autograd.grad(at, (xr, yr))
+                ox, sx, oy, sy = ref.chamfer_grad_parts(x.numpy(), y.numpy(), r["ix"], r["iy"], sd, ps, bs)
+                assert np.abs(ox + sx - gx.numpy()).max() <= 1e-12 * float(gx.abs().max())
+                assert np.abs(oy + sy - gy.numpy()).max() <= 1e-12 * float(gy.abs().max())
+                if sd:
+                    assert (oy == 0).all() and (sx == 0).all()
+
+
+def test_hand_meshes_sparse_against_dense_laplacian_and_known_answers():
+    from smilify_amd.mesh3d import Topology
+
+    meshes = ref.hand_meshes()
+    assert [len(meshes[k][0]) for k in ("grid_15x17", "grid_16x16", "grid_16x16_plus_1")] == [255, 256, 257]
+    for name, (v, f) in meshes.items():
+        assert v.dtype == np.float32
+        vb = torch.from_numpy(v).double()[None] * torch.tensor([1.0, 0.5, 0.25], dtype=torch.float64)[:, None, None]
+        ls, gs = ref.with_grad(ref.laplacian_loss_sparse, vb, f)
+        ld, gd = ref.with_grad(ref.laplacian_loss, vb, f)
+        assert abs(ls - ld) <= 1e-12 * max(ld, 1.0), name
+        if name != "flat_grid_5x5":  # (there the dense form's 1/deg products leave residuals of 1e-16 whose direction is noise)
+            assert (gs - gd).abs().max() <= 1e-9 * gd.abs().max(), name
+        assert torch.isfinite(gs).all(), name
+        T = Topology(f, len(v))
+        assert np.array_equal(T.edges, ref.edges_brute(f)) and T.Q == len(ref.normal_pairs_brute(f)), name
+    T = Topology(meshes["triangle"][1], 3)
+    assert (T.E, T.Q) == (3, 0)
+    T = Topology(meshes["three_on_edge"][1], 5)
+    assert T.Q == 3
+    roles = {i: sorted((T.vpair[T.vpair_ptr[i]:T.vpair_ptr[i + 1]] & 3).tolist()) for i in range(5)}
+    assert roles[0] == [0, 0, 0] and roles[1] == [1, 1, 1] and sorted(sum((roles[i] for i in (2, 3, 4)), [])) == [2, 2, 2, 3, 3, 3]
+    assert any(2 in roles[i] and 3 in roles[i] for i in (2, 3, 4))
+    T = Topology(meshes["grid_16x16"][1], 256)
+    assert T.E > 2 * 256 and T.Q > 2 * 256  # the block count of k_mesh_reg comes from E
+    T = Topology(meshes["isolated"][1], 6)
+    assert T.deg[4] == T.deg[5] == 0 and T.inv_deg[4] == 0
+    # closed forms of the float64 reference
+    one = lambda name, fn: float(fn(torch.from_numpy(meshes[name][0]).double()[None], meshes[name][1]))  # noqa: E731
+    assert one("triangle", ref.normal_loss) == 0.0 and abs(one("triangle", ref.edge_loss) - 4.0 / 3.0) < 1e-12
+    assert abs(one("tetrahedron", ref.edge_loss) - 1.5) < 1e-12
+    assert abs(one("folded", ref.normal_loss) - (1 - ref.FOLD_COS / np.hypot(ref.FOLD_COS, ref.FOLD_SIN))) < 1e-12
+    v = meshes["isolated"][0].astype(np.float64)
+    lap_iso = one("isolated", ref.laplacian_loss_sparse)
+    lap_tet = float(ref.laplacian_loss_sparse(torch.from_numpy(v[:4])[None], meshes["isolated"][1]))
+    assert abs(lap_iso * 6 - (lap_tet * 4 + 0.0 + np.linalg.norm(v[5]))) < 1e-12  # rows of unreferenced vertices are -v_i
+    # the flat grid's interior residuals are exactly 0 in the sparse float64 reference, and its gradient there is autograd's 0
+    v, f = meshes["flat_grid_5x5"]
+    vv = torch.from_numpy(v).double()[None]
+    e = torch.from_numpy(ref.edges_brute(f))
+    rows, cols = torch.cat([e[:, 0], e[:, 1]]), torch.cat([e[:, 1], e[:, 0]])
+    deg = torch.bincount(rows, minlength=25).double()
+    r = torch.zeros_like(vv).index_add_(1, rows, vv[:, cols]) * (1.0 / deg)[None, :, None] - vv  # as laplacian_loss_sparse
+    interior = [i * 5 + j for i in range(1, 4) for j in range(1, 4)]
+    assert (r[0, interior] == 0).all()
+    # a face with a zero normal: torch divides each vector by max(|n|, 1e-8), so the pair's term is 1 and its gradient is finite
+    l, g = ref.with_grad(ref.normal_loss, torch.from_numpy(meshes["zero_normal"][0])[None], meshes["zero_normal"][1])
+    assert np.isfinite(l) and torch.isfinite(g).all() and float(g.abs().max()) > 1e6
+    a = torch.zeros(1, 3, dtype=torch.float64, requires_grad=True)
+    b = torch.tensor([[0.0, 0, 2]], dtype=torch.float64)
+    c = torch.cosine_similarity(a, b, dim=-1)
+    assert float(c.detach()) == 0.0 and torch.equal(torch.autograd.grad(c.sum(), a)[0], torch.tensor([[0.0, 0, 1e8]], dtype=torch.float64))
