@@ -447,6 +447,42 @@ size_t smil_mesh_reg_workspace_bytes(const SmilMeshTopology *t, int32_t B);
 int smil_mesh_regularisers(const SmilMeshTopology *t, const float *verts, int32_t B, int32_t terms, float *out3, float *d_edge,
                            float *d_normal, float *d_lap, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The SDF-guided term of the 3-D registration (reference fitter_3d/utils.py:973-1394, trainer.py:398-433): K nearest neighbours,
+ * the term itself and the vertex sampler.  Deterministic like the functions above.
+ * ---------------------------------------------------------------------------------------- */
+#define SMIL_KNN_MAX_K 64
+/* pytorch3d.ops.knn_points(x, y, K) with norm=2, no lengths: for every point of x (N,P1,3) its K nearest points of y (N,P2,3) by
+ * squared distance, ascending by (distance, index): dists_x / idx_x (N,P1,K).  With dists_y / idx_y (N,P2,K) also y's points in x
+ * (both or neither).  1 <= K <= SMIL_KNN_MAX_K and K <= the number of candidates.  After the call the first 8 bytes of the
+ * workspace hold the number of list insertions as a uint64 (a measure of the search's work). */
+size_t smil_knn_workspace_bytes(int32_t N, int32_t P1, int32_t P2, int32_t K);
+int smil_knn(const float *x, const float *y, int32_t N, int32_t P1, int32_t P2, int32_t K, float *dists_x, int32_t *idx_x, float *dists_y,
+             int32_t *idx_y, void *workspace, void *stream);
+
+/* SDF_distance (utils.py:1127): with z the per-(mesh, side) z-scores of the values ((s - mean) / max(unbiased std, 1e-8)) and
+ * (d_ik, j_ik) the K nearest candidates of query i, r_i = sum_k softmax_k(-|z_q[i] - z_c[j_ik]| / 0.1) d_ik;
+ * loss[0] = red_n [ red_i r_i(x in y) + red_j r_j(y in x) ], red = mean (or sum with point_sum / batch_sum); the second half is dropped
+ * when single_directional.  x (N,P1,3), y (N,P2,3), x_sdf (N,P1), y_sdf (N,P2); P1, P2 >= 2.  d_x, d_y: dloss/dx, dloss/dy (both
+ * or neither; the values carry no gradient).  dists_x / idx_x (N,P1,K), dists_y / idx_y (N,P2,K): the neighbour tables, or NULL.
+ * The first 8 bytes of the workspace: as smil_knn. */
+size_t smil_sdf_distance_workspace_bytes(int32_t N, int32_t P1, int32_t P2, int32_t K);
+int smil_sdf_distance(const float *x, const float *y, const float *x_sdf, const float *y_sdf, int32_t N, int32_t P1, int32_t P2, int32_t K,
+                      int32_t single_directional, int32_t point_sum, int32_t batch_sum, float *loss, float *d_x, float *d_y,
+                      float *dists_x, int32_t *idx_x, float *dists_y, int32_t *idx_y, void *workspace, void *stream);
+
+/* sample_points_from_meshes_and_SDF (utils.py:1264): S vertices per mesh of N packed meshes, uniform with replacement.  verts
+ * (n_verts,3) and values (n_verts) packed, vert_off (N+1) the first vertex of every mesh.  Sample s of mesh n takes word 0 of
+ * Philox4x32-10 at counter (s, n, 1, 0) under the key (seed lo, seed hi) as r and the vertex (r * V_n) >> 32.  out (N,S,3),
+ * out_values (N,S), out_idx (N,S) the vertex within its mesh (-1 and zeros for an empty mesh). */
+int smil_sample_vertices(const float *verts, const float *values, const int32_t *vert_off, int32_t N, int32_t S, uint64_t seed, float *out,
+                         float *out_values, int32_t *out_idx, void *stream);
+/* Its gradient: d_verts (n_verts,3) = the sum of d_pts (N,S,3) over the samples that drew each vertex, in an order-independent
+ * fixed-point sum.  max_verts: the largest mesh's vertex count. */
+size_t smil_sample_vertices_backward_workspace_bytes(int32_t n_verts, int32_t N);
+int smil_sample_vertices_backward(const float *d_pts, const int32_t *idx, const int32_t *vert_off, int32_t n_verts, int32_t max_verts,
+                                  int32_t N, int32_t S, float *d_verts, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,8 @@ EXPORTS = [
     "smil_image_abs_sum", "smil_sil_objective", "smil_window_terms", "smil_adam_step", "smil_adam_step_multi", "smil_adam_step_dev", "smil_profile_enable",
     "smil_profile_read", "smil_colour_workspace_bytes", "smil_render_colour",
     "smil_sample_points", "smil_chamfer_workspace_bytes", "smil_chamfer", "smil_mesh_reg_workspace_bytes", "smil_mesh_regularisers",
+    "smil_knn_workspace_bytes", "smil_knn", "smil_sdf_distance_workspace_bytes", "smil_sdf_distance", "smil_sample_vertices",
+    "smil_sample_vertices_backward_workspace_bytes", "smil_sample_vertices_backward",
 ]
 
 N_OBJS = 10
@@ -93,6 +95,7 @@ class MeshTopology(Structure):
 
 
 REG_EDGE, REG_NORMAL, REG_LAPLACIAN = 1, 2, 4
+KNN_MAX_K = 64  # SMIL_KNN_MAX_K
 
 _lib = None
 
@@ -164,6 +167,17 @@ def load():
     lib.smil_mesh_reg_workspace_bytes.argtypes = [POINTER(MeshTopology), c_int32]
     lib.smil_mesh_reg_workspace_bytes.restype = c_size_t
     lib.smil_mesh_regularisers.argtypes = [POINTER(MeshTopology), c_void_p, c_int32, c_int32] + [c_void_p] * 6
+    lib.smil_knn_workspace_bytes.argtypes = [c_int32] * 4
+    lib.smil_knn_workspace_bytes.restype = c_size_t
+    lib.smil_knn.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 6
+    lib.smil_sdf_distance_workspace_bytes.argtypes = [c_int32] * 4
+    lib.smil_sdf_distance_workspace_bytes.restype = c_size_t
+    lib.smil_sdf_distance.argtypes = [c_void_p] * 4 + [c_int32] * 7 + [c_void_p] * 9
+    lib.smil_sample_vertices.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.smil_sample_vertices_backward_workspace_bytes.argtypes = [c_int32, c_int32]
+    lib.smil_sample_vertices_backward_workspace_bytes.restype = c_size_t
+    lib.smil_sample_vertices_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                                  c_void_p]
     lib.smil_profile_enable.argtypes = [c_int32]
     lib.smil_profile_read.argtypes = [POINTER(c_float), POINTER(c_int32)]
     for name in EXPORTS:

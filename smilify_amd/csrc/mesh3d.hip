@@ -21,6 +21,16 @@
 //                        term t, normal pair t and Laplacian row t for the loss, and gathers vertex t's gradient from its neighbour and
 //                        pair incidence lists (recomputing the few terms it touches: no atomics).  Per-block partials, then
 //                        k_mesh_reg_reduce in a fixed order.
+//
+// The SDF-guided term (reference fitter_3d/utils.py:973-1394, trainer.py:398-433), see the section at the end of the file:
+//  * k_knn               wave = KNN_QPW queries, both directions in one launch.  A query's K-list is spread over the wave's lanes as
+//                        64-bit keys {distance bits, candidate index}, ascending; lane l takes candidate c0 + l of every 64, and a
+//                        candidate enters a list only when its key is below the list's K-th (one compare and a ballot per query).
+//  * k_sdf_stats         per (mesh, side) mean and unbiased std of the values in two float64 passes, then the z-scores.
+//  * k_sdf_term          wave per query, lane per neighbour: softmax weights, r_i, the owned gradient, and the scattered gradient into
+//                        the chamfer path's int64 fixed-point accumulators (k_chamfer_scatter / _reduce / _total finish the call).
+//  * k_sample_vertices   lane per sample: a Philox draw keyed by (seed, mesh, sample), index = (r * V_n) >> 32, points and values
+//                        gathered; k_sv_* scatter a gradient on the samples back to the vertices as int64 fixed point.
 #include <algorithm>
 
 #include "common.h"
@@ -99,6 +109,7 @@ struct ChamferArgs {
     const float *pts[2];      // (N, P[d], 3): direction d's queries are pts[d], its candidates pts[1 - d]
     int P[2];
     int N, dirs, splits;
+    int K;                    // terms of one query that can meet in a scattered sum's point: 1 (chamfer), K (the SDF term)
     float w[2];               // loss weight of one term of direction d (1/P and/or 1/N as reduced)
     unsigned long long *key;  // (N, P[0] + P[1]) {distance bits, candidate index}: direction 0's queries first
     float *dist;              // (N, P[0] + P[1])
@@ -114,12 +125,13 @@ __device__ __forceinline__ size_t ch_row(const ChamferArgs &a, int n, int d) { r
 
 // Exponent s of the fixed-point unit 2^-s of direction d's scattered sums in mesh n.  Every component of q - c* is below 2^eb, where
 // 2^(2 eb) >= the largest minimum (one more bit covers the rounding of the distance), and at most P[d] < 2^pb of them meet in one
-// sum: with s = 61 - pb - eb the sum stays below 2^62.  A fixed 2^-32 lost the gradient of clouds whose extent is far below 1.
+// sum (P[d] K < 2^pb in the SDF term, whose addends carry a weight <= 1): with s = 61 - pb - eb the sum stays below 2^62.  A fixed
+// 2^-32 lost the gradient of clouds whose extent is far below 1.
 __device__ __forceinline__ int ch_fix_exp(const ChamferArgs &a, int n, int d) {
     int ex;
     frexpf(fminf(__uint_as_float(a.dmax[n * 2 + d]), 3.0e38f), &ex);  // (non-finite input: any finite unit)
     const int eb = ((ex + 1) >> 1) + 1;
-    const int pb = 32 - __clz(a.P[d]);
+    const int pb = 64 - __clzll((long long)a.P[d] * a.K);
     return 61 - pb - eb;
 }
 
@@ -277,7 +289,7 @@ extern "C" int smil_chamfer(const float *x, const float *y, int32_t N, int32_t P
     chamfer_layout(N, P1, P2, (char *)workspace, a);
     a.pts[0] = x; a.pts[1] = y;
     a.P[0] = P1; a.P[1] = P2;
-    a.N = N; a.dirs = single_directional ? 1 : 2;
+    a.N = N; a.dirs = single_directional ? 1 : 2; a.K = 1;
     const float bw = batch_sum ? 1.0f : 1.0f / (float)N;
     a.w[0] = (point_sum ? 1.0f : 1.0f / (float)P1) * bw;
     a.w[1] = (point_sum ? 1.0f : 1.0f / (float)P2) * bw;
@@ -504,6 +516,440 @@ extern "C" int smil_mesh_regularisers(const SmilMeshTopology *t, const float *ve
     hipLaunchKernelGGL(k_mesh_reg, dim3(nblk, B), dim3(REG_BLOCK), 0, stream, a);
     SMIL_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_mesh_reg_reduce, dim3(1), dim3(256), 0, stream, a, nblk);
+    SMIL_LAUNCH_CHECK();
+    return SMIL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// K nearest neighbours (pytorch3d.ops.knn_points, norm 2, no lengths)
+// ---------------------------------------------------------------------------------------------
+#define KNN_BLOCK 256
+#define KNN_QPW 4                     // queries per wave of k_knn
+#define KNN_QPB (KNN_QPW * KNN_BLOCK / WAVE)
+#define KNN_TILE 256                  // candidates staged in LDS per step
+#define KNN_EMPTY 0xFFFFFFFFFFFFFFFFull
+static_assert(SMIL_KNN_MAX_K == WAVE, "k_knn keeps one list entry per lane");
+
+struct KnnArgs {
+    const float *pts[2];           // (N, P[d], 3): direction d's queries are pts[d], its candidates pts[1 - d]
+    int P[2];
+    int N, dirs, K;
+    float *dists[2];               // (N, P[d], K) ascending by (distance, candidate index)
+    int *idx[2];                   // (N, P[d], K)
+    unsigned int *dmax;            // (N, 2) bits of the largest K-th distance of (mesh, direction), or NULL
+    unsigned long long *n_insert;  // (1) list insertions of the call, or NULL
+};
+
+__device__ __forceinline__ unsigned long long readlane64(unsigned long long v, int lane) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, lane);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// Lane l of a wave holds the l-th smallest key seen so far of each of the wave's KNN_QPW queries (KNN_EMPTY: none yet); keys order
+// like (distance, index) because distances are >= 0.  All 64 entries are kept whatever K is: thr, the key of lane K - 1, is what a
+// candidate has to beat, and the first K lanes are the result.  A step gives every lane one candidate; the lanes whose candidate
+// beats thr are served in lane order (ascending index), each tested again because thr falls with every insertion, and an
+// insertion is one shift by a lane of the entries above the new key.  No list is indexed at run time: nothing goes to scratch.
+__global__ void __launch_bounds__(KNN_BLOCK) k_knn(KnnArgs a) {
+    __shared__ float4 tile[KNN_TILE];
+    const int d = blockIdx.z % a.dirs, n = blockIdx.z / a.dirs;
+    const int Pq = a.P[d], Pc = a.P[1 - d];
+    if ((int)blockIdx.x * KNN_QPB >= Pq) return;  // (block-uniform)
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int q0 = ((int)blockIdx.x * (KNN_BLOCK / WAVE) + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6)) * KNN_QPW;
+    const float *Q = a.pts[d] + (size_t)n * Pq * 3;
+    const float *C = a.pts[1 - d] + (size_t)n * Pc * 3;
+    float qx[KNN_QPW], qy[KNN_QPW], qz[KNN_QPW];
+    unsigned long long key[KNN_QPW], thr[KNN_QPW];
+#pragma unroll
+    for (int k = 0; k < KNN_QPW; ++k) {
+        const int qc = min(q0 + k, Pq - 1);
+        qx[k] = Q[3 * qc]; qy[k] = Q[3 * qc + 1]; qz[k] = Q[3 * qc + 2];
+        key[k] = KNN_EMPTY;
+        thr[k] = q0 + k < Pq ? KNN_EMPTY : 0ull;  // (a query past the end accepts nothing)
+    }
+    unsigned int ins = 0;
+    for (int c0 = 0; c0 < Pc; c0 += KNN_TILE) {
+        const int cnt = min(KNN_TILE, Pc - c0);
+        __syncthreads();
+        if ((int)threadIdx.x < cnt) {
+            const float *p = C + 3 * (size_t)(c0 + threadIdx.x);
+            tile[threadIdx.x] = make_float4(p[0], p[1], p[2], 0.f);
+        }
+        __syncthreads();
+        for (int j0 = 0; j0 < cnt; j0 += WAVE) {
+            const int j = j0 + lane;  // (< KNN_TILE: the read stays inside the tile, entries past cnt are not used)
+            const float4 c = tile[j];
+#pragma unroll
+            for (int k = 0; k < KNN_QPW; ++k) {
+                const float dx = qx[k] - c.x, dy = qy[k] - c.y, dz = qz[k] - c.z;
+                const float dd = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+                const unsigned long long ck =
+                    j < cnt ? ((unsigned long long)__float_as_uint(dd) << 32) | (unsigned long long)(uint32_t)(c0 + j) : KNN_EMPTY;
+                unsigned long long m = __ballot(ck < thr[k]);
+                while (m) {
+                    const int l = __ffsll((long long)m) - 1;
+                    m &= m - 1;
+                    const unsigned long long nk = readlane64(ck, l);
+                    if (nk < thr[k]) {
+                        const unsigned long long up = __shfl_up(key[k], 1, WAVE);
+                        if (key[k] > nk) key[k] = (lane > 0 && up > nk) ? up : nk;
+                        thr[k] = readlane64(key[k], a.K - 1);
+                        ++ins;
+                    }
+                }
+            }
+        }
+    }
+    float kmax = 0.f;
+#pragma unroll
+    for (int k = 0; k < KNN_QPW; ++k) {
+        const int q = q0 + k;
+        if (q < Pq) {
+            if (lane < a.K) {
+                const size_t o = ((size_t)n * Pq + q) * a.K + lane;
+                a.dists[d][o] = __uint_as_float((uint32_t)(key[k] >> 32));
+                a.idx[d][o] = (int)(uint32_t)key[k];
+            }
+            kmax = fmaxf(kmax, __uint_as_float((uint32_t)(thr[k] >> 32)));  // (K <= Pc: the K-th entry is a candidate)
+        }
+    }
+    if (lane == 0) {  // (an integer maximum and an integer sum: neither depends on the order)
+        if (a.dmax) atomicMax(&a.dmax[n * 2 + d], __float_as_uint(kmax));
+        if (a.n_insert) atomicAdd(a.n_insert, (unsigned long long)ins);
+    }
+}
+
+static bool knn_sizes_ok(int N, int P1, int P2, int K, bool both) {
+    return N > 0 && P1 > 0 && P2 > 0 && K >= 1 && K <= SMIL_KNN_MAX_K && K <= P2 && (!both || K <= P1) && N <= 32767 &&
+           (size_t)std::max(P1, P2) * (size_t)K <= 0x7FFFFFFFu;
+}
+
+static size_t knn_layout(char *base, KnnArgs &a) {
+    Workspace w{base};
+    a.n_insert = w.take<unsigned long long>(1);
+    return w.used;
+}
+
+extern "C" size_t smil_knn_workspace_bytes(int32_t N, int32_t P1, int32_t P2, int32_t K) {
+    KnnArgs a;
+    return knn_sizes_ok(N, P1, P2, K, false) ? knn_layout(nullptr, a) : 0;
+}
+
+static int knn_launch(KnnArgs &a, hipStream_t stream) {
+    hipLaunchKernelGGL(k_knn, dim3(ceil_div(std::max(a.P[0], a.dirs == 2 ? a.P[1] : 1), KNN_QPB), 1, a.N * a.dirs), dim3(KNN_BLOCK), 0, stream,
+                       a);
+    SMIL_LAUNCH_CHECK();
+    return SMIL_OK;
+}
+
+extern "C" int smil_knn(const float *x, const float *y, int32_t N, int32_t P1, int32_t P2, int32_t K, float *dists_x, int32_t *idx_x,
+                        float *dists_y, int32_t *idx_y, void *workspace, void *stream_) {
+    SMIL_REQUIRE(x && y && dists_x && idx_x && workspace, "smil_knn: null argument");
+    SMIL_REQUIRE((dists_y == nullptr) == (idx_y == nullptr), "smil_knn: dists_y and idx_y are given together or not at all");
+    SMIL_REQUIRE(knn_sizes_ok(N, P1, P2, K, dists_y != nullptr),
+                 "smil_knn: bad sizes N=%d P1=%d P2=%d K=%d (1 <= K <= %d, K <= candidates, N <= 32767)", N, P1, P2, K, SMIL_KNN_MAX_K);
+    hipStream_t stream = (hipStream_t)stream_;
+    KnnArgs a;
+    knn_layout((char *)workspace, a);
+    a.pts[0] = x; a.pts[1] = y;
+    a.P[0] = P1; a.P[1] = P2;
+    a.N = N; a.dirs = dists_y ? 2 : 1; a.K = K;
+    a.dists[0] = dists_x; a.dists[1] = dists_y;
+    a.idx[0] = (int *)idx_x; a.idx[1] = (int *)idx_y;
+    a.dmax = nullptr;
+    SMIL_HIP(hipMemsetAsync(a.n_insert, 0, sizeof(unsigned long long), stream));
+    return knn_launch(a, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// the SDF-guided term (reference fitter_3d/utils.py:973-1261)
+// ---------------------------------------------------------------------------------------------
+#define SDF_INV_TEMPERATURE 10.0  // utils.py:1069: temperature 0.1
+#define SDF_STD_MIN 1e-8          // utils.py:1044
+
+struct SdfArgs {
+    ChamferArgs c;         // clouds, weights, fixed-point accumulators, gradients, partial sums; c.dist holds r_i, c.key is unused
+    KnnArgs knn;
+    const float *val[2];   // (N, P[s]) per-point values of side s
+    double *z;             // (N, P[0] + P[1]) their z-scores, side 0's first (ch_row)
+};
+
+// sums of blockDim.x = 256 doubles in a fixed order; the result in every thread
+__device__ __forceinline__ double block_sum_f64(double v, double *sm) {
+    __syncthreads();
+    sm[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
+        __syncthreads();
+    }
+    return sm[0];
+}
+
+// z = (s - mean) / max(std, 1e-8) per (mesh, side), std unbiased (torch's default): the mean first, then the squares of the
+// differences from it, both in float64, so a large common offset of the values costs nothing.
+__global__ void __launch_bounds__(256) k_sdf_stats(SdfArgs a) {
+    __shared__ double sm[256];
+    const int side = blockIdx.x & 1, n = blockIdx.x >> 1;
+    const int P = a.c.P[side];
+    const float *v = a.val[side] + (size_t)n * P;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < P; i += 256) s += (double)v[i];
+    const double mean = block_sum_f64(s, sm) / (double)P;
+    double ss = 0.0;
+    for (int i = threadIdx.x; i < P; i += 256) {
+        const double e = (double)v[i] - mean;
+        ss += e * e;
+    }
+    const double sd = fmax(sqrt(block_sum_f64(ss, sm) / (double)(P - 1)), SDF_STD_MIN);
+    double *z = a.z + ch_row(a.c, n, side);
+    for (int i = threadIdx.x; i < P; i += 256) z[i] = ((double)v[i] - mean) / sd;
+}
+
+__device__ __forceinline__ double wave_max_f64(double v) {
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, WAVE));
+    return v;
+}
+
+// wave = one query i of direction d, lane k = its k-th neighbour j: w_k = softmax_k(-|z_q[i] - z_c[j]| / 0.1), r_i = sum_k w_k d_k,
+// the owned gradient 2 w sum_k w_k (q - c_j), and -w_k (q - c_j) added to candidate j's fixed-point sums.
+__global__ void __launch_bounds__(256) k_sdf_term(SdfArgs a) {
+    const int d = blockIdx.z % a.c.dirs, n = blockIdx.z / a.c.dirs;
+    const int Pq = a.c.P[d], Pc = a.c.P[1 - d], K = a.knn.K;
+    const int q = (int)blockIdx.x * (256 / WAVE) + ((int)threadIdx.x >> 6);
+    if (q >= Pq) return;  // (wave-uniform)
+    const int lane = threadIdx.x & (WAVE - 1);
+    const bool on = lane < K;
+    const size_t row = ch_row(a.c, n, d) + q;
+    const size_t o = ((size_t)n * Pq + q) * K + lane;
+    int j = on ? a.knn.idx[d][o] : 0;
+    const float dd = on ? a.knn.dists[d][o] : 0.f;
+    j = min(max(j, 0), Pc - 1);
+    const double zd = fabs(a.z[row] - a.z[ch_row(a.c, n, 1 - d) + j]) * SDF_INV_TEMPERATURE;
+    const double lo = on ? -zd : -__builtin_inf();
+    const double top = wave_max_f64(lo);
+    const float e = on ? expf((float)(lo - top)) : 0.f;
+    const float w = e / wave_sum(e);
+    const float r = wave_sum(w * dd);
+    if (lane == 0) a.c.dist[row] = r;
+    if (!a.c.grad[0]) return;
+    const float *Qp = a.c.pts[d] + ((size_t)n * Pq + q) * 3;
+    const float *Cp = a.c.pts[1 - d] + ((size_t)n * Pc + j) * 3;
+    const float ex[3] = {Qp[0] - Cp[0], Qp[1] - Cp[1], Qp[2] - Cp[2]};
+    const float s = 2.0f * a.c.w[d];
+    const float g0 = wave_sum(w * ex[0]), g1 = wave_sum(w * ex[1]), g2 = wave_sum(w * ex[2]);
+    if (lane == 0) {
+        float *g = a.c.grad[d] + ((size_t)n * Pq + q) * 3;
+        g[0] = s * g0; g[1] = s * g1; g[2] = s * g2;
+    }
+    if (on) {  // (the product in float64 is exact: the integer added does not depend on the clouds' scale)
+        long long *acc = a.c.acc + (ch_row(a.c, n, 1 - d) + j) * 3;
+        const int fix = ch_fix_exp(a.c, n, d);
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            atomicAdd((unsigned long long *)&acc[k], (unsigned long long)__double2ll_rn(ldexp(-(double)w * (double)ex[k], fix)));
+    }
+}
+
+static bool sdf_sizes_ok(int N, int P1, int P2, int K, bool both) { return knn_sizes_ok(N, P1, P2, K, both) && P1 >= 2 && P2 >= 2; }
+
+static size_t sdf_layout(int N, int P1, int P2, int K, bool own_tables, char *base, SdfArgs &a) {
+    const size_t pts = (size_t)N * ((size_t)P1 + P2);
+    Workspace w{base};
+    a.knn.n_insert = w.take<unsigned long long>(1);
+    a.c.dmax = w.take<unsigned int>((size_t)N * 2);
+    a.c.part = w.take<float>((size_t)N * 2);
+    a.c.dist = w.take<float>(pts);
+    a.z = w.take<double>(pts);
+    a.c.acc = w.take<long long>(pts * 3);
+    if (own_tables) {
+        a.knn.dists[0] = w.take<float>((size_t)N * P1 * K);
+        a.knn.idx[0] = w.take<int>((size_t)N * P1 * K);
+        a.knn.dists[1] = w.take<float>((size_t)N * P2 * K);
+        a.knn.idx[1] = w.take<int>((size_t)N * P2 * K);
+    }
+    return w.used;
+}
+
+extern "C" size_t smil_sdf_distance_workspace_bytes(int32_t N, int32_t P1, int32_t P2, int32_t K) {
+    SdfArgs a;
+    return sdf_sizes_ok(N, P1, P2, K, false) ? sdf_layout(N, P1, P2, K, true, nullptr, a) : 0;
+}
+
+extern "C" int smil_sdf_distance(const float *x, const float *y, const float *x_sdf, const float *y_sdf, int32_t N, int32_t P1, int32_t P2,
+                                 int32_t K, int32_t single_directional, int32_t point_sum, int32_t batch_sum, float *loss, float *d_x,
+                                 float *d_y, float *dists_x, int32_t *idx_x, float *dists_y, int32_t *idx_y, void *workspace,
+                                 void *stream_) {
+    SMIL_REQUIRE(x && y && x_sdf && y_sdf && loss && workspace, "smil_sdf_distance: null argument");
+    SMIL_REQUIRE(sdf_sizes_ok(N, P1, P2, K, !single_directional),
+                 "smil_sdf_distance: bad sizes N=%d P1=%d P2=%d K=%d (1 <= K <= %d, K <= candidates, P >= 2, N <= 32767)", N, P1, P2, K,
+                 SMIL_KNN_MAX_K);
+    SMIL_REQUIRE((d_x == nullptr) == (d_y == nullptr), "smil_sdf_distance: d_x and d_y are given together or not at all");
+    SMIL_REQUIRE((dists_x == nullptr) == (idx_x == nullptr) && (dists_y == nullptr) == (idx_y == nullptr),
+                 "smil_sdf_distance: a neighbour table is its dists and its idx");
+    SMIL_REQUIRE(!(single_directional && dists_y), "smil_sdf_distance: dists_y has no meaning when single_directional");
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t pts = (size_t)N * ((size_t)P1 + P2);
+    SdfArgs a;
+    sdf_layout(N, P1, P2, K, true, (char *)workspace, a);
+    if (dists_x) { a.knn.dists[0] = dists_x; a.knn.idx[0] = (int *)idx_x; }
+    if (dists_y) { a.knn.dists[1] = dists_y; a.knn.idx[1] = (int *)idx_y; }
+    ChamferArgs &c = a.c;
+    c.pts[0] = x; c.pts[1] = y;
+    c.P[0] = P1; c.P[1] = P2;
+    c.N = N; c.dirs = single_directional ? 1 : 2; c.splits = 1; c.K = K;
+    const float bw = batch_sum ? 1.0f : 1.0f / (float)N;
+    c.w[0] = (point_sum ? 1.0f : 1.0f / (float)P1) * bw;
+    c.w[1] = (point_sum ? 1.0f : 1.0f / (float)P2) * bw;
+    c.key = nullptr;
+    c.idx[0] = c.idx[1] = nullptr;
+    c.grad[0] = d_x; c.grad[1] = d_y;
+    c.loss = loss;
+    a.knn.pts[0] = x; a.knn.pts[1] = y;
+    a.knn.P[0] = P1; a.knn.P[1] = P2;
+    a.knn.N = N; a.knn.dirs = c.dirs; a.knn.K = K;
+    a.knn.dmax = c.dmax;
+    a.val[0] = x_sdf; a.val[1] = y_sdf;
+    SMIL_HIP(hipMemsetAsync(a.knn.n_insert, 0, sizeof(unsigned long long), stream));
+    SMIL_HIP(hipMemsetAsync(c.dmax, 0, (size_t)N * 2 * sizeof(unsigned int), stream));
+    if (d_x) SMIL_HIP(hipMemsetAsync(c.acc, 0, pts * 3 * 8, stream));
+    hipLaunchKernelGGL(k_sdf_stats, dim3(N * 2), dim3(256), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    if (knn_launch(a.knn, stream) != SMIL_OK) return SMIL_E_DEVICE;
+    hipLaunchKernelGGL(k_sdf_term, dim3(ceil_div(std::max(P1, c.dirs == 2 ? P2 : 1), 256 / WAVE), 1, N * c.dirs), dim3(256), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    if (d_x) {
+        hipLaunchKernelGGL(k_chamfer_scatter, dim3(ceil_div(std::max(P1, P2), 256), 1, N * 2), dim3(256), 0, stream, c);
+        SMIL_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_chamfer_reduce, dim3(N * c.dirs), dim3(256), 0, stream, c);
+    SMIL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_chamfer_total, dim3(1), dim3(64), 0, stream, (const float *)c.part, N * c.dirs, loss);
+    SMIL_LAUNCH_CHECK();
+    return SMIL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// vertex sampling (reference fitter_3d/utils.py:1264-1394)
+// ---------------------------------------------------------------------------------------------
+#define SV_STREAM 1u  // third counter word: the surface sampler's draws use 0
+
+__global__ void __launch_bounds__(256) k_sample_vertices(const float *__restrict__ verts, const float *__restrict__ values,
+                                                         const int *__restrict__ vert_off, int S, uint32_t seed_lo, uint32_t seed_hi,
+                                                         float *__restrict__ out, float *__restrict__ out_val, int *__restrict__ out_idx) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    const int n = blockIdx.y;
+    if (s >= S) return;
+    const size_t o = (size_t)n * S + s;
+    const int v0 = vert_off[n], V = vert_off[n + 1] - v0;
+    if (V <= 0) {  // an empty mesh: zeros, as the reference leaves them
+        out[3 * o] = 0.f; out[3 * o + 1] = 0.f; out[3 * o + 2] = 0.f;
+        out_val[o] = 0.f;
+        out_idx[o] = -1;
+        return;
+    }
+    const uint4 r = philox4x32_10(make_uint4((uint32_t)s, (uint32_t)n, SV_STREAM, 0u), make_uint2(seed_lo, seed_hi));
+    const int i = (int)(((uint64_t)r.x * (uint64_t)(uint32_t)V) >> 32);  // [0, V)
+    const float *p = verts + 3 * (size_t)(v0 + i);
+    out[3 * o] = p[0]; out[3 * o + 1] = p[1]; out[3 * o + 2] = p[2];
+    out_val[o] = values[v0 + i];
+    out_idx[o] = i;
+}
+
+extern "C" int smil_sample_vertices(const float *verts, const float *values, const int32_t *vert_off, int32_t N, int32_t S, uint64_t seed,
+                                    float *out, float *out_values, int32_t *out_idx, void *stream_) {
+    SMIL_REQUIRE(verts && values && vert_off && out && out_values && out_idx, "smil_sample_vertices: null argument");
+    SMIL_REQUIRE(N > 0 && S > 0 && N <= 65535, "smil_sample_vertices: bad sizes N=%d S=%d (N <= 65535)", N, S);
+    hipStream_t stream = (hipStream_t)stream_;
+    hipLaunchKernelGGL(k_sample_vertices, dim3(ceil_div(S, 256), N), dim3(256), 0, stream, verts, values, (const int *)vert_off, S,
+                       (uint32_t)seed, (uint32_t)(seed >> 32), out, out_values, (int *)out_idx);
+    SMIL_LAUNCH_CHECK();
+    return SMIL_OK;
+}
+
+// The gradient of the sampled points back to the vertices: duplicates of a vertex are summed as int64 fixed point, with a unit
+// that follows the data like ch_fix_exp (the mesh's largest |component| and S addends), so the sum does not depend on the order.
+struct SvGradArgs {
+    const float *d_pts;    // (N, S, 3)
+    const int *idx;        // (N, S) vertex within its mesh, -1: none
+    const int *vert_off;   // (N + 1)
+    int N, S;
+    float *d_verts;        // (n_verts, 3)
+    long long *acc;        // (n_verts, 3)
+    unsigned int *gmax;    // (N) bits of the mesh's largest |component|
+};
+
+__device__ __forceinline__ int sv_fix_exp(const SvGradArgs &a, int n) {
+    int ex;
+    frexpf(fminf(__uint_as_float(a.gmax[n]), 3.0e38f), &ex);  // every |component| < 2^ex
+    return 61 - (32 - __clz(a.S)) - ex;
+}
+
+__global__ void __launch_bounds__(256) k_sv_max(SvGradArgs a) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x, n = blockIdx.y;
+    float m = 0.f;
+    if (s < a.S) {
+        const float *g = a.d_pts + ((size_t)n * a.S + s) * 3;
+        m = fmaxf(fabsf(g[0]), fmaxf(fabsf(g[1]), fabsf(g[2])));
+    }
+    m = wave_max(m);
+    if ((threadIdx.x & 63) == 0) atomicMax(&a.gmax[n], __float_as_uint(m));
+}
+
+__global__ void __launch_bounds__(256) k_sv_add(SvGradArgs a) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x, n = blockIdx.y;
+    if (s >= a.S) return;
+    const size_t o = (size_t)n * a.S + s;
+    const int v0 = a.vert_off[n], i = a.idx[o];
+    if (i < 0 || i >= a.vert_off[n + 1] - v0) return;
+    const int fix = sv_fix_exp(a, n);
+    long long *acc = a.acc + (size_t)(v0 + i) * 3;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        atomicAdd((unsigned long long *)&acc[k], (unsigned long long)__double2ll_rn(ldexp((double)a.d_pts[3 * o + k], fix)));
+}
+
+__global__ void __launch_bounds__(256) k_sv_out(SvGradArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, n = blockIdx.y;
+    const int v0 = a.vert_off[n];
+    if (i >= a.vert_off[n + 1] - v0) return;
+    const int fix = sv_fix_exp(a, n);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) a.d_verts[(size_t)(v0 + i) * 3 + k] = (float)ldexp((double)a.acc[(size_t)(v0 + i) * 3 + k], -fix);
+}
+
+static size_t sv_grad_layout(int n_verts, int N, char *base, SvGradArgs &a) {
+    Workspace w{base};
+    a.acc = w.take<long long>((size_t)n_verts * 3);
+    a.gmax = w.take<unsigned int>((size_t)N);
+    return w.used;
+}
+
+extern "C" size_t smil_sample_vertices_backward_workspace_bytes(int32_t n_verts, int32_t N) {
+    SvGradArgs a;
+    return (n_verts > 0 && N > 0) ? sv_grad_layout(n_verts, N, nullptr, a) : 0;
+}
+
+extern "C" int smil_sample_vertices_backward(const float *d_pts, const int32_t *idx, const int32_t *vert_off, int32_t n_verts, int32_t max_verts,
+                                             int32_t N, int32_t S, float *d_verts, void *workspace, void *stream_) {
+    SMIL_REQUIRE(d_pts && idx && vert_off && d_verts && workspace, "smil_sample_vertices_backward: null argument");
+    SMIL_REQUIRE(N > 0 && S > 0 && N <= 65535 && n_verts > 0 && max_verts > 0 && max_verts <= n_verts,
+                 "smil_sample_vertices_backward: bad sizes N=%d S=%d n_verts=%d max_verts=%d", N, S, n_verts, max_verts);
+    hipStream_t stream = (hipStream_t)stream_;
+    SvGradArgs a;
+    sv_grad_layout(n_verts, N, (char *)workspace, a);
+    a.d_pts = d_pts; a.idx = (const int *)idx; a.vert_off = (const int *)vert_off;
+    a.N = N; a.S = S; a.d_verts = d_verts;
+    SMIL_HIP(hipMemsetAsync(a.acc, 0, (size_t)n_verts * 3 * 8, stream));
+    SMIL_HIP(hipMemsetAsync(a.gmax, 0, (size_t)N * sizeof(unsigned int), stream));
+    SMIL_HIP(hipMemsetAsync(d_verts, 0, (size_t)n_verts * 3 * sizeof(float), stream));  // (vertices outside vert_off's ranges)
+    hipLaunchKernelGGL(k_sv_max, dim3(ceil_div(S, 256), N), dim3(256), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_sv_add, dim3(ceil_div(S, 256), N), dim3(256), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_sv_out, dim3(ceil_div(max_verts, 256), N), dim3(256), 0, stream, a);
     SMIL_LAUNCH_CHECK();
     return SMIL_OK;
 }

@@ -726,6 +726,84 @@ def chamfer(x: torch.Tensor, y: torch.Tensor, single_directional=False, point_su
     return loss, idx_x, idx_y, d_x, d_y
 
 
+def _check_knn_sizes(what: str, P1: int, P2: int, K: int, both: bool, min_points: int = 1) -> None:
+    if not 1 <= K <= _lib.KNN_MAX_K:
+        raise ValueError(f"{what}: K={K} outside 1 .. {_lib.KNN_MAX_K} (SMIL_KNN_MAX_K)")
+    if K > P2 or (both and K > P1):
+        raise ValueError(f"{what}: K={K} exceeds the number of candidate points (P1={P1}, P2={P2})")
+    if min(P1, P2) < min_points:
+        raise ValueError(f"{what}: every cloud needs at least {min_points} points (P1={P1}, P2={P2})")
+
+
+def _insertions(ws: torch.Tensor) -> torch.Tensor:
+    return ws[:8].view(torch.int64)
+
+
+def knn(x: torch.Tensor, y: torch.Tensor, K: int, both: bool = False):
+    """The K nearest points of y (N,P2,3) for every point of x (N,P1,3), ascending by (squared distance, index):
+    (dists_x (N,P1,K), idx_x (N,P1,K) int32, dists_y, idx_y (N,P2,K) or None, insertions (1,) int64 on the device)."""
+    N, P1, P2, K = int(x.shape[0]), int(x.shape[1]), int(y.shape[1]), int(K)
+    _check_knn_sizes("knn", P1, P2, K, both)
+    dev = x.device
+    lib = _lib.load()
+    ws = torch.empty(int(lib.smil_knn_workspace_bytes(N, P1, P2, K)), dtype=torch.uint8, device=dev)
+    dx = torch.empty(N, P1, K, device=dev, dtype=torch.float32)
+    ix = torch.empty(N, P1, K, device=dev, dtype=torch.int32)
+    dy = torch.empty(N, P2, K, device=dev, dtype=torch.float32) if both else None
+    iy = torch.empty(N, P2, K, device=dev, dtype=torch.int32) if both else None
+    _lib.check(lib.smil_knn(_ptr(x), _ptr(y), N, P1, P2, K, _ptr(dx), _ptr(ix), _ptr(dy), _ptr(iy), _ptr(ws), _stream()), "smil_knn")
+    return dx, ix, dy, iy, _insertions(ws)
+
+
+def sdf_distance(x: torch.Tensor, y: torch.Tensor, x_sdf: torch.Tensor, y_sdf: torch.Tensor, K: int, single_directional=False,
+                 point_sum=False, batch_sum=False, want_grad=True, want_tables=False):
+    """The SDF-guided term of x (N,P1,3), y (N,P2,3) with per-point values x_sdf (N,P1), y_sdf (N,P2): (loss (1,), d_x, d_y or
+    None, tables (dists_x, idx_x, dists_y, idx_y) or None, insertions (1,) int64 on the device)."""
+    N, P1, P2, K = int(x.shape[0]), int(x.shape[1]), int(y.shape[1]), int(K)
+    _check_knn_sizes("sdf_distance", P1, P2, K, not single_directional, min_points=2)
+    dev = x.device
+    lib = _lib.load()
+    ws = torch.empty(int(lib.smil_sdf_distance_workspace_bytes(N, P1, P2, K)), dtype=torch.uint8, device=dev)
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    d_x = torch.empty_like(x) if want_grad else None
+    d_y = torch.empty_like(y) if want_grad else None
+    tables = None
+    if want_tables:
+        tables = (torch.empty(N, P1, K, device=dev, dtype=torch.float32), torch.empty(N, P1, K, device=dev, dtype=torch.int32),
+                  None if single_directional else torch.empty(N, P2, K, device=dev, dtype=torch.float32),
+                  None if single_directional else torch.empty(N, P2, K, device=dev, dtype=torch.int32))
+    t = tables or (None,) * 4
+    _lib.check(lib.smil_sdf_distance(_ptr(x), _ptr(y), _ptr(x_sdf), _ptr(y_sdf), N, P1, P2, K, int(bool(single_directional)),
+                                     int(bool(point_sum)), int(bool(batch_sum)), _ptr(loss), _ptr(d_x), _ptr(d_y), _ptr(t[0]), _ptr(t[1]),
+                                     _ptr(t[2]), _ptr(t[3]), _ptr(ws), _stream()), "smil_sdf_distance")
+    return loss, d_x, d_y, tables, _insertions(ws)
+
+
+def sample_vertices(verts_packed: torch.Tensor, values_packed: torch.Tensor, vert_off: torch.Tensor, n_meshes: int, num_samples: int,
+                    seed: int):
+    """(points (N,S,3), values (N,S), vertex index within its mesh (N,S) int32) of S vertices drawn uniformly with replacement from each
+    of N packed meshes; vert_off (N+1) int32."""
+    dev = verts_packed.device
+    out = torch.empty(n_meshes, num_samples, 3, device=dev, dtype=torch.float32)
+    val = torch.empty(n_meshes, num_samples, device=dev, dtype=torch.float32)
+    idx = torch.empty(n_meshes, num_samples, device=dev, dtype=torch.int32)
+    _lib.check(_lib.load().smil_sample_vertices(_ptr(verts_packed), _ptr(values_packed), _ptr(vert_off), int(n_meshes), int(num_samples),
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out), _ptr(val), _ptr(idx), _stream()),
+               "smil_sample_vertices")
+    return out, val, idx
+
+
+def sample_vertices_backward(d_pts: torch.Tensor, idx: torch.Tensor, vert_off: torch.Tensor, n_verts: int, max_verts: int):
+    """d_verts (n_verts,3): d_pts (N,S,3) summed over the samples that drew each vertex (order-independent)."""
+    N, S = int(idx.shape[0]), int(idx.shape[1])
+    lib = _lib.load()
+    ws = torch.empty(int(lib.smil_sample_vertices_backward_workspace_bytes(int(n_verts), N)), dtype=torch.uint8, device=d_pts.device)
+    d_verts = torch.empty(int(n_verts), 3, device=d_pts.device, dtype=torch.float32)
+    _lib.check(lib.smil_sample_vertices_backward(_ptr(d_pts), _ptr(idx), _ptr(vert_off), int(n_verts), int(max_verts), N, S, _ptr(d_verts),
+                                                 _ptr(ws), _stream()), "smil_sample_vertices_backward")
+    return d_verts
+
+
 class DeviceTopology:
     """The regulariser tables of one face array (``mesh3d.Topology``) resident on one GPU (``SmilMeshTopology``)."""
 

@@ -4,6 +4,7 @@
 
     from smilify_amd.fit3d import sample_points_from_meshes, chamfer_distance, mesh_edge_loss, \\
         mesh_laplacian_smoothing, mesh_normal_consistency
+    from smilify_amd.fit3d import SDF_distance, sample_points_from_meshes_and_SDF  # fitter_3d.utils
     from smilify_amd.mesh3d import Meshes
 
 and this module carries its ``SMAL3DFitter`` / ``SMALParamGroup`` / ``Stage`` / ``StageManager`` as well, with the SMAL half on the
@@ -12,15 +13,20 @@ computes the loss and its gradient in one launch sequence; backward scales that 
 
 Deviations: sampling draws from a Philox counter-based generator keyed by a 64-bit seed taken from torch's
 default CPU generator, so ``torch.manual_seed`` makes runs reproducible but the points differ from pytorch3d's (torch.multinomial /
-torch.rand streams).  Out of scope and raising: the SDF term, loss / mesh plots, normals / lengths / norm=1 in chamfer_distance,
-the cot / cotcurv Laplacians.
+torch.rand / torch.randint streams).  The SDF term (``SDF_distance``, ``knn_points``, ``sample_points_from_meshes_and_SDF``)
+orders neighbours by (squared distance, index) and supports 1 <= K <= 64, K <= the number of candidates and clouds of at least two
+points.  Out of scope and raising: computing the per-vertex diameter values (they are an input, as in the reference), the SDF heat
+maps, loss / mesh plots, normals / lengths / norm=1 in chamfer_distance, knn_points and SDF_distance, the cot / cotcurv Laplacians.
 
-Run as ``python -m smilify_amd.fit3d --model MODEL.npz --mesh_dir DIR [--yaml_src CFG.yaml]`` (fitter_3d/optimise.py).
+Run as ``python -m smilify_amd.fit3d --model MODEL.npz --mesh_dir DIR [--yaml_src CFG.yaml] [--use_sdf --sdf_dir DIR]``
+(fitter_3d/optimise.py).
 """
 from __future__ import annotations
 
 import argparse
 import os
+import pickle
+from collections import namedtuple
 from math import ceil
 from typing import Optional
 
@@ -96,6 +102,155 @@ def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_nor
         raise ValueError("chamfer_distance: x (N,P1,3) and y (N,P2,3) tensors")
     loss = _ChamferFn.apply(x, y, bool(single_directional), point_reduction == "sum", batch_reduction == "sum")
     return loss, None
+
+
+# ---- the SDF-guided term (fitter_3d/utils.py:973-1394) --------------------------------------------------------------------------
+_KNN = namedtuple("KNN", "dists idx knn")
+
+
+def _check_clouds(what: str, x, y) -> None:
+    if not (isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor) and x.dim() == 3 and y.dim() == 3 and x.shape[2] == 3
+            and y.shape[2] == 3 and x.shape[0] == y.shape[0]):
+        raise ValueError(f"{what}: x (N,P1,3) and y (N,P2,3) tensors")
+
+
+class _KnnFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p1, p2, K):
+        a, b = _gpu_f32(p1), _gpu_f32(p2)
+        dists, idx, _, _, _ = engine.knn(a, b, K)
+        idx = idx.long()
+        ctx.save_for_backward(a, b, idx)
+        ctx.mark_non_differentiable(idx)
+        return dists, idx
+
+    @staticmethod
+    def backward(ctx, g, _):
+        # d dists[n,i,k] = 2 (p1_i - p2_j): gathered for p1, summed per candidate in float64 for p2 (not on the Stage's path, which
+        # takes the fused term's gradient from the kernel)
+        a, b, idx = ctx.saved_tensors
+        N, P1, K = idx.shape
+        flat = idx.reshape(N, P1 * K, 1).expand(-1, -1, 3)
+        e = (a[:, :, None, :] - torch.gather(b, 1, flat).reshape(N, P1, K, 3)).double() * (2.0 * g.double())[..., None]
+        d2 = torch.zeros(b.shape, dtype=torch.float64, device=b.device).scatter_add_(1, flat, -e.reshape(N, P1 * K, 3))
+        return e.sum(2).float(), d2.float(), None
+
+
+def knn_points(p1, p2, lengths1=None, lengths2=None, norm: int = 2, K: int = 1, version: int = -1, return_nn: bool = False,
+               return_sorted: bool = True):
+    """pytorch3d.ops.knn_points for (N,P1,3) / (N,P2,3) tensors without lengths: (dists (N,P1,K) squared, idx (N,P1,K) int64, knn
+    None), every row ascending by (distance, index)."""
+    if lengths1 is not None or lengths2 is not None:
+        raise NotImplementedError("knn_points: lengths are not supported")
+    if norm != 2:
+        raise NotImplementedError("knn_points: only norm=2")
+    if return_nn:
+        raise NotImplementedError("knn_points: return_nn is not supported (gather p2 at idx)")
+    _check_clouds("knn_points", p1, p2)
+    dists, idx = _KnnFn.apply(p1, p2, int(K))
+    return _KNN(dists, idx, None)
+
+
+class _SdfFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, x_sdf, y_sdf, K, single_directional, point_sum, batch_sum):
+        want = x.requires_grad or y.requires_grad
+        loss, dx, dy, _, _ = engine.sdf_distance(_gpu_f32(x), _gpu_f32(y), _gpu_f32(x_sdf), _gpu_f32(y_sdf), K, single_directional,
+                                                 point_sum, batch_sum, want_grad=want)
+        ctx.save_for_backward(dx, dy) if want else ctx.save_for_backward()
+        ctx.want = want
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.want:
+            return (None,) * 8
+        dx, dy = ctx.saved_tensors
+        return (dx * g, dy * g) + (None,) * 6
+
+
+def SDF_distance(x, y, x_sdf, y_sdf, k: int, batch_reduction="mean", point_reduction="mean", norm: int = 2,
+                 single_directional: bool = False, visualize: bool = False, output_dir: str = "sdf_visualization",
+                 title: str = "sdf_loss_contribution", mesh_names=None):
+    """fitter_3d.utils.SDF_distance: with the per-cloud z-scores of the values and the k nearest candidates (d_ik, j_ik) of every
+    query, sum_k softmax_k(-|z_q[i] - z_c[j_ik]| / 0.1) d_ik, reduced over points and meshes, both directions added.  The values
+    carry no gradient (the reference's do, but they are data in its Stage)."""
+    if norm not in (1, 2):
+        raise ValueError("Support for 1 or 2 norm.")
+    if norm != 2:
+        raise NotImplementedError("SDF_distance: only norm=2")
+    if visualize:
+        raise NotImplementedError("SDF_distance: the heat-map visualisation is not supported")
+    if point_reduction not in ("mean", "sum") or batch_reduction not in ("mean", "sum"):
+        raise NotImplementedError("SDF_distance: point_reduction / batch_reduction must be 'mean' or 'sum'")
+    _check_clouds("SDF_distance", x, y)
+    if not (isinstance(x_sdf, torch.Tensor) and isinstance(y_sdf, torch.Tensor) and x_sdf.shape == x.shape[:2]
+            and y_sdf.shape == y.shape[:2]):
+        raise ValueError("SDF_distance: x_sdf (N,P1) and y_sdf (N,P2) must match the clouds")
+    if k < 1:
+        raise ValueError("k must be at least 1")
+    return _SdfFn.apply(x, y, x_sdf, y_sdf, int(k), bool(single_directional), point_reduction == "sum", batch_reduction == "sum")
+
+
+def _pack_sdf_values(meshes: Meshes, sdf_values):
+    """The three forms of ``sdf_values`` (a (V,) tensor shared by all meshes, an (N,V) tensor, a list of N (V_n,) tensors) as one
+    packed float32 tensor on the meshes' device, with the meshes' vertex offsets: (values, vert_off int32, n_verts, max_verts)."""
+    nv = meshes.num_verts_per_mesh()
+    N, dev = len(meshes), meshes.device
+    if isinstance(sdf_values, (list, tuple)):
+        if len(sdf_values) != N:
+            raise ValueError(f"Number of SDF value tensors ({len(sdf_values)}) must match number of meshes ({N})")
+        rows = [torch.as_tensor(v).reshape(-1) for v in sdf_values]
+    elif isinstance(sdf_values, torch.Tensor):
+        if sdf_values.dim() == 1:
+            if any(n != nv[0] for n in nv):
+                raise ValueError("When providing a single 1D tensor of SDF values, all meshes must have the same number of vertices")
+            rows = [sdf_values] * N
+        elif sdf_values.dim() == 2 and sdf_values.shape[0] == N:
+            rows = list(sdf_values.unbind(0))
+        else:
+            raise ValueError(f"sdf_values of shape {tuple(sdf_values.shape)} for {N} meshes: expected (V,) or ({N}, V)")
+    else:
+        raise TypeError("sdf_values must be either a list of tensors or a single tensor")
+    for n, (r, v) in enumerate(zip(rows, nv)):
+        if int(r.shape[0]) != v:
+            raise ValueError(f"Number of SDF values ({int(r.shape[0])}) must match number of vertices ({v}) of mesh {n}")
+    values = torch.cat([r.detach().to(device=dev, dtype=torch.float32) for r in rows]).contiguous()
+    off = torch.from_numpy(np.concatenate([[0], np.cumsum(nv)]).astype(np.int32)).to(dev)
+    return values, off, int(sum(nv)), int(max(nv))
+
+
+class _SampleVertsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, verts_packed, packed, N, S, seed):
+        values, off, n_verts, max_verts = packed
+        pts, val, idx = engine.sample_vertices(_gpu_f32(verts_packed), values, off, N, S, seed)
+        ctx.save_for_backward(idx, off)
+        ctx.sizes = (n_verts, max_verts)
+        ctx.mark_non_differentiable(val, idx)
+        return pts, val, idx
+
+    @staticmethod
+    def backward(ctx, g, _v, _i):
+        idx, off = ctx.saved_tensors
+        return engine.sample_vertices_backward(g.to(torch.float32).contiguous(), idx, off, *ctx.sizes), None, None, None, None
+
+
+def sample_vertices_with_index(meshes: Meshes, sdf_values, num_samples: int, seed: Optional[int] = None, _packed=None):
+    """(points (N,S,3) with gradient to the vertices, values (N,S), vertex index within its mesh (N,S) int32).  ``seed`` None: a
+    63-bit value from torch's default generator."""
+    if seed is None:
+        seed = int(torch.empty((), dtype=torch.int64).random_().item())
+    packed = _packed if _packed is not None else _pack_sdf_values(meshes, sdf_values)
+    engine.require_gpu(meshes.device)
+    return _SampleVertsFn.apply(meshes.verts_packed(), packed, len(meshes), int(num_samples), int(seed))
+
+
+def sample_points_from_meshes_and_SDF(meshes: Meshes, sdf_values, num_samples: int = 10000):
+    """fitter_3d.utils.sample_points_from_meshes_and_SDF: ``num_samples`` vertices of every mesh, uniform with replacement, and their
+    values: (samples (N,S,3), sdf_samples (N,S)).  Values whose length is not the mesh's vertex count raise ValueError."""
+    pts, val, _ = sample_vertices_with_index(meshes, sdf_values, num_samples)
+    return pts, val
 
 
 class _RegFn(torch.autograd.Function):
@@ -226,7 +381,7 @@ class SMALParamGroup:
 
 class Stage:
     """trainer.py:294-509: one optimisation stage (Adam over a scheme's parameters, chamfer to 3000 fresh target samples per
-    iteration plus the mesh regularisers)."""
+    iteration plus the mesh regularisers, and the SDF-guided term when ``w_sdf`` > 0 and both value sets are given)."""
 
     def __init__(self, nits: int, scheme: str, smal_3d_fitter: SMAL3DFitter, target_meshes: Meshes, mesh_names=(), name="optimise",
                  loss_weights=None, lr=1e-3, out_dir="static_fits_output", custom_lrs=None, device="cuda", plot_normals=False,
@@ -243,11 +398,10 @@ class Stage:
         if loss_weights is not None:
             self.loss_weights.update(loss_weights)
         self.sample_size = sample_size
-        if (sdf_values is not None or source_sdf_values is not None) and self.loss_weights["w_sdf"] > 0:
-            raise NotImplementedError("the SDF term (w_sdf with sdf_values) is not supported on the HIP path")
         if visualize_sdf_loss:
             raise NotImplementedError("SDF loss visualisation is not supported")
-        self.sdf_values = self.source_sdf_values = None
+        self.sdf_values, self.source_sdf_values = sdf_values, source_sdf_values
+        self.sdf_vis_frequency = sdf_vis_frequency
         self.losses_to_plot = []
         if custom_lrs is not None:
             for attr in custom_lrs:
@@ -261,6 +415,10 @@ class Stage:
         self.n_verts = self.src_verts.shape[1]
         self.last_target_samples = None
         self.consider_loss = lambda loss_name: self.loss_weights[f"w_{loss_name}"] > 0
+        # the values, packed once for the sampler (the vertex counts are fixed for the stage): a wrong length raises here
+        self._sdf_packed = None
+        if sdf_values is not None and source_sdf_values is not None:
+            self._sdf_packed = (_pack_sdf_values(self.src_mesh, source_sdf_values), _pack_sdf_values(target_meshes, sdf_values))
 
     def forward(self, src_mesh: Meshes, iteration=0):
         loss = 0
@@ -277,6 +435,12 @@ class Stage:
                 if on:
                     comps[k] = r
                     loss = loss + self.loss_weights[f"w_{k}"] * r
+        if self.consider_loss("sdf") and self._sdf_packed is not None:  # trainer.py:399-433: 10000 vertices a side, K = 50
+            src_pts, src_sdf, _ = sample_vertices_with_index(src_mesh, None, 10000, _packed=self._sdf_packed[0])
+            tgt_pts, tgt_sdf, _ = sample_vertices_with_index(self.target_meshes, None, 10000, _packed=self._sdf_packed[1])
+            comps["sdf"] = SDF_distance(src_pts, tgt_pts, src_sdf, tgt_sdf, k=50, batch_reduction="mean", point_reduction="mean",
+                                        norm=2, single_directional=False)
+            loss = loss + self.loss_weights["w_sdf"] * comps["sdf"]
         return loss, comps
 
     def step(self, epoch):
@@ -361,6 +525,34 @@ def combine_stage_results(results_dir, stage_names, n_batches):
                     os.remove(path)
 
 
+def load_sdf_values(mesh_name: str, sdf_dir: str, device) -> Optional[torch.Tensor]:
+    """The per-vertex values of one mesh: ``NAME_sdf.npz`` (array ``vertex_sdf``), else ``NAME_sdf.pkl`` (a dict with a
+    ``vertex_sdf`` tensor, optimise.py:113-142); the name is tried as given and without a 4-character extension.  None: no file."""
+    for name in (mesh_name, mesh_name[:-4]):
+        npz, pkl = os.path.join(sdf_dir, f"{name}_sdf.npz"), os.path.join(sdf_dir, f"{name}_sdf.pkl")
+        if os.path.exists(npz):
+            with np.load(npz) as d:
+                return torch.from_numpy(np.asarray(d["vertex_sdf"], np.float32).reshape(-1)).to(device)
+        if os.path.exists(pkl):
+            with open(pkl, "rb") as fh:
+                data = pickle.load(fh)
+            if "vertex_sdf" not in data:
+                raise KeyError(f"vertex_sdf not found in {pkl}")
+            return torch.as_tensor(data["vertex_sdf"], dtype=torch.float32).reshape(-1).to(device)
+    return None
+
+
+def check_and_load_sdf_values(mesh_names, sdf_dir: str, device):
+    """optimise.py:145-171: the values of every mesh (None where there is no file), with the reference's warning."""
+    out = [load_sdf_values(n, sdf_dir, device) for n in mesh_names]
+    missing = [n for n, v in zip(mesh_names, out) if v is None]
+    if missing:
+        print(f"\nWarning: SDF values not found for {len(missing)} meshes:")
+        for n in missing:
+            print(f"  - {n}")
+    return out
+
+
 def get_mesh_files(mesh_dir, frame_step=1):
     return sorted(os.path.join(mesh_dir, f) for f in os.listdir(mesh_dir) if f.endswith(".obj"))[::frame_step]
 
@@ -379,6 +571,9 @@ def build_parser():
     p.add_argument("--batch_size", type=int, default=None,
                    help="SPLIT_TARGET_MESHES_INTO_BATCHES_OF_SIZE (reference config.py:24); <= 0: one batch")
     p.add_argument("--device", type=str, default="cuda")
+    p.add_argument("--use_sdf", action="store_true", help="add the SDF-guided term (needs --sdf_dir)")
+    p.add_argument("--sdf_dir", type=str, default=None,
+                   help="directory of NAME_sdf.npz / NAME_sdf.pkl files (vertex_sdf) for the source model and the target meshes")
     return p
 
 
@@ -394,6 +589,16 @@ def main(args):
             setattr(args, k, v)
     if args.model is None and (_config.current is None or _config.current.SMAL_FILE is None):
         raise ValueError("--model is required when smilify_amd.config.current names no SMAL_FILE")
+    source_sdf_values = None
+    if getattr(args, "use_sdf", False):  # optimise.py:202-228: the source model's file is required
+        if not args.sdf_dir:
+            raise ValueError("--use_sdf needs --sdf_dir")
+        model_file = args.model if args.model is not None else _config.current.SMAL_FILE
+        source_name = os.path.splitext(os.path.basename(model_file))[0]
+        source_sdf_values = load_sdf_values(source_name, args.sdf_dir, args.device)
+        if source_sdf_values is None:
+            raise FileNotFoundError(f"SDF file for source model not found at {os.path.join(args.sdf_dir, source_name + '_sdf.npz')} "
+                                    "(or .pkl). Compute the values of the source model first.")
     mesh_files = get_mesh_files(args.mesh_dir, args.frame_step)
     if not mesh_files:
         raise FileNotFoundError(f"no .obj files in {args.mesh_dir}")
@@ -411,6 +616,10 @@ def main(args):
         manager = StageManager(out_dir=args.results_dir, labels=names)
         model = SMAL3DFitter(batch_size=len(targets), device=args.device, shape_family=args.shape_family_id, model_path=args.model)
         kw = dict(target_meshes=targets, smal_3d_fitter=model, out_dir=args.results_dir, device=args.device, mesh_names=names)
+        if source_sdf_values is not None:
+            tv = check_and_load_sdf_values(names, args.sdf_dir, args.device)
+            if all(v is not None for v in tv):  # (the reference hands over the list as it is and fails on a None inside)
+                kw.update(sdf_values=tv, source_sdf_values=source_sdf_values)
         if stage_options is not None:
             for stage_name, skw in stage_options.items():
                 manager.add_stage(Stage(name=f"{stage_name}_batch_{b}" if n_batches > 1 else stage_name, **skw, **kw))

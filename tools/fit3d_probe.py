@@ -2,6 +2,11 @@
 fp32 VALU floor, and the same losses composed from plain torch ops at equal inputs.  Prints one JSON line and writes it to
 ``--out`` (default profiles/fit3d_probe.json).
 
+With ``--sdf`` it measures the SDF-guided term instead (10 000 vertex samples a side, K = 50) and writes
+profiles/fit3d_sdf_probe.json: the ``sdf_distance`` call with gradients, Stage.step with the term on and off, the same term from
+plain torch ops (cdist + topk + gathers + softmax under autograd, in chunks of at most 8 meshes to bound its (n, 10 000, 10 000)
+matrices), the VALU floor of the two searches and the measured list insertions per query.
+
 Setup: the STICK and mouse models as sources, the Atta worker scan (tests/golden/atta_worker_mesh.npz) as every target, each copy
 under its own random rigid motion, B in {1, 16, 64}.  Device events after a warm-up.
 """
@@ -70,14 +75,83 @@ def torch_losses(x, verts, topo, faces):
     return ch + edge + 0.01 * normal + 0.1 * lap
 
 
+SDF_SAMPLES, SDF_K, TORCH_CHUNK = 10000, 50, 8
+
+
+def torch_sdf(x, y, xs, ys, K):
+    """The term from plain torch ops: the yardstick."""
+    def z(s):
+        return (s - s.mean(1, keepdim=True)) / s.std(1, keepdim=True).clamp(min=1e-8)
+
+    def one(q, c, zq, zc):
+        d, i = (torch.cdist(q, c) ** 2).topk(K, dim=2, largest=False)
+        w = torch.softmax(-(zq[:, :, None] - torch.gather(zc, 1, i.reshape(i.shape[0], -1)).reshape(i.shape)).abs() / 0.1, dim=-1)
+        return (w * d).sum(-1).mean(1).sum()
+
+    zx, zy = z(xs), z(ys)
+    return (one(x, y, zx, zy) + one(y, x, zy, zx)) / x.shape[0]
+
+
+def sdf_rows(args, dev):
+    rows = []
+    for key, path in MODELS.items():
+        for B in [int(b) for b in args.batches.split(",")]:
+            tgt = targets(B, dev)
+            model = fit3d.SMAL3DFitter(batch_size=B, device=dev, model_path=os.path.join(REPO, path))
+            with torch.no_grad():
+                src = model()[0]
+            src_val = (src - src.mean(0)).norm(dim=1)
+            tv = tgt.verts_list()[0]
+            tgt_val = (tv - tv.mean(0)).norm(dim=1)
+            step_ms = {}
+            for name, kw in (("off", {}), ("on", dict(sdf_values=tgt_val, source_sdf_values=src_val))):
+                stage = fit3d.Stage(args.iters, "all", model, tgt, lr=1e-4, **kw)
+                for _ in range(3):
+                    stage.optimizer.zero_grad()
+                    stage.step(0)
+                step_ms[name] = timed(lambda: (stage.optimizer.zero_grad(), stage.step(0)), args.iters)
+            with torch.no_grad():
+                x, xs, _ = fit3d.sample_vertices_with_index(stage.src_mesh, src_val, SDF_SAMPLES, seed=1)
+                y, ys, _ = fit3d.sample_vertices_with_index(tgt, tgt_val, SDF_SAMPLES, seed=2)
+            call = lambda: engine.sdf_distance(x, y, xs, ys, SDF_K)  # noqa: E731
+            for _ in range(3):
+                ins = call()[4]
+            call_ms = timed(call, args.iters)
+            pairs = 2.0 * B * SDF_SAMPLES * SDF_SAMPLES
+            floor_ms = pairs * FLOPS_PER_PAIR / VALU_FP32_FLOPS * 1e3
+
+            def torch_fn():
+                for b0 in range(0, B, TORCH_CHUNK):
+                    xa = x[b0:b0 + TORCH_CHUNK].clone().requires_grad_(True)
+                    ya = y[b0:b0 + TORCH_CHUNK].clone().requires_grad_(True)
+                    torch.autograd.grad(torch_sdf(xa, ya, xs[b0:b0 + TORCH_CHUNK], ys[b0:b0 + TORCH_CHUNK], SDF_K), (xa, ya))
+
+            torch_fn()
+            torch_ms = timed(torch_fn, 3)
+            rows.append(dict(model=key, B=B, V=int(src.shape[0]), samples=SDF_SAMPLES, K=SDF_K, sdf_call_ms=call_ms, sdf_torch_ms=torch_ms,
+                             stage_step_sdf_on_ms=step_ms["on"], stage_step_sdf_off_ms=step_ms["off"], search_pairs=pairs,
+                             search_valu_floor_ms=floor_ms, search_floor_over_call=floor_ms / call_ms,
+                             insertions_per_query=float(ins.item()) / (2.0 * B * SDF_SAMPLES)))
+            print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--sdf", action="store_true", help="measure the SDF-guided term (profiles/fit3d_sdf_probe.json)")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--batches", type=str, default="1,16,64")
     ap.add_argument("--out", type=str, default=os.path.join(REPO, "profiles", "fit3d_probe.json"))
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
+    if args.sdf:
+        out = args.out if args.out != ap.get_default("out") else os.path.join(REPO, "profiles", "fit3d_sdf_probe.json")
+        res = dict(device=torch.cuda.get_device_name(0), iters=args.iters, torch_chunk_meshes=TORCH_CHUNK, rows=sdf_rows(args, dev))
+        with open(out, "w") as fh:
+            json.dump(res, fh, indent=1)
+        print(json.dumps(res))
+        return
     rows = []
     for key, path in MODELS.items():
         for B in [int(b) for b in args.batches.split(",")]:
