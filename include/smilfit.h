@@ -483,6 +483,24 @@ size_t smil_sample_vertices_backward_workspace_bytes(int32_t n_verts, int32_t N)
 int smil_sample_vertices_backward(const float *d_pts, const int32_t *idx, const int32_t *vert_off, int32_t n_verts, int32_t max_verts,
                                   int32_t N, int32_t S, float *d_verts, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The per-sample "spatial diameter" values that the SDF-guided term takes as input, by brute-force ray casting
+ * (smilify_amd/csrc/raycast.hip).  Replaces compute_ray_mesh_intersections_vectorized (reference fitter_3d/SDF_tests.py:112-222) and
+ * the ray / sample loops of compute_sdf (:344-382).  Deterministic: two calls on the same inputs give the same bits.
+ * ---------------------------------------------------------------------------------------- */
+/* S samples with R rays each against all F faces of one mesh: verts (V,3), faces (F,3), origins (S,3), own_face (S) the face a
+ * sample lies on (never hit by its rays; -1: none), dirs (S,R,3) used as given (not normalised).  With e1 = v1 - v0, e2 = v2 - v0,
+ * h = d x e2, a = e1 . h, f = 1 / a, s = o - v0, u = f (s . h), q = s x e1, v = f (d . q), t = f (e2 . q), face j is hit when
+ * j != own_face, |a| > 1e-6, 0 <= u <= 1, v >= 0, u + v <= 1 and t > t_min, all in float32.  A ray's value is the LARGEST t over its
+ * hits (the winning face's t, evaluated once more in float64 and rounded): ray_t (S,R), -1 where nothing is hit, or NULL.  diam (S):
+ * the rays are walked in order, a ray is valid when it has a hit with d_lo < t < d_hi, the walk ends once `cap` (>= 1) valid rays
+ * are taken; the mean of those as float32 (summed in float64), or d_lo when there are none.
+ * t_min >= 0.  A face with a vertex index outside [0, V) is never hit.  workspace: smil_ray_diameters_workspace_bytes. */
+size_t smil_ray_diameters_workspace_bytes(int32_t F, int32_t S, int32_t R);
+int smil_ray_diameters(const float *verts, int32_t V, const int32_t *faces, int32_t F, const float *origins, const int32_t *own_face,
+                       const float *dirs, int32_t S, int32_t R, float t_min, float d_lo, float d_hi, int32_t cap, float *ray_t,
+                       float *diam, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@ EXPORTS = [
     "smil_sample_points", "smil_chamfer_workspace_bytes", "smil_chamfer", "smil_mesh_reg_workspace_bytes", "smil_mesh_regularisers",
     "smil_knn_workspace_bytes", "smil_knn", "smil_sdf_distance_workspace_bytes", "smil_sdf_distance", "smil_sample_vertices",
     "smil_sample_vertices_backward_workspace_bytes", "smil_sample_vertices_backward",
+    "smil_ray_diameters_workspace_bytes", "smil_ray_diameters",
 ]
 
 N_OBJS = 10
@@ -178,6 +179,10 @@ def load():
     lib.smil_sample_vertices_backward_workspace_bytes.restype = c_size_t
     lib.smil_sample_vertices_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                                   c_void_p]
+    lib.smil_ray_diameters_workspace_bytes.argtypes = [c_int32] * 3
+    lib.smil_ray_diameters_workspace_bytes.restype = c_size_t
+    lib.smil_ray_diameters.argtypes = [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_float,
+                                       c_float, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.smil_profile_enable.argtypes = [c_int32]
     lib.smil_profile_read.argtypes = [POINTER(c_float), POINTER(c_int32)]
     for name in EXPORTS:

@@ -831,3 +831,28 @@ def mesh_regularisers(topo: DeviceTopology, verts: torch.Tensor, terms: int, wan
     _lib.check(lib.smil_mesh_regularisers(ctypes.byref(topo.struct), _ptr(verts), B, int(terms), _ptr(out), _ptr(g[0]), _ptr(g[1]),
                                           _ptr(g[2]), _ptr(ws), _stream()), "smil_mesh_regularisers")
     return out, g[0], g[1], g[2]
+
+
+# ---- spatial-diameter values by ray casting (raycast.hip) -------------------------------------------------------------------------
+def ray_diameters(verts: torch.Tensor, faces: torch.Tensor, origins: torch.Tensor, own_face: torch.Tensor, dirs: torch.Tensor, t_min: float,
+                  d_lo: float, d_hi: float, cap: int, want_ray_t: bool = False):
+    """S samples with R rays each against every face of one mesh: verts (V,3) float32, faces (F,3) int32, origins (S,3), own_face (S)
+    int32, dirs (S,R,3).  (diam (S), ray_t (S,R) or None): a ray's value is the largest t over its hits (-1: none), a sample's the
+    mean of its first ``cap`` rays with d_lo < t < d_hi in ray order, or d_lo (smil_ray_diameters, include/smilfit.h)."""
+    V, F, S, R = int(verts.shape[0]), int(faces.shape[0]), int(dirs.shape[0]), int(dirs.shape[1])
+    if verts.dtype != torch.float32 or origins.dtype != torch.float32 or dirs.dtype != torch.float32:
+        raise ValueError("ray_diameters: verts, origins and dirs must be float32")
+    if faces.dtype != torch.int32 or own_face.dtype != torch.int32:
+        raise ValueError("ray_diameters: faces and own_face must be int32")
+    if tuple(verts.shape) != (V, 3) or tuple(faces.shape) != (F, 3) or tuple(origins.shape) != (S, 3) or tuple(own_face.shape) != (S,) \
+            or tuple(dirs.shape) != (S, R, 3):
+        raise ValueError("ray_diameters: verts (V,3), faces (F,3), origins (S,3), own_face (S), dirs (S,R,3)")
+    dev = verts.device
+    verts, faces, origins, own_face, dirs = (t.contiguous() for t in (verts, faces, origins, own_face, dirs))
+    lib = _lib.load()
+    ws = torch.empty(int(lib.smil_ray_diameters_workspace_bytes(F, S, R)), dtype=torch.uint8, device=dev)
+    diam = torch.empty(S, device=dev, dtype=torch.float32)
+    ray_t = torch.empty(S, R, device=dev, dtype=torch.float32) if want_ray_t else None
+    _lib.check(lib.smil_ray_diameters(_ptr(verts), V, _ptr(faces), F, _ptr(origins), _ptr(own_face), _ptr(dirs), S, R, float(t_min), float(d_lo),
+                                      float(d_hi), int(cap), _ptr(ray_t), _ptr(diam), _ptr(ws), _stream()), "smil_ray_diameters")
+    return diam, ray_t

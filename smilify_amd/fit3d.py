@@ -15,7 +15,7 @@ Deviations: sampling draws from a Philox counter-based g
 default CPU generator, so ``torch.manual_seed`` makes runs reproducible but the points differ from pytorch3d's (torch.multinomial /
 torch.rand / torch.randint streams).  The SDF term (``SDF_distance``, ``knn_points``, ``sample_points_from_meshes_and_SDF``)
 orders neighbours by (squared distance, index) and supports 1 <= K <= 64, K <= the number of candidates and clouds of at least two
-points.  Out of scope and raising: computing the per-vertex diameter values (they are an input, as in the reference), the SDF heat
+points.  The per-vertex diameter values it loads are computed by ``smilify_amd.sdf``.  Out of scope and raising: the SDF heat
 maps, loss / mesh plots, normals / lengths / norm=1 in chamfer_distance, knn_points and SDF_distance, the cot / cotcurv Laplacians.
 
 Run as ``python -m smilify_amd.fit3d --model MODEL.npz --mesh_dir DIR [--yaml_src CFG.yaml] [--use_sdf --sdf_dir DIR]``
@@ -598,7 +598,8 @@ def main(args):
         source_sdf_values = load_sdf_values(source_name, args.sdf_dir, args.device)
         if source_sdf_values is None:
             raise FileNotFoundError(f"SDF file for source model not found at {os.path.join(args.sdf_dir, source_name + '_sdf.npz')} "
-                                    "(or .pkl). Compute the values of the source model first.")
+                                    "(or .pkl). Compute the values of the source model first "
+                                    "(python -m smilify_amd.sdf MESH_DIR --model MODEL).")
     mesh_files = get_mesh_files(args.mesh_dir, args.frame_step)
     if not mesh_files:
         raise FileNotFoundError(f"no .obj files in {args.mesh_dir}")
