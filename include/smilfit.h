@@ -501,6 +501,43 @@ int smil_ray_diameters(const float *verts, int32_t V, const int32_t *faces, int3
                        const float *dirs, int32_t S, int32_t R, float t_min, float d_lo, float d_hi, int32_t cap, float *ray_t,
                        float *diam, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The PointNet++ set-abstraction operations of the point-cloud regressor (smilify_amd/csrc/pointnet2.hip).  Replace
+ * farthest_point_sample, query_ball_point and the index_points + cat + permute grouping of the reference's
+ * fitter_3d/pointcloud2smil/pointnet2_utils.py.  Deterministic: two calls on the same inputs give the same bits (no float atomics).
+ * Every function checks its sizes before its pointers and both before it launches anything.
+ * ---------------------------------------------------------------------------------------- */
+#define SMIL_FPS_MAX_N 16384     /* points of one cloud in smil_fps: a cloud stays in the registers of one workgroup */
+#define SMIL_BALL_MAX_RADII 4    /* (radius, nsample) pairs of one smil_ball_query call */
+/* farthest_point_sample (pointnet2_utils.py:69-90): xyz (B,N,3), start (B) the first index of every cloud (the reference draws it
+ * with torch.randint; clamped to [0, N)), out (B,npoint) int32.  out[b,0] = start[b]; the running distance starts at 1e10 and takes
+ * d = (dx dx + dy dy) + dz dz (float32, every operation rounded on its own) where d < distance; the next index is the argmax of the
+ * running distance, the SMALLEST index among equal maxima (so npoint > N or duplicate points give index 0 once every distance is
+ * 0).  N > SMIL_FPS_MAX_N: SMIL_E_UNSUPPORTED. */
+int smil_fps(const float *xyz, const int32_t *start, int32_t B, int32_t N, int32_t npoint, int32_t *out, void *stream);
+
+/* query_ball_point (pointnet2_utils.py:93-113) at 1 .. SMIL_BALL_MAX_RADII radii in one pass: xyz (B,N,3) candidates, new_xyz
+ * (B,S,3) queries; radii, nsample and out are HOST arrays of n_radii entries, out[r] a device array (B,S,K_r) int32 with
+ * K_r = min(nsample[r], N).  A row holds the first K_r candidate indices, ascending, with d^2 <= r^2 (d^2 as in smil_fps,
+ * r^2 = radius * radius formed in double and rounded once to float32; equality is inside, as the reference excludes only
+ * sqrdists > radius ** 2), padded with the row's first hit; a query without a hit gets N in every slot. */
+int smil_ball_query(const float *xyz, const float *new_xyz, int32_t B, int32_t N, int32_t S, int32_t n_radii, const double *radii,
+                    const int32_t *nsample, int32_t *const *out, void *stream);
+
+/* The grouped tensor a set-abstraction layer's Conv2d reads (pointnet2_utils.py:131-138 and :249-258), contiguous (B,C,K,S):
+ * out[b,c,k,s] over the channels [xyz[b,i] - centres[b,s] (3), features[b,i] (D)] with i = idx[b,s,k] - or [features, xyz - centre]
+ * when xyz_last (the two orders of sample_and_group and PointNetSetAbstractionMsg).  xyz (B,N,3) or NULL (no coordinate channels:
+ * index_points), centres (B,S,3) or NULL (coordinates as they are), features (B,N,D) or NULL when D = 0, idx (B,S,K) int32.  An
+ * index outside [0, N) gives zeros in every channel (the reference raises IndexError). */
+int smil_group_points(const float *xyz, const float *centres, const float *features, const int32_t *idx, int32_t B, int32_t N, int32_t S,
+                      int32_t K, int32_t D, int32_t xyz_last, float *out, void *stream);
+/* Its gradient to the features: d_features (B,N,D) = the sum of d_out (B,C,K,S)'s feature channels over the (s,k) with
+ * idx[b,s,k] = n, as an order-independent int64 fixed-point sum (unit from the cloud's largest |d_out| and K S addends); an index
+ * outside [0, N) receives nothing.  has_xyz / xyz_last: the channel layout of the forward call.  The coordinates carry no gradient. */
+size_t smil_group_points_backward_workspace_bytes(int32_t B, int32_t N, int32_t D);
+int smil_group_points_backward(const float *d_out, const int32_t *idx, int32_t B, int32_t N, int32_t S, int32_t K, int32_t D,
+                               int32_t has_xyz, int32_t xyz_last, float *d_features, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

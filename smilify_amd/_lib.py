@@ -25,6 +25,7 @@ EXPORTS = [
     "smil_knn_workspace_bytes", "smil_knn", "smil_sdf_distance_workspace_bytes", "smil_sdf_distance", "smil_sample_vertices",
     "smil_sample_vertices_backward_workspace_bytes", "smil_sample_vertices_backward",
     "smil_ray_diameters_workspace_bytes", "smil_ray_diameters",
+    "smil_fps", "smil_ball_query", "smil_group_points", "smil_group_points_backward_workspace_bytes", "smil_group_points_backward",
 ]
 
 N_OBJS = 10
@@ -97,6 +98,9 @@ class MeshTopology(Structure):
 
 REG_EDGE, REG_NORMAL, REG_LAPLACIAN = 1, 2, 4
 KNN_MAX_K = 64  # SMIL_KNN_MAX_K
+FPS_MAX_N = 16384  # SMIL_FPS_MAX_N
+BALL_MAX_RADII = 4  # SMIL_BALL_MAX_RADII
+E_UNSUPPORTED = -3  # SMIL_E_UNSUPPORTED
 
 _lib = None
 
@@ -183,6 +187,13 @@ def load():
     lib.smil_ray_diameters_workspace_bytes.restype = c_size_t
     lib.smil_ray_diameters.argtypes = [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_float,
                                        c_float, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.smil_fps.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]
+    lib.smil_ball_query.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_double), POINTER(c_int32),
+                                    POINTER(c_void_p), c_void_p]
+    lib.smil_group_points.argtypes = [c_void_p] * 4 + [c_int32] * 6 + [c_void_p, c_void_p]
+    lib.smil_group_points_backward_workspace_bytes.argtypes = [c_int32] * 3
+    lib.smil_group_points_backward_workspace_bytes.restype = c_size_t
+    lib.smil_group_points_backward.argtypes = [c_void_p, c_void_p] + [c_int32] * 7 + [c_void_p, c_void_p, c_void_p]
     lib.smil_profile_enable.argtypes = [c_int32]
     lib.smil_profile_read.argtypes = [POINTER(c_float), POINTER(c_int32)]
     for name in EXPORTS:

@@ -856,3 +856,95 @@ def ray_diameters(verts: torch.Tensor, faces: torch.Tensor, origins: torch.Tenso
     _lib.check(lib.smil_ray_diameters(_ptr(verts), V, _ptr(faces), F, _ptr(origins), _ptr(own_face), _ptr(dirs), S, R, float(t_min), float(d_lo),
                                       float(d_hi), int(cap), _ptr(ray_t), _ptr(diam), _ptr(ws), _stream()), "smil_ray_diameters")
     return diam, ray_t
+
+
+# ---- PointNet++ set-abstraction operations (pointnet2.hip) ---------------------------------------------------------------------
+def _check_cloud(what: str, name: str, t: torch.Tensor, B: Optional[int] = None, last: Optional[int] = 3) -> None:
+    if not (isinstance(t, torch.Tensor) and t.dim() == 3 and t.dtype == torch.float32 and (last is None or t.shape[2] == last)
+            and (B is None or t.shape[0] == B)):
+        raise ValueError(f"{what}: {name} must be a float32 tensor (B, n, {'D' if last is None else last})")
+
+
+def fps(xyz: torch.Tensor, npoint: int, start: torch.Tensor) -> torch.Tensor:
+    """Farthest point sampling of xyz (B,N,3) from the start indices (B) int32: (B,npoint) int32 (smil_fps, include/smilfit.h).
+    ValueError when N exceeds SMIL_FPS_MAX_N."""
+    _check_cloud("fps", "xyz", xyz)
+    B, N, npoint = int(xyz.shape[0]), int(xyz.shape[1]), int(npoint)
+    if start.dtype != torch.int32 or tuple(start.shape) != (B,):
+        raise ValueError("fps: start must be an int32 tensor (B)")
+    if N > _lib.FPS_MAX_N:
+        raise ValueError(f"fps: N={N} above SMIL_FPS_MAX_N={_lib.FPS_MAX_N}")
+    if B < 1 or N < 1 or npoint < 1:
+        raise ValueError(f"fps: bad sizes B={B} N={N} npoint={npoint}")
+    xyz, start = xyz.contiguous(), start.contiguous()
+    out = torch.empty(B, npoint, device=xyz.device, dtype=torch.int32)
+    _lib.check(_lib.load().smil_fps(_ptr(xyz), _ptr(start), B, N, npoint, _ptr(out), _stream()), "smil_fps")
+    return out
+
+
+def ball_query(xyz: torch.Tensor, new_xyz: torch.Tensor, radii, nsamples):
+    """The ball queries of new_xyz (B,S,3) in xyz (B,N,3) at 1 .. SMIL_BALL_MAX_RADII (radius, nsample) pairs in one launch: a list of
+    (B,S,min(nsample, N)) int32 index tensors (smil_ball_query, include/smilfit.h)."""
+    _check_cloud("ball_query", "xyz", xyz)
+    _check_cloud("ball_query", "new_xyz", new_xyz, B=int(xyz.shape[0]))
+    radii, nsamples = [float(r) for r in radii], [int(k) for k in nsamples]
+    n = len(radii)
+    if not 1 <= n <= _lib.BALL_MAX_RADII or len(nsamples) != n:
+        raise ValueError(f"ball_query: 1 .. {_lib.BALL_MAX_RADII} (radius, nsample) pairs, got {n} radii and {len(nsamples)} nsample")
+    if min(nsamples) < 1 or not all(np.isfinite(r) and r >= 0.0 for r in radii):
+        raise ValueError(f"ball_query: nsample >= 1 and finite radii >= 0 (got {nsamples}, {radii})")
+    B, N, S = int(xyz.shape[0]), int(xyz.shape[1]), int(new_xyz.shape[1])
+    if B < 1 or N < 1 or S < 1:
+        raise ValueError(f"ball_query: bad sizes B={B} N={N} S={S}")
+    xyz, new_xyz = xyz.contiguous(), new_xyz.contiguous()
+    outs = [torch.empty(B, S, min(k, N), device=xyz.device, dtype=torch.int32) for k in nsamples]
+    _lib.check(_lib.load().smil_ball_query(_ptr(xyz), _ptr(new_xyz), B, N, S, n, (ctypes.c_double * n)(*radii), (ctypes.c_int32 * n)(*nsamples),
+                                           (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), _stream()), "smil_ball_query")
+    return outs
+
+
+def group_points(xyz: Optional[torch.Tensor], centres: Optional[torch.Tensor], features: Optional[torch.Tensor], idx: torch.Tensor,
+                 xyz_last: bool = False) -> torch.Tensor:
+    """The grouped tensor (B,C,K,S) of idx (B,S,K) int32: channels [xyz - centres (3), features (D)], or [features, xyz - centres]
+    with ``xyz_last``; xyz None: features only, centres None: coordinates as they are (smil_group_points, include/smilfit.h)."""
+    if xyz is None and features is None:
+        raise ValueError("group_points: neither coordinates nor features")
+    if idx.dim() != 3 or idx.dtype != torch.int32:
+        raise ValueError("group_points: idx must be an int32 tensor (B, S, K)")
+    B, S, K = (int(v) for v in idx.shape)
+    src = xyz if xyz is not None else features
+    N = int(src.shape[1]) if src.dim() == 3 else 0
+    if xyz is not None:
+        _check_cloud("group_points", "xyz", xyz, B=B)
+    if centres is not None:
+        _check_cloud("group_points", "centres", centres, B=B)
+        if xyz is None or int(centres.shape[1]) != S:
+            raise ValueError("group_points: centres (B, S, 3) need xyz and one centre per query")
+    D = 0
+    if features is not None:
+        _check_cloud("group_points", "features", features, B=B, last=None)
+        D = int(features.shape[2])
+        if int(features.shape[1]) != N:
+            raise ValueError("group_points: features (B, N, D) and xyz (B, N, 3) differ in N")
+    if min(B, S, K, N) < 1 or (xyz is None and D < 1):
+        raise ValueError(f"group_points: bad sizes B={B} N={N} S={S} K={K} D={D}")
+    xyz, centres, features, idx = (None if t is None else t.contiguous() for t in (xyz, centres, features, idx))
+    out = torch.empty(B, (0 if xyz is None else 3) + D, K, S, device=idx.device, dtype=torch.float32)
+    _lib.check(_lib.load().smil_group_points(_ptr(xyz), _ptr(centres), _ptr(features if D else None), _ptr(idx), B, N, S, K, D,
+                                             int(bool(xyz_last)), _ptr(out), _stream()), "smil_group_points")
+    return out
+
+
+def group_points_backward(d_out: torch.Tensor, idx: torch.Tensor, N: int, D: int, has_xyz: bool, xyz_last: bool) -> torch.Tensor:
+    """d_features (B,N,D): d_out (B,C,K,S)'s feature channels summed over the positions that drew each point (order-independent)."""
+    B, S, K = (int(v) for v in idx.shape)
+    N, D = int(N), int(D)
+    if idx.dtype != torch.int32 or d_out.dtype != torch.float32 or tuple(d_out.shape) != (B, (3 if has_xyz else 0) + D, K, S) or D < 1:
+        raise ValueError("group_points_backward: d_out (B, C, K, S) float32 and idx (B, S, K) int32 with C = 3 + D or D >= 1")
+    d_out, idx = d_out.contiguous(), idx.contiguous()
+    lib = _lib.load()
+    ws = torch.empty(int(lib.smil_group_points_backward_workspace_bytes(B, N, D)), dtype=torch.uint8, device=d_out.device)
+    d_feat = torch.empty(B, N, D, device=d_out.device, dtype=torch.float32)
+    _lib.check(lib.smil_group_points_backward(_ptr(d_out), _ptr(idx), B, N, S, K, D, int(bool(has_xyz)), int(bool(xyz_last)), _ptr(d_feat),
+                                              _ptr(ws), _stream()), "smil_group_points_backward")
+    return d_feat
