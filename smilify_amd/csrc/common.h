@@ -120,13 +120,21 @@ struct DeviceLimits { int cus; size_t lds_block; };
 DeviceLimits smil_device_limits();
 
 // ---- wave-level helpers (wave64) --------------------------------------------------------------
+// The value of lane `lane` (wave-uniform) in every lane.
+__device__ __forceinline__ int read_lane(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
+__device__ __forceinline__ float read_lane(float v, int lane) { return __builtin_bit_cast(float, read_lane(__builtin_bit_cast(int, v), lane)); }
+__device__ __forceinline__ unsigned long long read_lane(unsigned long long v, int lane) {
+    const uint32_t lo = (uint32_t)read_lane((int)(uint32_t)v, lane), hi = (uint32_t)read_lane((int)(uint32_t)(v >> 32), lane);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
 // Sum over the 64 lanes using DPP within rows of 16 and readlane across rows; result valid in all lanes.
 __device__ __forceinline__ float wave_sum(float v) {
     v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));  // quad_perm [1,0,3,2]
     v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));  // quad_perm [2,3,0,1]
     v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true)); // row_half_mirror
     v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true)); // row_mirror
-    const int iv = __builtin_bit_cast(int, v);
+    const int iv = __builtin_bit_cast(int, v);  // (one cast, not four read_lane calls: those schedule lbs.hip's kernels differently)
     const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 0));
     const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 16));
     const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 32));
@@ -194,6 +202,32 @@ __device__ __forceinline__ void wave_sum12(const float (&v)[12], float (&q)[3]) 
         x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x140, 0xF, 0xF, true));  // row_mirror
         q[i] = x;
     }
+}
+
+// ---- order-independent scatter sums: int64 fixed point with a unit that follows the data (mesh3d.hip, pointnet2.hip) ----
+// A gradient that many threads add into one element is summed as integers: no float atomics, and the result does not depend on the
+// order of the additions.  The unit 2^-fix is a power of two per segment (a mesh and direction, a mesh, a cloud).  A first pass
+// leaves the bits of the segment's largest magnitude with an atomicMax (magnitudes are >= 0: their bits order like the values, and
+// a maximum does not depend on the order either).  With every |addend| < 2^eb and fewer than 2^pb addends meeting in one element,
+// fix = 61 - pb - eb keeps the sum, roundings included, below 2^62 whatever the data's extent (a fixed 2^-32 lost the gradient
+// of clouds whose extent is far below 1), and scaling the data by a power of two scales the result exactly.
+
+// eb with m < 2^eb for a recorded maximum m, from its bits
+__device__ __forceinline__ int fix_max_exp(unsigned int max_bits) {
+    int ex;
+    frexpf(fminf(__uint_as_float(max_bits), 3.0e38f), &ex);  // (non-finite input: any finite unit)
+    return ex;
+}
+// fix for |addend| < 2^eb and at most `addends` (>= 1, < 2^pb) addends per element
+__device__ __forceinline__ int fix_unit_exp(int eb, long long addends) { return 61 - (64 - __clzll(addends)) - eb; }
+__device__ __forceinline__ void fix_add(long long *acc, double v, int fix) {
+    atomicAdd((unsigned long long *)acc, (unsigned long long)__double2ll_rn(ldexp(v, fix)));
+}
+__device__ __forceinline__ float fix_read(long long acc, int fix) { return (float)ldexp((double)acc, -fix); }
+// the first pass: the wave's largest m (>= 0) into the segment's slot, zeroed before the launch
+__device__ __forceinline__ void fix_record_max(unsigned int *slot, float m) {
+    m = wave_max(m);
+    if ((threadIdx.x & 63) == 0) atomicMax(slot, __float_as_uint(m));
 }
 
 // ---- FoV-perspective camera of image n (project.hip; also read by the fused LBS backward in lbs.hip) ----

@@ -12,9 +12,8 @@
 //                        which is order independent (distances are >= 0, so their bits order like the values; ties go to the
 //                        smaller index, as a sequential scan with < gives).
 //  * k_chamfer_owned     thread per query: argmin out, the owned gradient 2 w (q - c*), and the scattered side (c* - q) added to the
-//                        candidate's int64 fixed-point accumulator (integer sums do not depend on the order).  The unit is a
-//                        power of two chosen per (mesh, direction) from the largest minimum found and the number of queries, so
-//                        that the sum uses the 64 bits whatever the clouds' extent (ch_fix_exp).
+//                        candidate's int64 fixed-point accumulator, whose unit follows the largest minimum found and the number
+//                        of queries of its (mesh, direction): ch_fix_exp, and "order-independent scatter sums" in common.h.
 //  * k_chamfer_scatter   thread per point: the scattered sum converted and added to the owned gradient.
 //  * k_chamfer_reduce    per (mesh, direction) sums of the minima in a fixed order, then the batch in a fixed order.
 //  * k_mesh_reg          edge, normal consistency and uniform Laplacian terms and their gradients in one pass: thread t evaluates edge
@@ -105,34 +104,45 @@ extern "C" int smil_sample_points(const float *verts, int32_t n_verts, const int
 // ---------------------------------------------------------------------------------------------
 // chamfer distance
 // ---------------------------------------------------------------------------------------------
-struct ChamferArgs {
+// What chamfer and the SDF term share: two clouds, a per-query distance, its loss, and the gradient of both clouds.  (Pointers
+// before sizes: the other way round hipcc 7.2 gives k_chamfer_nn 76 VGPRs for 47.)
+struct CloudLossArgs {
     const float *pts[2];      // (N, P[d], 3): direction d's queries are pts[d], its candidates pts[1 - d]
-    int P[2];
-    int N, dirs, splits;
-    int K;                    // terms of one query that can meet in a scattered sum's point: 1 (chamfer), K (the SDF term)
-    float w[2];               // loss weight of one term of direction d (1/P and/or 1/N as reduced)
-    unsigned long long *key;  // (N, P[0] + P[1]) {distance bits, candidate index}: direction 0's queries first
-    float *dist;              // (N, P[0] + P[1])
+    float *dist;              // (N, P[0] + P[1]) direction 0's queries first: the minimum (chamfer), r_i (the SDF term)
     long long *acc;           // (N, P[0] + P[1], 3) fixed-point scattered sums, per point of either cloud
-    unsigned int *dmax;       // (N, 2) bits of the largest per-split minimum of (mesh, direction): bounds every |q - c*|^2
-    int *idx[2];              // (N, P[d]) or NULL
+    unsigned int *dmax;       // (N, 2) bits of the largest squared distance of (mesh, direction) that enters a gradient
     float *grad[2];           // (N, P[d], 3) or NULL
     float *part;              // (N, dirs)
     float *loss;              // (1)
+    int P[2];
+    int N, dirs;
+    int K;                    // terms of one query that can meet in a scattered sum's point: 1 (chamfer), K (the SDF term)
+    float w[2];               // loss weight of one term of direction d (1/P and/or 1/N as reduced)
 };
 
-__device__ __forceinline__ size_t ch_row(const ChamferArgs &a, int n, int d) { return (size_t)n * (a.P[0] + a.P[1]) + (d ? a.P[0] : 0); }
+// ... and what only the nearest-neighbour search of chamfer uses
+struct ChamferArgs : CloudLossArgs {
+    int splits;
+    unsigned long long *key;  // (N, P[0] + P[1]) {distance bits, candidate index}: direction 0's queries first
+    int *idx[2];              // (N, P[d]) or NULL
+};
 
-// Exponent s of the fixed-point unit 2^-s of direction d's scattered sums in mesh n.  Every component of q - c* is below 2^eb, where
-// 2^(2 eb) >= the largest minimum (one more bit covers the rounding of the distance), and at most P[d] < 2^pb of them meet in one
-// sum (P[d] K < 2^pb in the SDF term, whose addends carry a weight <= 1): with s = 61 - pb - eb the sum stays below 2^62.  A fixed
-// 2^-32 lost the gradient of clouds whose extent is far below 1.
-__device__ __forceinline__ int ch_fix_exp(const ChamferArgs &a, int n, int d) {
-    int ex;
-    frexpf(fminf(__uint_as_float(a.dmax[n * 2 + d]), 3.0e38f), &ex);  // (non-finite input: any finite unit)
-    const int eb = ((ex + 1) >> 1) + 1;
-    const int pb = 64 - __clzll((long long)a.P[d] * a.K);
-    return 61 - pb - eb;
+__device__ __forceinline__ size_t ch_row(const CloudLossArgs &a, int n, int d) { return (size_t)n * (a.P[0] + a.P[1]) + (d ? a.P[0] : 0); }
+
+// Unit exponent (common.h) of direction d's scattered sums in mesh n.  Magnitude: the half exponent of the largest squared distance plus
+// one (for the rounding of the distance), which bounds every component of q - c*.  Addends: P[d] K (the SDF term's weigh <= 1).
+__device__ __forceinline__ int ch_fix_exp(const CloudLossArgs &a, int n, int d) {
+    return fix_unit_exp(((fix_max_exp(a.dmax[n * 2 + d]) + 1) >> 1) + 1, (long long)a.P[d] * a.K);
+}
+
+// The workgroup's first cnt (<= 256) threads stage candidates c0 .. c0 + cnt - 1 of C into LDS as float4, between two barriers.
+__device__ __forceinline__ void stage_tile(float4 *tile, const float *C, int c0, int cnt) {
+    __syncthreads();
+    if ((int)threadIdx.x < cnt) {
+        const float *p = C + 3 * (size_t)(c0 + threadIdx.x);
+        tile[threadIdx.x] = make_float4(p[0], p[1], p[2], 0.f);
+    }
+    __syncthreads();
 }
 
 __global__ void __launch_bounds__(CH_BLOCK) k_chamfer_nn(ChamferArgs a) {
@@ -158,12 +168,7 @@ __global__ void __launch_bounds__(CH_BLOCK) k_chamfer_nn(ChamferArgs a) {
     }
     for (int c0 = c_begin; c0 < c_end; c0 += CH_TILE) {
         const int cnt = min(CH_TILE, c_end - c0);
-        __syncthreads();
-        if ((int)threadIdx.x < cnt) {
-            const float *p = C + 3 * (size_t)(c0 + threadIdx.x);
-            tile[threadIdx.x] = make_float4(p[0], p[1], p[2], 0.f);
-        }
-        __syncthreads();
+        stage_tile(tile, C, c0, cnt);
 #pragma unroll 4
         for (int j = 0; j < cnt; ++j) {
             const float4 c = tile[j];
@@ -187,10 +192,7 @@ __global__ void __launch_bounds__(CH_BLOCK) k_chamfer_nn(ChamferArgs a) {
             bmax = fmaxf(bmax, best[k]);
         }
     }
-    if (a.grad[0]) {  // distances are >= 0: their bits order like the values, and a maximum does not depend on the order
-        bmax = wave_max(bmax);
-        if ((threadIdx.x & 63) == 0) atomicMax(&a.dmax[n * 2 + d], __float_as_uint(bmax));
-    }
+    if (a.grad[0]) fix_record_max(&a.dmax[n * 2 + d], bmax);
 }
 
 __global__ void __launch_bounds__(256) k_chamfer_owned(ChamferArgs a) {
@@ -217,13 +219,12 @@ __global__ void __launch_bounds__(256) k_chamfer_owned(ChamferArgs a) {
         long long *acc = a.acc + (ch_row(a, n, 1 - d) + j) * 3;
         const int fix = ch_fix_exp(a, n, d);
 #pragma unroll
-        for (int k = 0; k < 3; ++k)
-            atomicAdd((unsigned long long *)&acc[k], (unsigned long long)__double2ll_rn(ldexp(-(double)e[k], fix)));
+        for (int k = 0; k < 3; ++k) fix_add(&acc[k], -(double)e[k], fix);
     }
 }
 
 // both clouds' points: the scattered sums of direction 1 - s land on cloud s's points, weighted by w[1 - s]
-__global__ void __launch_bounds__(256) k_chamfer_scatter(ChamferArgs a) {
+__global__ void __launch_bounds__(256) k_chamfer_scatter(CloudLossArgs a) {
     const int side = blockIdx.z & 1, n = blockIdx.z >> 1;
     const int P = a.P[side];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -236,12 +237,12 @@ __global__ void __launch_bounds__(256) k_chamfer_scatter(ChamferArgs a) {
     const int fix = receives ? ch_fix_exp(a, n, 1 - side) : 0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const float sc = receives ? (float)ldexp((double)acc[k], -fix) * s : 0.f;
+        const float sc = receives ? fix_read(acc[k], fix) * s : 0.f;
         g[k] = (has_owned ? g[k] : 0.f) + sc;
     }
 }
 
-__global__ void __launch_bounds__(256) k_chamfer_reduce(ChamferArgs a) {
+__global__ void __launch_bounds__(256) k_chamfer_reduce(CloudLossArgs a) {
     __shared__ float red[16];
     const int d = blockIdx.x % a.dirs, n = blockIdx.x / a.dirs;
     const int P = a.P[d];
@@ -257,6 +258,32 @@ __global__ void __launch_bounds__(64) k_chamfer_total(const float *__restrict__ 
     for (int i = threadIdx.x; i < n; i += 64) s += part[i];
     s = wave_sum(s);
     if (threadIdx.x == 0) loss[0] = s;
+}
+
+// the shared part but its workspace regions and K
+static void cloud_loss_fill(CloudLossArgs &c, const float *x, const float *y, int N, int P1, int P2, int single_directional, int point_sum,
+                            int batch_sum, float *d_x, float *d_y, float *loss) {
+    c.pts[0] = x; c.pts[1] = y;
+    c.P[0] = P1; c.P[1] = P2;
+    c.N = N; c.dirs = single_directional ? 1 : 2;
+    const float bw = batch_sum ? 1.0f : 1.0f / (float)N;
+    c.w[0] = (point_sum ? 1.0f : 1.0f / (float)P1) * bw;
+    c.w[1] = (point_sum ? 1.0f : 1.0f / (float)P2) * bw;
+    c.grad[0] = d_x; c.grad[1] = d_y;
+    c.loss = loss;
+}
+
+// the end of both calls: the scattered sums into the gradients, then the loss from c.dist
+static int cloud_loss_finish(const CloudLossArgs &c, hipStream_t stream) {
+    if (c.grad[0]) {
+        hipLaunchKernelGGL(k_chamfer_scatter, dim3(ceil_div(std::max(c.P[0], c.P[1]), 256), 1, c.N * 2), dim3(256), 0, stream, c);
+        SMIL_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_chamfer_reduce, dim3(c.N * c.dirs), dim3(256), 0, stream, c);
+    SMIL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_chamfer_total, dim3(1), dim3(64), 0, stream, (const float *)c.part, c.N * c.dirs, c.loss);
+    SMIL_LAUNCH_CHECK();
+    return SMIL_OK;
 }
 
 static size_t chamfer_layout(int N, int P1, int P2, char *base, ChamferArgs &a) {
@@ -287,15 +314,9 @@ extern "C" int smil_chamfer(const float *x, const float *y, int32_t N, int32_t P
     const size_t pts = (size_t)N * ((size_t)P1 + P2);
     ChamferArgs a;
     chamfer_layout(N, P1, P2, (char *)workspace, a);
-    a.pts[0] = x; a.pts[1] = y;
-    a.P[0] = P1; a.P[1] = P2;
-    a.N = N; a.dirs = single_directional ? 1 : 2; a.K = 1;
-    const float bw = batch_sum ? 1.0f : 1.0f / (float)N;
-    a.w[0] = (point_sum ? 1.0f : 1.0f / (float)P1) * bw;
-    a.w[1] = (point_sum ? 1.0f : 1.0f / (float)P2) * bw;
+    cloud_loss_fill(a, x, y, N, P1, P2, single_directional, point_sum, batch_sum, d_x, d_y, loss);
+    a.K = 1;
     a.idx[0] = idx_x; a.idx[1] = idx_y;
-    a.grad[0] = d_x; a.grad[1] = d_y;
-    a.loss = loss;
     // candidate splits: enough workgroups for the whole GPU (>= 2048) while every split still streams >= 4 tiles
     const int qblocks = ceil_div(std::max(P1, P2), CH_BLOCK * CH_QPT);
     const int base = qblocks * N * a.dirs;
@@ -310,15 +331,7 @@ extern "C" int smil_chamfer(const float *x, const float *y, int32_t N, int32_t P
     SMIL_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_chamfer_owned, dim3(ceil_div(std::max(P1, P2), 256), 1, N * a.dirs), dim3(256), 0, stream, a);
     SMIL_LAUNCH_CHECK();
-    if (d_x) {
-        hipLaunchKernelGGL(k_chamfer_scatter, dim3(ceil_div(std::max(P1, P2), 256), 1, N * 2), dim3(256), 0, stream, a);
-        SMIL_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(k_chamfer_reduce, dim3(N * a.dirs), dim3(256), 0, stream, a);
-    SMIL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_chamfer_total, dim3(1), dim3(64), 0, stream, (const float *)a.part, N * a.dirs, loss);
-    SMIL_LAUNCH_CHECK();
-    return SMIL_OK;
+    return cloud_loss_finish(a, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -540,12 +553,6 @@ struct KnnArgs {
     unsigned long long *n_insert;  // (1) list insertions of the call, or NULL
 };
 
-__device__ __forceinline__ unsigned long long readlane64(unsigned long long v, int lane) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, lane);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
 // Lane l of a wave holds the l-th smallest key seen so far of each of the wave's KNN_QPW queries (KNN_EMPTY: none yet); keys order
 // like (distance, index) because distances are >= 0.  All 64 entries are kept whatever K is: thr, the key of lane K - 1, is what a
 // candidate has to beat, and the first K lanes are the result.  A step gives every lane one candidate; the lanes whose candidate
@@ -572,12 +579,7 @@ __global__ void __launch_bounds__(KNN_BLOCK) k_knn(KnnArgs a) {
     unsigned int ins = 0;
     for (int c0 = 0; c0 < Pc; c0 += KNN_TILE) {
         const int cnt = min(KNN_TILE, Pc - c0);
-        __syncthreads();
-        if ((int)threadIdx.x < cnt) {
-            const float *p = C + 3 * (size_t)(c0 + threadIdx.x);
-            tile[threadIdx.x] = make_float4(p[0], p[1], p[2], 0.f);
-        }
-        __syncthreads();
+        stage_tile(tile, C, c0, cnt);
         for (int j0 = 0; j0 < cnt; j0 += WAVE) {
             const int j = j0 + lane;  // (< KNN_TILE: the read stays inside the tile, entries past cnt are not used)
             const float4 c = tile[j];
@@ -591,11 +593,11 @@ __global__ void __launch_bounds__(KNN_BLOCK) k_knn(KnnArgs a) {
                 while (m) {
                     const int l = __ffsll((long long)m) - 1;
                     m &= m - 1;
-                    const unsigned long long nk = readlane64(ck, l);
+                    const unsigned long long nk = read_lane(ck, l);
                     if (nk < thr[k]) {
                         const unsigned long long up = __shfl_up(key[k], 1, WAVE);
                         if (key[k] > nk) key[k] = (lane > 0 && up > nk) ? up : nk;
-                        thr[k] = readlane64(key[k], a.K - 1);
+                        thr[k] = read_lane(key[k], a.K - 1);
                         ++ins;
                     }
                 }
@@ -615,7 +617,7 @@ __global__ void __launch_bounds__(KNN_BLOCK) k_knn(KnnArgs a) {
             kmax = fmaxf(kmax, __uint_as_float((uint32_t)(thr[k] >> 32)));  // (K <= Pc: the K-th entry is a candidate)
         }
     }
-    if (lane == 0) {  // (an integer maximum and an integer sum: neither depends on the order)
+    if (lane == 0) {  // (kmax is wave-uniform already: fix_record_max's wave maximum is not needed; the sum is an integer's)
         if (a.dmax) atomicMax(&a.dmax[n * 2 + d], __float_as_uint(kmax));
         if (a.n_insert) atomicAdd(a.n_insert, (unsigned long long)ins);
     }
@@ -670,7 +672,7 @@ extern "C" int smil_knn(const float *x, const float *y, int32_t N, int32_t P1, i
 #define SDF_STD_MIN 1e-8          // utils.py:1044
 
 struct SdfArgs {
-    ChamferArgs c;         // clouds, weights, fixed-point accumulators, gradients, partial sums; c.dist holds r_i, c.key is unused
+    CloudLossArgs c;       // clouds, weights, fixed-point accumulators, gradients, partial sums; c.dist holds r_i
     KnnArgs knn;
     const float *val[2];   // (N, P[s]) per-point values of side s
     double *z;             // (N, P[0] + P[1]) their z-scores, side 0's first (ch_row)
@@ -748,8 +750,7 @@ __global__ void __launch_bounds__(256) k_sdf_term(SdfArgs a) {
         long long *acc = a.c.acc + (ch_row(a.c, n, 1 - d) + j) * 3;
         const int fix = ch_fix_exp(a.c, n, d);
 #pragma unroll
-        for (int k = 0; k < 3; ++k)
-            atomicAdd((unsigned long long *)&acc[k], (unsigned long long)__double2ll_rn(ldexp(-(double)w * (double)ex[k], fix)));
+        for (int k = 0; k < 3; ++k) fix_add(&acc[k], -(double)w * (double)ex[k], fix);
     }
 }
 
@@ -796,17 +797,9 @@ extern "C" int smil_sdf_distance(const float *x, const float *y, const float *x_
     sdf_layout(N, P1, P2, K, true, (char *)workspace, a);
     if (dists_x) { a.knn.dists[0] = dists_x; a.knn.idx[0] = (int *)idx_x; }
     if (dists_y) { a.knn.dists[1] = dists_y; a.knn.idx[1] = (int *)idx_y; }
-    ChamferArgs &c = a.c;
-    c.pts[0] = x; c.pts[1] = y;
-    c.P[0] = P1; c.P[1] = P2;
-    c.N = N; c.dirs = single_directional ? 1 : 2; c.splits = 1; c.K = K;
-    const float bw = batch_sum ? 1.0f : 1.0f / (float)N;
-    c.w[0] = (point_sum ? 1.0f : 1.0f / (float)P1) * bw;
-    c.w[1] = (point_sum ? 1.0f : 1.0f / (float)P2) * bw;
-    c.key = nullptr;
-    c.idx[0] = c.idx[1] = nullptr;
-    c.grad[0] = d_x; c.grad[1] = d_y;
-    c.loss = loss;
+    CloudLossArgs &c = a.c;
+    cloud_loss_fill(c, x, y, N, P1, P2, single_directional, point_sum, batch_sum, d_x, d_y, loss);
+    c.K = K;
     a.knn.pts[0] = x; a.knn.pts[1] = y;
     a.knn.P[0] = P1; a.knn.P[1] = P2;
     a.knn.N = N; a.knn.dirs = c.dirs; a.knn.K = K;
@@ -820,15 +813,7 @@ extern "C" int smil_sdf_distance(const float *x, const float *y, const float *x_
     if (knn_launch(a.knn, stream) != SMIL_OK) return SMIL_E_DEVICE;
     hipLaunchKernelGGL(k_sdf_term, dim3(ceil_div(std::max(P1, c.dirs == 2 ? P2 : 1), 256 / WAVE), 1, N * c.dirs), dim3(256), 0, stream, a);
     SMIL_LAUNCH_CHECK();
-    if (d_x) {
-        hipLaunchKernelGGL(k_chamfer_scatter, dim3(ceil_div(std::max(P1, P2), 256), 1, N * 2), dim3(256), 0, stream, c);
-        SMIL_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(k_chamfer_reduce, dim3(N * c.dirs), dim3(256), 0, stream, c);
-    SMIL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_chamfer_total, dim3(1), dim3(64), 0, stream, (const float *)c.part, N * c.dirs, loss);
-    SMIL_LAUNCH_CHECK();
-    return SMIL_OK;
+    return cloud_loss_finish(c, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -869,8 +854,8 @@ extern "C" int smil_sample_vertices(const float *verts, const float *values, con
     return SMIL_OK;
 }
 
-// The gradient of the sampled points back to the vertices: duplicates of a vertex are summed as int64 fixed point, with a unit
-// that follows the data like ch_fix_exp (the mesh's largest |component| and S addends), so the sum does not depend on the order.
+// The gradient of the sampled points back to the vertices: duplicates of a vertex are summed as int64 fixed point (common.h);
+// magnitude: the mesh's largest |component|, addends: S.
 struct SvGradArgs {
     const float *d_pts;    // (N, S, 3)
     const int *idx;        // (N, S) vertex within its mesh, -1: none
@@ -881,11 +866,7 @@ struct SvGradArgs {
     unsigned int *gmax;    // (N) bits of the mesh's largest |component|
 };
 
-__device__ __forceinline__ int sv_fix_exp(const SvGradArgs &a, int n) {
-    int ex;
-    frexpf(fminf(__uint_as_float(a.gmax[n]), 3.0e38f), &ex);  // every |component| < 2^ex
-    return 61 - (32 - __clz(a.S)) - ex;
-}
+__device__ __forceinline__ int sv_fix_exp(const SvGradArgs &a, int n) { return fix_unit_exp(fix_max_exp(a.gmax[n]), (unsigned)a.S); }
 
 __global__ void __launch_bounds__(256) k_sv_max(SvGradArgs a) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x, n = blockIdx.y;
@@ -894,8 +875,7 @@ __global__ void __launch_bounds__(256) k_sv_max(SvGradArgs a) {
         const float *g = a.d_pts + ((size_t)n * a.S + s) * 3;
         m = fmaxf(fabsf(g[0]), fmaxf(fabsf(g[1]), fabsf(g[2])));
     }
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) atomicMax(&a.gmax[n], __float_as_uint(m));
+    fix_record_max(&a.gmax[n], m);
 }
 
 __global__ void __launch_bounds__(256) k_sv_add(SvGradArgs a) {
@@ -907,8 +887,7 @@ __global__ void __launch_bounds__(256) k_sv_add(SvGradArgs a) {
     const int fix = sv_fix_exp(a, n);
     long long *acc = a.acc + (size_t)(v0 + i) * 3;
 #pragma unroll
-    for (int k = 0; k < 3; ++k)
-        atomicAdd((unsigned long long *)&acc[k], (unsigned long long)__double2ll_rn(ldexp((double)a.d_pts[3 * o + k], fix)));
+    for (int k = 0; k < 3; ++k) fix_add(&acc[k], (double)a.d_pts[3 * o + k], fix);
 }
 
 __global__ void __launch_bounds__(256) k_sv_out(SvGradArgs a) {
@@ -917,7 +896,7 @@ __global__ void __launch_bounds__(256) k_sv_out(SvGradArgs a) {
     if (i >= a.vert_off[n + 1] - v0) return;
     const int fix = sv_fix_exp(a, n);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) a.d_verts[(size_t)(v0 + i) * 3 + k] = (float)ldexp((double)a.acc[(size_t)(v0 + i) * 3 + k], -fix);
+    for (int k = 0; k < 3; ++k) a.d_verts[(size_t)(v0 + i) * 3 + k] = fix_read(a.acc[(size_t)(v0 + i) * 3 + k], fix);
 }
 
 static size_t sv_grad_layout(int n_verts, int N, char *base, SvGradArgs &a) {

@@ -20,9 +20,8 @@
 //  * k_group_points    the (B, C, K, S) tensor Conv2d reads, through a 64 x 64 LDS tile: feature rows are read along the channels and
 //                      stored along the positions, both coalesced.  An index outside [0, N) gives a zero row.
 //  * k_group_max / _add / _out   the gradient of the grouped features back to (B, N, D): duplicates of an index (padding makes them
-//                      the common case) are summed as int64 fixed point with a unit that follows the cloud's largest |gradient| and
-//                      the K S addends an element can get, like k_sv_* (mesh3d.hip): no float atomics, the sum does not depend on
-//                      the order.  The tile is the forward's, walked the other way.
+//                      the common case) are summed as int64 fixed point (common.h, "order-independent scatter sums"; magnitude:
+//                      the cloud's largest |gradient|, addends: K S).  The tile is the forward's, walked the other way.
 #include <algorithm>
 #include <cmath>
 
@@ -45,19 +44,9 @@ __device__ __forceinline__ unsigned long long row_max_u64(unsigned long long k) 
     return k;
 }
 
-__device__ __forceinline__ unsigned long long read_lane_u64(unsigned long long k, int lane) {
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)k, lane);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(k >> 32), lane);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-__device__ __forceinline__ float read_lane_f32(float v, int lane) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
-}
-
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k) {
     k = row_max_u64(k);
-    const unsigned long long r0 = read_lane_u64(k, 0), r1 = read_lane_u64(k, 16), r2 = read_lane_u64(k, 32), r3 = read_lane_u64(k, 48);
+    const unsigned long long r0 = read_lane(k, 0), r1 = read_lane(k, 16), r2 = read_lane(k, 32), r3 = read_lane(k, 48);
     const unsigned long long a = r0 > r1 ? r0 : r1, b = r2 > r3 ? r2 : r3;
     return a > b ? a : b;
 }
@@ -103,9 +92,9 @@ __global__ void __launch_bounds__(ONE_WAVE ? 64 : 1024) k_fps(const float *xyz, 
         unsigned long long m = wave_max_u64(key);
         if (ONE_WAVE) {
             const int w = __builtin_ctzll(__ballot(key == m));  // keys are unique: they hold the index
-            cx = read_lane_f32(bx, w);
-            cy = read_lane_f32(by, w);
-            cz = read_lane_f32(bz, w);
+            cx = read_lane(bx, w);
+            cy = read_lane(by, w);
+            cz = read_lane(bz, w);
         } else {
             const int par = it & 1, wave = tid >> 6, nw = T >> 6;
             if (key == m) {
@@ -118,11 +107,11 @@ __global__ void __launch_bounds__(ONE_WAVE ? 64 : 1024) k_fps(const float *xyz, 
             const bool on = lane < nw;
             const unsigned long long k2 = on ? s_key[par][lane] : 0ull;
             const float x2 = on ? s_c[par][lane][0] : 0.f, y2 = on ? s_c[par][lane][1] : 0.f, z2 = on ? s_c[par][lane][2] : 0.f;
-            m = read_lane_u64(row_max_u64(k2), 0);  // nw <= 16: the entries sit in the first row
+            m = read_lane(row_max_u64(k2), 0);  // nw <= 16: the entries sit in the first row
             const int w = __builtin_ctzll(__ballot(on && k2 == m));
-            cx = read_lane_f32(x2, w);
-            cy = read_lane_f32(y2, w);
-            cz = read_lane_f32(z2, w);
+            cx = read_lane(x2, w);
+            cy = read_lane(y2, w);
+            cz = read_lane(z2, w);
         }
         far = 0xFFFFFFFFu - (unsigned)m;
     }
@@ -304,11 +293,7 @@ __global__ void __launch_bounds__(256) k_group_points(GroupArgs a) {
     }
 }
 
-__device__ __forceinline__ int group_fix_exp(const GroupArgs &a, int b) {
-    int ex;
-    frexpf(fminf(__uint_as_float(a.gmax[b]), 3.0e38f), &ex);  // every |gradient| of the cloud < 2^ex
-    return 61 - (32 - __clz(a.K * a.S)) - ex;                 // an element gets at most K S < 2^(32 - clz) addends
-}
+__device__ __forceinline__ int group_fix_exp(const GroupArgs &a, int b) { return fix_unit_exp(fix_max_exp(a.gmax[b]), (unsigned)(a.K * a.S)); }
 
 __global__ void __launch_bounds__(256) k_group_max(GroupArgs a) {
     const int b = blockIdx.x / a.max_blocks, j = blockIdx.x % a.max_blocks;
@@ -316,8 +301,7 @@ __global__ void __launch_bounds__(256) k_group_max(GroupArgs a) {
     const float *g = a.out + ((size_t)b * a.C + a.feat_off) * a.K * a.S;  // the feature channels are one contiguous range
     float m = 0.f;
     for (size_t i = (size_t)j * 256 + threadIdx.x; i < n; i += (size_t)a.max_blocks * 256) m = fmaxf(m, fabsf(g[i]));
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(&a.gmax[b], __float_as_uint(m));
+    fix_record_max(&a.gmax[b], m);
 }
 
 __global__ void __launch_bounds__(256) k_group_add(GroupArgs a) {
@@ -339,7 +323,7 @@ __global__ void __launch_bounds__(256) k_group_add(GroupArgs a) {
             if (i >= 0 && d < a.D) {
                 const float v = tile[r][lane];
                 if (v != 0.f)
-                    atomicAdd((unsigned long long *)&a.acc[((size_t)b * a.N + i) * a.D + d], (unsigned long long)__double2ll_rn(ldexp((double)v, fix)));
+                    fix_add(&a.acc[((size_t)b * a.N + i) * a.D + d], (double)v, fix);
             }
         }
         __syncthreads();
@@ -349,7 +333,7 @@ __global__ void __launch_bounds__(256) k_group_add(GroupArgs a) {
 __global__ void __launch_bounds__(256) k_group_out(GroupArgs a, int B) {
     const size_t per = (size_t)a.N * a.D, i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= per * B) return;
-    a.d_feat[i] = (float)ldexp((double)a.acc[i], -group_fix_exp(a, (int)(i / per)));
+    a.d_feat[i] = fix_read(a.acc[i], group_fix_exp(a, (int)(i / per)));
 }
 
 static bool group_sizes_ok(int64_t B, int64_t N, int64_t S, int64_t K, int64_t D, int64_t C) {

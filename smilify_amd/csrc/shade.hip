@@ -31,8 +31,6 @@
 #define C_EPS 1e-8f              // pytorch3d kEpsilon of the rasteriser
 #define N_EPS 1e-6f              // F.normalize eps of the normals and the light / view directions
 
-__device__ __forceinline__ float rdl(float x, int j) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), j)); }
-__device__ __forceinline__ int rdl(int x, int j) { return __builtin_amdgcn_readlane(x, j); }
 __device__ __forceinline__ float cpix_to_ndc(int i, int S) { return -1.0f + (2.0f * (float)i + 1.0f) / (float)S; }
 
 // ---------------------------------------------------------------------------------------------
@@ -111,7 +109,7 @@ __global__ void __launch_bounds__(64) k_colour_tiles(ColourArgs a) {
     const int xl = lane & (CTILE - 1), yl = lane >> 3;
     for (uint32_t t = blockIdx.x; t < total; t += gridDim.x) {
         const int k = __popcll(__ballot(incl <= t));  // (lanes >= nk never count)
-        const uint32_t slot = t - (uint32_t)rdl((int)excl, k);
+        const uint32_t slot = t - (uint32_t)read_lane((int)excl, k);
         const int part = k % cs.n_parts, cls = k / cs.n_parts;
         const size_t idx = (size_t)(2 * part + (cls >> 1)) * cs.item_cap + ((cls & 1) ? cs.item_cap - 1u - slot : slot);
         const uint4 it = cs.items[idx];
@@ -162,15 +160,15 @@ __global__ void __launch_bounds__(64) k_colour_tiles(ColourArgs a) {
             while (mask) {
                 const int j = __builtin_ctzll(mask);
                 mask &= mask - 1ull;
-                const float w0 = fmaf(rdl(A0, j), dx, fmaf(rdl(B0, j), dy, rdl(C0, j)));
-                const float w1 = fmaf(rdl(A1, j), dx, fmaf(rdl(B1, j), dy, rdl(C1, j)));
-                const float w2 = fmaf(rdl(A2, j), dx, fmaf(rdl(B2, j), dy, rdl(C2, j)));
+                const float w0 = fmaf(read_lane(A0, j), dx, fmaf(read_lane(B0, j), dy, read_lane(C0, j)));
+                const float w1 = fmaf(read_lane(A1, j), dx, fmaf(read_lane(B1, j), dy, read_lane(C1, j)));
+                const float w2 = fmaf(read_lane(A2, j), dx, fmaf(read_lane(B2, j), dy, read_lane(C2, j)));
                 if (w0 > 0.f && w1 > 0.f && w2 > 0.f) {
                     const float den = fmaxf(w0 + w1 + w2, C_EPS);
-                    const float pz = (w0 * rdl(z0, j) + w1 * rdl(z1, j) + w2 * rdl(z2, j)) / den;
-                    const uint32_t kj = (uint32_t)rdl((int)key, j);
+                    const float pz = (w0 * read_lane(z0, j) + w1 * read_lane(z1, j) + w2 * read_lane(z2, j)) / den;
+                    const uint32_t kj = (uint32_t)read_lane((int)key, j);
                     if (pz >= 0.f && (pz < bz || (pz == bz && kj < bkey))) {
-                        bz = pz; bkey = kj; bfid = rdl(f, j); bw0 = w0; bw1 = w1; bw2 = w2;
+                        bz = pz; bkey = kj; bfid = read_lane(f, j); bw0 = w0; bw1 = w1; bw2 = w2;
                     }
                 }
             }

@@ -180,3 +180,28 @@ def test_grouping_backward_against_float64(D, xyz_last):
         pointnet2._group(xyz.clone().requires_grad_(True), centres, feats, idx.to(DEV))
     with pytest.raises(NotImplementedError):
         pointnet2.sample_and_group(4, 0.5, 4, xyz.clone().requires_grad_(True), None)
+
+
+def test_grouping_backward_scales_exactly_with_the_gradient():
+    """The fixed-point unit follows the cloud's largest |gradient|: d_out times 2^k gives feats.grad times 2^k, bit for bit, and an
+    all-zero d_out (a recorded maximum of 0) exact zeros."""
+    from smilify_amd import pointnet2
+
+    B, N, S, K, D = 2, 20, 16, 8, 5
+    g = torch.Generator().manual_seed(D)
+    xyz, centres = torch.randn(B, N, 3, generator=g).to(DEV), torch.randn(B, S, 3, generator=g).to(DEV)
+    idx = torch.randint(0, N - 1, (B, S, K), generator=g)
+    idx[0, 3] = 7  # a row of K duplicates
+    d_out = torch.randn(B, 3 + D, K, S, generator=g) * torch.exp2(torch.randint(-6, 7, (B, 3 + D, K, S), generator=g).float())
+
+    def grad(d):
+        feats = torch.randn(B, N, D, generator=torch.Generator().manual_seed(1)).to(DEV).requires_grad_(True)
+        pointnet2._group(xyz, centres, feats, idx.to(DEV), False).backward(d.to(DEV))
+        return feats.grad.cpu()
+
+    base = grad(d_out)
+    assert base.abs().sum() > 0
+    for k in (-40, 0, 40):
+        assert torch.equal(grad(d_out * 2.0 ** k), base * 2.0 ** k), k
+    zero = grad(torch.zeros_like(d_out))
+    assert torch.equal(zero, torch.zeros_like(zero))

@@ -262,3 +262,28 @@ def test_sampler_gradient_sums_duplicates_deterministically():
         np.add.at(mag, i, probe[n].double().abs().numpy())
         assert (np.abs(grads[0][n].double().cpu().numpy() - want) <= 8 * U * mag).all()
     assert len(set(idx[0].tolist())) == 6  # (every vertex of the small mesh is drawn many times)
+
+
+def test_sampler_gradient_scales_exactly_with_the_probe():
+    """The fixed-point unit follows the mesh's largest |component|: a probe times 2^k gives the gradients times 2^k, bit for bit,
+    and an all-zero probe (a recorded maximum of 0) exact zeros."""
+    from smilify_amd import fit3d
+    from smilify_amd.mesh3d import Meshes
+
+    verts, vals, off = _sampler_inputs()
+    S = 257
+    vl = [verts[:6].to(DEV).requires_grad_(True), verts[6:].to(DEV).requires_grad_(True)]
+    meshes = Meshes(vl, [torch.zeros(1, 3, dtype=torch.int64, device=DEV)] * 2)
+    probe = torch.randn(2, S, 3, generator=torch.Generator().manual_seed(2)) * torch.tensor([1.0, 2.0 ** -12]).view(2, 1, 1)
+
+    def grads(p):
+        pts, _, _ = fit3d.sample_vertices_with_index(meshes, [vals[:6], vals[6:]], S, seed=77)
+        return torch.autograd.grad((pts * p.to(DEV)).sum(), vl)
+
+    base = grads(probe)
+    assert all(g.abs().sum() > 0 for g in base)
+    for k in (-40, 0, 40):
+        for g, b in zip(grads(probe * 2.0 ** k), base):
+            assert torch.equal(g, b * 2.0 ** k), k
+    for g in grads(torch.zeros_like(probe)):
+        assert torch.equal(g, torch.zeros_like(g))
