@@ -246,7 +246,8 @@ def lbs_forward(model: DeviceModel, beta, theta, trans=None, logscale=None, btra
                 v_template=None, Rs_in=None, shared_beta=False, logscale_shared=False, btrans_shared=False,
                 propagate_scaling=False, allow_limb_scaling=True, trans_after_joints=False, theta_mask=None,
                 project: Optional[Dict] = None) -> Dict[str, torch.Tensor]:
-    """``theta_mask`` (J,3): the kernels use ``theta * mask`` without a masked copy being made (SMALFitter's rotation masks).
+    """``theta_mask`` (J,3): the kernels use ``theta * mask`` without a masked copy being made (SMALFitter's rotation masks);
+    ``lbs_backward`` then returns ``d_theta`` as the gradient on ``theta * mask`` (``fit_epilogue`` multiplies it by the mask).
     ``project`` = ``dict(cams=CameraSet, ndc=bool, yx=bool)``: the vertices / joints are also projected through the cameras
     (``smil_lbs_forward_project``: one kernel per frame with skinning and joint regression); the result carries ``ndc`` (N,V,3)
     and / or ``yx`` (N,J,2)."""

@@ -91,6 +91,9 @@ def run_case(seed, wide=False, big=False, table=None):
     N = B * views
     d_ndc = (1e-3 * torch.randn(N, V, 2, generator=g)).to(DEV)
     d_yx = (1e-2 * torch.randn(N, J, 2, generator=g)).to(DEV)
+    if use_mask:  # (J,3) zeros and ones: the kernels use theta * mask, the oracle is given the masked pose (drawn last: the other inputs keep their values)
+        host["mask"] = (torch.rand(J, 3, generator=g) < 0.6).float()
+        kw["theta_mask"] = host["mask"].to(DEV)
     ok_sup = eng.lbs_backward_ndc_supported(dm, nB, views)
     # --- HIP, fused and separate
     ref = eng.lbs_forward(dm, dev["beta"], dev["theta"], **kw)
@@ -113,10 +116,12 @@ def run_case(seed, wide=False, big=False, table=None):
         checks.append(close(fov_a, fov_b, 3e-5, "bwd fov"))
     # --- the oracle's autograd through LBS + projection on the same upstream gradients
     m = oracle_model(t)
-    leaves = {k: v.clone().requires_grad_() for k, v in host.items()}
+    leaves = {k: v.clone().requires_grad_() for k, v in host.items() if k != "mask"}
+    theta_o = leaves["theta"] * host["mask"] if use_mask else leaves["theta"]
+    theta_o.retain_grad()  # (lbs_backward's d_theta is the gradient on theta * mask: fit_epilogue applies the mask to it)
     beta_o = leaves["beta"][None].expand(B, -1) if shared_beta else leaves["beta"]
     ls_o = leaves["ls"][None].expand(B, -1, -1) if ls_shared else leaves["ls"]
-    o = lbs_ref.smal_forward(m, beta_o, leaves["theta"], trans=None if trans_after else leaves["trans"], betas_logscale=ls_o,
+    o = lbs_ref.smal_forward(m, beta_o, theta_o, trans=None if trans_after else leaves["trans"], betas_logscale=ls_o,
                              betas_trans=leaves["bt"][None].expand(B, -1, -1))
     vo, jo = o["verts"], o["joints"]
     if trans_after:
@@ -130,7 +135,7 @@ def run_case(seed, wide=False, big=False, table=None):
     checks.append(close(got["ndc"].cpu(), ndc_o.detach(), 2e-5, "oracle ndc"))
     for k, n in (("d_beta", "beta"), ("d_theta", "theta"), ("d_trans", "trans"), ("d_logscale", "ls"), ("d_btrans", "bt")):
         if src[k] is not None and src[k].numel():
-            checks.append(close(src[k].cpu(), leaves[n].grad, 5e-4, "oracle " + k))
+            checks.append(close(src[k].cpu(), theta_o.grad if n == "theta" else leaves[n].grad, 5e-4, "oracle " + k))
     info = dict(V=V, J=J, nB=nB, static=int(t.static_joints), B=B, views=views, shared_beta=int(shared_beta), trans_after=int(trans_after),
-                fused_bwd=int(ok_sup))
+                fused_bwd=int(ok_sup), mask=int(use_mask))
     return checks, info
