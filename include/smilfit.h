@@ -538,6 +538,35 @@ size_t smil_group_points_backward_workspace_bytes(int32_t B, int32_t N, int32_t 
 int smil_group_points_backward(const float *d_out, const int32_t *idx, int32_t B, int32_t N, int32_t S, int32_t K, int32_t D,
                                int32_t has_xyz, int32_t xyz_last, float *d_features, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Multi-view keypoint triangulation (smilify_amd/csrc/triangulate.hip).  Replaces the loop of triangulate_all and the functions it
+ * calls in the reference's smal_fitter/sleap_data/triangulate_3d_points.py (:156-301, :830-978).  float64 throughout; one wave per
+ * (frame, keypoint) problem; deterministic.  Sizes, limits and pointers are checked, in that order, before anything is launched.
+ * ---------------------------------------------------------------------------------------- */
+#define SMIL_TRI_MAX_VIEWS 32        /* cameras: the 2 C rows of a problem's system are the lanes of one wave */
+#define SMIL_TRI_MAX_HYP 50          /* pair hypotheses of one problem (the reference's max_hypotheses) */
+#define SMIL_TRI_RANSAC 1            /* mode bit: pair RANSAC where a problem has >= 3 valid views (use_ransac) */
+#define SMIL_TRI_KEEP_ALL_VIEWS 2    /* mode bit: no view filter, every camera is a valid view (the single-point functions) */
+/* P (C,3,4) projection matrices; K (C,3,3) and dist (C,5) = (k1,k2,p1,p2,k3), both or neither: with them the observations of a
+ * camera whose coefficients are not all within 1e-8 of zero are undistorted first (normalise by fx, fy, cx, cy; five rounds of
+ * x <- (x0 - tangential(x)) / radial(x); back through K).  obs (N,Kp,C,2) pixel (x, y), scores (N,Kp,C) or NULL.
+ * A view is dropped when a coordinate is NaN, when its score is not NaN and < confidence_threshold, or when it is exactly (0, 0);
+ * n views remain, numbered in camera order.  status (N,Kp): 0 triangulated, 1 n < min_views, 2 no hypothesis reached min_views
+ * inliers.  mode & SMIL_TRI_RANSAC and n >= 3: the hypotheses are the pairs pairs[n][0 .. min(n (n - 1) / 2, SMIL_TRI_MAX_HYP))
+ * (pairs: (SMIL_TRI_MAX_VIEWS + 1, SMIL_TRI_MAX_HYP, 2) int32 view numbers, row n for n views, made by the caller); each is
+ * triangulated from its two views, a view is its inlier when the reprojection error is < reproj_threshold, the lowest-index
+ * hypothesis of the largest count wins and its inliers are triangulated again.  Otherwise all n views are.  A triangulation is the
+ * right singular vector X of the smallest singular value of the rows x P[2] - P[0], y P[2] - P[1]; xyz (N,Kp,3) = X[:3] / X[3]
+ * (X[3] = 0 and non-finite values propagate by IEEE arithmetic), NaN for status != 0.  views_used (N,Kp): the views of the final
+ * system (0 for status != 0); mean_err (N,Kp): the mean reprojection error of xyz over all n views; view_err (N,Kp,C) or NULL: the
+ * error per camera, NaN for a dropped view; inlier_mask (N,Kp) or NULL: bit c set when camera c is in the final system;
+ * obs_undistorted (N,Kp,C,2) or NULL: the points of the valid views as they enter the systems (dropped views are not written).
+ * C > SMIL_TRI_MAX_VIEWS: SMIL_E_UNSUPPORTED.  min_views >= 1. */
+int smil_triangulate(const double *P, const double *K, const double *dist, const double *obs, const double *scores, const int32_t *pairs,
+                     int64_t N, int32_t Kp, int32_t C, double confidence_threshold, int32_t min_views, double reproj_threshold,
+                     int32_t mode, double *xyz, int32_t *status, int32_t *views_used, double *mean_err, double *view_err,
+                     uint32_t *inlier_mask, double *obs_undistorted, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

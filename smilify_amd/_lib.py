@@ -26,6 +26,7 @@ EXPORTS = [
     "smil_sample_vertices_backward_workspace_bytes", "smil_sample_vertices_backward",
     "smil_ray_diameters_workspace_bytes", "smil_ray_diameters",
     "smil_fps", "smil_ball_query", "smil_group_points", "smil_group_points_backward_workspace_bytes", "smil_group_points_backward",
+    "smil_triangulate",
 ]
 
 N_OBJS = 10
@@ -101,6 +102,9 @@ KNN_MAX_K = 64  # SMIL_KNN_MAX_K
 FPS_MAX_N = 16384  # SMIL_FPS_MAX_N
 BALL_MAX_RADII = 4  # SMIL_BALL_MAX_RADII
 E_UNSUPPORTED = -3  # SMIL_E_UNSUPPORTED
+TRI_MAX_VIEWS = 32  # SMIL_TRI_MAX_VIEWS
+TRI_MAX_HYP = 50  # SMIL_TRI_MAX_HYP
+TRI_RANSAC, TRI_KEEP_ALL_VIEWS = 1, 2  # SMIL_TRI_RANSAC, SMIL_TRI_KEEP_ALL_VIEWS
 
 _lib = None
 
@@ -194,6 +198,7 @@ def load():
     lib.smil_group_points_backward_workspace_bytes.argtypes = [c_int32] * 3
     lib.smil_group_points_backward_workspace_bytes.restype = c_size_t
     lib.smil_group_points_backward.argtypes = [c_void_p, c_void_p] + [c_int32] * 7 + [c_void_p, c_void_p, c_void_p]
+    lib.smil_triangulate.argtypes = [c_void_p] * 6 + [c_int64, c_int32, c_int32, c_double, c_int32, c_double, c_int32] + [c_void_p] * 8
     lib.smil_profile_enable.argtypes = [c_int32]
     lib.smil_profile_read.argtypes = [POINTER(c_float), POINTER(c_int32)]
     for name in EXPORTS:

@@ -156,6 +156,21 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+__device__ __forceinline__ int wave_max(int v) {
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// float64 (triangulate.hip): the value of a lane, and the sum over the 64 lanes as a butterfly.  Both partners of an exchange add
+// the same two numbers, so every lane ends with the same bits and the result depends on nothing but the values.
+__device__ __forceinline__ double read_lane(double v, int lane) {
+    return __builtin_bit_cast(double, read_lane(__builtin_bit_cast(unsigned long long, v), lane));
+}
+__device__ __forceinline__ double wave_sum(double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
 // Block-wide sum for blocks of up to 1024 threads; result valid in thread 0 (and all threads of wave 0).
 __device__ __forceinline__ float block_sum(float v, float *smem /* >= 16 floats */) {
     v = wave_sum(v);

@@ -949,3 +949,52 @@ def group_points_backward(d_out: torch.Tensor, idx: torch.Tensor, N: int, D: int
     _lib.check(lib.smil_group_points_backward(_ptr(d_out), _ptr(idx), B, N, S, K, D, int(bool(has_xyz)), int(bool(xyz_last)), _ptr(d_feat),
                                               _ptr(ws), _stream()), "smil_group_points_backward")
     return d_feat
+
+
+def triangulate(P: torch.Tensor, obs: torch.Tensor, scores: Optional[torch.Tensor], pairs: Optional[torch.Tensor], *,
+                K: Optional[torch.Tensor] = None, dist: Optional[torch.Tensor] = None, confidence_threshold: float = 0.3,
+                min_views: int = 2, reproj_threshold: float = 15.0, mode: int = _lib.TRI_RANSAC, want_view_err: bool = False,
+                want_inlier_mask: bool = False, want_undistorted: bool = False):
+    """DLT / pair-RANSAC triangulation of obs (N,Kp,C,2) float64 through P (C,3,4) float64 (smil_triangulate, include/smilfit.h):
+    ``(xyz (N,Kp,3), status (N,Kp) int32, views_used (N,Kp) int32, mean_err (N,Kp), view_err (N,Kp,C) or None, inlier_mask (N,Kp)
+    int32 bits or None, obs_undistorted (N,Kp,C,2) or None: NaN for a dropped view)``.  scores (N,Kp,C) or None; K (C,3,3) and dist (C,5) together or not at all; pairs: the hypothesis table
+    (SMIL_TRI_MAX_VIEWS + 1, SMIL_TRI_MAX_HYP, 2) int32, needed with ``mode & TRI_RANSAC``.  ValueError above SMIL_TRI_MAX_VIEWS."""
+    if obs.dim() != 4 or obs.shape[3] != 2 or obs.dtype != torch.float64:
+        raise ValueError("triangulate: obs must be a float64 tensor (N, Kp, C, 2)")
+    require_gpu(obs.device)
+    N, Kp, C = (int(v) for v in obs.shape[:3])
+    if C > _lib.TRI_MAX_VIEWS:
+        raise ValueError(f"triangulate: C={C} cameras above SMIL_TRI_MAX_VIEWS={_lib.TRI_MAX_VIEWS}")
+    if min(N, Kp, C) < 1 or int(min_views) < 1:
+        raise ValueError(f"triangulate: bad sizes N={N} Kp={Kp} C={C} min_views={min_views}")
+
+    def f64(name, t, shape):
+        if t is None:
+            return None
+        if t.dtype != torch.float64 or tuple(t.shape) != shape or t.device != obs.device:
+            raise ValueError(f"triangulate: {name} must be a float64 tensor {shape} on {obs.device}")
+        return t.contiguous()
+
+    P, K, dist = f64("P", P, (C, 3, 4)), f64("K", K, (C, 3, 3)), f64("dist", dist, (C, 5))
+    scores = f64("scores", scores, (N, Kp, C))
+    if P is None or (K is None) != (dist is None):
+        raise ValueError("triangulate: P is required, and K and dist come together")
+    if mode & _lib.TRI_RANSAC:
+        if pairs is None or pairs.dtype != torch.int32 or tuple(pairs.shape) != (_lib.TRI_MAX_VIEWS + 1, _lib.TRI_MAX_HYP, 2) \
+                or pairs.device != obs.device:
+            raise ValueError("triangulate: RANSAC needs the int32 pair table (SMIL_TRI_MAX_VIEWS + 1, SMIL_TRI_MAX_HYP, 2)")
+        pairs = pairs.contiguous()
+    obs = obs.contiguous()
+    dev = obs.device
+    xyz = torch.empty(N, Kp, 3, device=dev, dtype=torch.float64)
+    status = torch.empty(N, Kp, device=dev, dtype=torch.int32)
+    used = torch.empty(N, Kp, device=dev, dtype=torch.int32)
+    mean_err = torch.empty(N, Kp, device=dev, dtype=torch.float64)
+    view_err = torch.empty(N, Kp, C, device=dev, dtype=torch.float64) if want_view_err else None
+    mask = torch.empty(N, Kp, device=dev, dtype=torch.int32) if want_inlier_mask else None
+    undist = torch.full((N, Kp, C, 2), float("nan"), device=dev, dtype=torch.float64) if want_undistorted else None
+    _lib.check(_lib.load().smil_triangulate(_ptr(P), _ptr(K), _ptr(dist), _ptr(obs), _ptr(scores), _ptr(pairs), N, Kp, C,
+                                            float(confidence_threshold), int(min_views), float(reproj_threshold), int(mode), _ptr(xyz),
+                                            _ptr(status), _ptr(used), _ptr(mean_err), _ptr(view_err), _ptr(mask), _ptr(undist), _stream()),
+               "smil_triangulate")
+    return xyz, status, used, mean_err, view_err, mask, undist
