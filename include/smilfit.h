@@ -567,6 +567,44 @@ int smil_triangulate(const double *P, const double *K, const double *dist, const
                      int32_t mode, double *xyz, int32_t *status, int32_t *views_used, double *mean_err, double *view_err,
                      uint32_t *inlier_mask, double *obs_undistorted, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Multi-view camera refinement (smilify_amd/csrc/refine.hip).  Replaces optimize_camera and reprojection_residuals of the reference's
+ * smal_fitter/sleap_data/refine_camera_params.py (:143-226): every camera's parameters (rvec 3, t 3, fx, fy, cx, cy) are fitted to
+ * its own 3-D / 2-D correspondences, all cameras in one call.  float64 throughout; deterministic (no atomics).
+ * The cost is scipy's loss="soft_l1" on every scalar residual f (projected - observed, x and y): z = (f / f_scale)^2,
+ * cost = 0.5 f_scale^2 sum 2 (sqrt(1 + z) - 1), weight w = 1 / sqrt(1 + z), g = J^T (w f), H = J^T diag(w) J with the analytic
+ * Jacobian J.  The projection is u = fx x / z + cx, v = fy y / z + cy of (x, y, z) = Rodrigues(rvec) X + t; z <= 0 divides as IEEE does.
+ * Correspondences are packed: camera c owns rows offsets[c] .. offsets[c + 1] of pts_3d (sum M, 3) and pts_2d (sum M, 2).  The
+ * offset table (C + 1, int64) is passed twice, as a HOST array (checked here, sizes the launch) and as the same values on the device.
+ * n_params = 6 fits rvec and t and keeps the four intrinsics of the initial parameters; 10 fits all.  Parameter arrays are (C,10).
+ * Arguments are checked, in the order C, n_params, f_scale, offsets / workspace, monotone offsets, points, (max_steps), the other
+ * pointers, before a device is touched.
+ * ---------------------------------------------------------------------------------------- */
+#define SMIL_REFINE_MIN_POINTS 20    /* a camera with fewer correspondences is skipped (reference :181-184) */
+#define SMIL_REFINE_CONVERGED 0      /* status: an accepted step lowered the cost by < 1e-12 cost, or lambda passed 1e12 */
+#define SMIL_REFINE_STEP_LIMIT 1     /*         max_steps evaluations without that */
+#define SMIL_REFINE_SKIPPED 2        /*         fewer than SMIL_REFINE_MIN_POINTS correspondences: parameters returned unchanged */
+#define SMIL_REFINE_NONFINITE 3      /*         the cost of the initial parameters is not finite: parameters returned unchanged */
+size_t smil_refine_workspace_bytes(int32_t C, int64_t max_count); /* max_count: the largest correspondence count of a camera */
+/* One accumulation at params (C,10): cost (C), g (C,10), H (C,10,10) symmetric; entries outside the n_params block are zero.  Every
+ * camera is evaluated, whatever its count (none: zeros). */
+int smil_refine_evaluate(const double *pts_3d, const double *pts_2d, const int64_t *offsets_host, const int64_t *offsets_dev, int32_t C,
+                         const double *params, int32_t n_params, double f_scale, double *cost, double *g, double *H, void *workspace,
+                         void *stream);
+/* Levenberg-Marquardt from params0 (C,10), lambda = 1e-3 at the start.  Every (accumulate, step) pair evaluates each camera's candidate
+ * and then, per camera: accept when the cost is finite and below the current one (the candidate, its g and H are taken over,
+ * lambda <- max(lambda / 10, 1e-12)), else reject (lambda <- 10 lambda); the next candidate is current + delta with
+ * (H + lambda diag H) delta = -g by Cholesky.  A factorisation that fails or a non-finite delta gives no step: lambda <- 10 lambda and
+ * the candidate is the current point, which the next pair rejects.  A camera is done when an accepted step lowered the cost by less
+ * than 1e-12 of it or when lambda > 1e12; its later launches do nothing.  At most max_steps pairs are enqueued, the first of which
+ * evaluates params0 itself.  Outputs per camera: params (C,10), status (SMIL_REFINE_*), n_accepted (accepted steps), n_trials
+ * (evaluations, the first included), cost0 and cost (initial and final; NaN for a skipped camera), g (C,10) at params.
+ * UNLIKE the rest of this header the call synchronises `stream`: it reads the done flags every 8 pairs and stops enqueuing once
+ * every camera is done.  It must not be captured into a graph. */
+int smil_refine_cameras(const double *pts_3d, const double *pts_2d, const int64_t *offsets_host, const int64_t *offsets_dev, int32_t C,
+                        const double *params0, int32_t n_params, double f_scale, int32_t max_steps, double *params, int32_t *status,
+                        int32_t *n_accepted, int32_t *n_trials, double *cost0, double *cost, double *g, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -998,3 +998,53 @@ def triangulate(P: torch.Tensor, obs: torch.Tensor, scores: Optional[torch.Tenso
                                             _ptr(status), _ptr(used), _ptr(mean_err), _ptr(view_err), _ptr(mask), _ptr(undist), _stream()),
                "smil_triangulate")
     return xyz, status, used, mean_err, view_err, mask, undist
+
+
+def _refine_inputs(who, pts_3d, pts_2d, offsets, params, n_params, f_scale):
+    """Shared checks of the two refinement entry points; offsets is a host int64 array (C + 1).  Returns the contiguous tensors, the
+    device copy of the offsets and a workspace."""
+    offsets = np.ascontiguousarray(offsets, np.int64)
+    if offsets.ndim != 1 or len(offsets) < 2 or offsets[0] != 0 or (np.diff(offsets) < 0).any():
+        raise ValueError(f"{who}: offsets must be a non-decreasing int64 table (C + 1) that starts at 0")
+    C, total = len(offsets) - 1, int(offsets[-1])
+    require_gpu(params.device)
+    for name, t, shape in (("pts_3d", pts_3d, (total, 3)), ("pts_2d", pts_2d, (total, 2)), ("params", params, (C, 10))):
+        if t.dtype != torch.float64 or tuple(t.shape) != shape or t.device != params.device:
+            raise ValueError(f"{who}: {name} must be a float64 tensor {shape} on {params.device}")
+    if int(n_params) not in (6, 10) or not float(f_scale) > 0.0:
+        raise ValueError(f"{who}: n_params={n_params} must be 6 or 10 and f_scale={f_scale} positive")
+    lib = _lib.load()
+    ws = torch.empty(int(lib.smil_refine_workspace_bytes(C, int(np.diff(offsets).max()))), dtype=torch.uint8, device=params.device)
+    return pts_3d.contiguous(), pts_2d.contiguous(), params.contiguous(), offsets, torch.from_numpy(offsets).to(params.device), C, ws
+
+
+def refine_evaluate(pts_3d: torch.Tensor, pts_2d: torch.Tensor, offsets, params: torch.Tensor, *, n_params: int = 10,
+                    f_scale: float = 5.0):
+    """One accumulation of the camera refinement (smil_refine_evaluate, include/smilfit.h) at params (C,10) float64 over the packed
+    correspondences pts_3d (sum M,3), pts_2d (sum M,2) with the host table offsets (C+1): ``(cost (C), g (C,10), H (C,10,10))``."""
+    pts_3d, pts_2d, params, offsets, off_dev, C, ws = _refine_inputs("refine_evaluate", pts_3d, pts_2d, offsets, params, n_params, f_scale)
+    dev = params.device
+    cost = torch.empty(C, device=dev, dtype=torch.float64)
+    g = torch.empty(C, 10, device=dev, dtype=torch.float64)
+    H = torch.empty(C, 10, 10, device=dev, dtype=torch.float64)
+    _lib.check(_lib.load().smil_refine_evaluate(_ptr(pts_3d), _ptr(pts_2d), offsets.ctypes.data, _ptr(off_dev), C, _ptr(params), int(n_params),
+                                                float(f_scale), _ptr(cost), _ptr(g), _ptr(H), _ptr(ws), _stream()), "smil_refine_evaluate")
+    return cost, g, H
+
+
+def refine_cameras(pts_3d: torch.Tensor, pts_2d: torch.Tensor, offsets, params0: torch.Tensor, *, n_params: int = 10, f_scale: float = 5.0,
+                   max_steps: int = 100):
+    """Robust Levenberg-Marquardt of every camera's parameters (smil_refine_cameras, include/smilfit.h): ``(params (C,10), status (C)
+    int32, n_accepted (C) int32, n_trials (C) int32, cost0 (C), cost (C), g (C,10))``.  Synchronises the current stream."""
+    if int(max_steps) < 1:
+        raise ValueError(f"refine_cameras: max_steps={max_steps} must be >= 1")
+    pts_3d, pts_2d, params0, offsets, off_dev, C, ws = _refine_inputs("refine_cameras", pts_3d, pts_2d, offsets, params0, n_params, f_scale)
+    dev = params0.device
+    params = torch.empty(C, 10, device=dev, dtype=torch.float64)
+    status, n_acc, n_trial = (torch.empty(C, device=dev, dtype=torch.int32) for _ in range(3))
+    cost0, cost = (torch.empty(C, device=dev, dtype=torch.float64) for _ in range(2))
+    g = torch.empty(C, 10, device=dev, dtype=torch.float64)
+    _lib.check(_lib.load().smil_refine_cameras(_ptr(pts_3d), _ptr(pts_2d), offsets.ctypes.data, _ptr(off_dev), C, _ptr(params0), int(n_params),
+                                               float(f_scale), int(max_steps), _ptr(params), _ptr(status), _ptr(n_acc), _ptr(n_trial),
+                                               _ptr(cost0), _ptr(cost), _ptr(g), _ptr(ws), _stream()), "smil_refine_cameras")
+    return params, status, n_acc, n_trial, cost0, cost, g
