@@ -605,6 +605,44 @@ int smil_refine_cameras(const double *pts_3d, const double *pts_2d, const int64_
                         const double *params0, int32_t n_params, double f_scale, int32_t max_steps, double *params, int32_t *status,
                         int32_t *n_accepted, int32_t *n_trials, double *cost0, double *cost, double *g, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Robust nonlinear refinement of triangulated points (smilify_amd/csrc/refine_points.hip).  AN EXTENSION: the reference has no such
+ * function, its points stay the DLT points of triangulate_point_dlt.  Every (frame, keypoint) point is moved from xyz0 to the minimum
+ * of the robust reprojection cost over its views, all points in one call: the point half of a bundle adjustment whose camera half is
+ * smil_refine_cameras.  float64 throughout; one wave per problem; deterministic (no atomics), and a problem's result does not depend
+ * on its place in the batch or on the batch size.
+ * Inputs in the layouts smil_triangulate produces: P (C,3,4); obs (N,Kp,C,2) undistorted pixels (its obs_undistorted); view_mask
+ * (N,Kp) with bit c set when camera c is a view of the problem (its inlier_mask; bits from C up are ignored); xyz0 (N,Kp,3).  The
+ * observation of a view outside the mask is never read: it may be unwritten, NaN or garbage.  C <= SMIL_TRI_MAX_VIEWS.
+ * For view c with h = P_c (X, 1) the two scalar residuals are f = (h0 / h2 - x, h1 / h2 - y) (h2 <= 0 divides as IEEE does) and their
+ * Jacobian rows (P_c[k,:3] - (h_k / h2) P_c[2,:3]) / h2.  Cost, w, g = J^T (w f) and H = J^T diag(w) J are exactly those defined for
+ * smil_refine_cameras above (scipy's soft_l1 on every scalar residual, the cost term written 2 z / (sqrt(1 + z) + 1)), with J 2n x 3.
+ * Arguments are checked, in the order C, f_scale, N and Kp, (max_steps), the pointers, before a device is touched: C < 1, a
+ * non-positive or non-finite f_scale, a negative N or Kp, max_steps < 1 or a null required pointer is SMIL_E_INVALID,
+ * C > SMIL_TRI_MAX_VIEWS is SMIL_E_UNSUPPORTED; a call with N Kp = 0 succeeds and launches nothing.  Both entry points are asynchronous
+ * on `stream` and need no workspace.
+ * ---------------------------------------------------------------------------------------- */
+#define SMIL_REFINE_POINTS_FEW_VIEWS 2 /* status: fewer than 2 views in the mask: xyz returned unchanged (0, 1 and 3 are SMIL_REFINE_CONVERGED,
+                                          SMIL_REFINE_STEP_LIMIT and SMIL_REFINE_NONFINITE: a non-finite cost at xyz0, which includes a NaN
+                                          xyz0 of a failed triangulation: xyz returned unchanged) */
+/* One accumulation at xyz (N,Kp,3): cost (N,Kp), g (N,Kp,3), H (N,Kp,3,3) symmetric.  Every problem is evaluated, whatever its views
+ * (none: zeros). */
+int smil_refine_points_evaluate(const double *P, const double *obs, const uint32_t *view_mask, const double *xyz, int64_t N, int32_t Kp,
+                                int32_t C, double f_scale, double *cost, double *g, double *H, void *stream);
+/* Levenberg-Marquardt per problem, the loop of smil_refine_cameras rule for rule: lambda = 1e-3 at the start; a candidate is accepted iff
+ * its cost is finite and below the current one (lambda <- max(lambda / 10, 1e-12)), else rejected (lambda <- 10 lambda); the next
+ * candidate is current + delta with (H + lambda diag H) delta = -g by a 3 x 3 Cholesky; a factorisation that fails or a non-finite
+ * delta gives no step and lambda <- 10 lambda; a problem is done when an accepted step lowers the cost by less than 1e-12 of it or
+ * when lambda > 1e12.  The first of the at most max_steps evaluations is of xyz0.
+ * UNLIKE smil_refine_cameras the loop runs INSIDE the kernel, bounded by max_steps: the problems are independent and there may be
+ * millions of them, so nothing is gained by a launch per step, the call does not synchronise and it may be captured into a graph.
+ * Outputs per problem: xyz (N,Kp,3), status, n_accepted (accepted steps), n_trials (evaluations, the first included; 0 for
+ * SMIL_REFINE_POINTS_FEW_VIEWS), cost0 and cost (initial and final; NaN for SMIL_REFINE_POINTS_FEW_VIEWS), view_err (N,Kp,C) or NULL:
+ * the reprojection error sqrt(f_x^2 + f_y^2) of the returned xyz per view of the mask, NaN for a view outside it. */
+int smil_refine_points(const double *P, const double *obs, const uint32_t *view_mask, const double *xyz0, int64_t N, int32_t Kp, int32_t C,
+                       double f_scale, int32_t max_steps, double *xyz, int32_t *status, int32_t *n_accepted, int32_t *n_trials,
+                       double *cost0, double *cost, double *view_err, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

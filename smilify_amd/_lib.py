@@ -28,6 +28,7 @@ EXPORTS = [
     "smil_fps", "smil_ball_query", "smil_group_points", "smil_group_points_backward_workspace_bytes", "smil_group_points_backward",
     "smil_triangulate",
     "smil_refine_workspace_bytes", "smil_refine_evaluate", "smil_refine_cameras",
+    "smil_refine_points_evaluate", "smil_refine_points",
 ]
 
 N_OBJS = 10
@@ -108,6 +109,7 @@ TRI_MAX_HYP = 50  # SMIL_TRI_MAX_HYP
 TRI_RANSAC, TRI_KEEP_ALL_VIEWS = 1, 2  # SMIL_TRI_RANSAC, SMIL_TRI_KEEP_ALL_VIEWS
 REFINE_MIN_POINTS = 20  # SMIL_REFINE_MIN_POINTS
 REFINE_CONVERGED, REFINE_STEP_LIMIT, REFINE_SKIPPED, REFINE_NONFINITE = 0, 1, 2, 3  # SMIL_REFINE_*
+REFINE_POINTS_FEW_VIEWS = 2  # SMIL_REFINE_POINTS_FEW_VIEWS
 
 _lib = None
 
@@ -206,6 +208,8 @@ def load():
     lib.smil_refine_workspace_bytes.restype = c_size_t
     lib.smil_refine_evaluate.argtypes = [c_void_p] * 4 + [c_int32, c_void_p, c_int32, c_double] + [c_void_p] * 5
     lib.smil_refine_cameras.argtypes = [c_void_p] * 4 + [c_int32, c_void_p, c_int32, c_double, c_int32] + [c_void_p] * 9
+    lib.smil_refine_points_evaluate.argtypes = [c_void_p] * 4 + [c_int64, c_int32, c_int32, c_double] + [c_void_p] * 4
+    lib.smil_refine_points.argtypes = [c_void_p] * 4 + [c_int64, c_int32, c_int32, c_double, c_int32] + [c_void_p] * 8
     lib.smil_profile_enable.argtypes = [c_int32]
     lib.smil_profile_read.argtypes = [POINTER(c_float), POINTER(c_int32)]
     for name in EXPORTS:

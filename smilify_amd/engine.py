@@ -1048,3 +1048,52 @@ def refine_cameras(pts_3d: torch.Tensor, pts_2d: torch.Tensor, offsets, params0:
                                                float(f_scale), int(max_steps), _ptr(params), _ptr(status), _ptr(n_acc), _ptr(n_trial),
                                                _ptr(cost0), _ptr(cost), _ptr(g), _ptr(ws), _stream()), "smil_refine_cameras")
     return params, status, n_acc, n_trial, cost0, cost, g
+
+
+def _refine_points_inputs(who, P, obs, view_mask, xyz, f_scale):
+    """Shared checks of the two point refinement entry points.  Returns the contiguous tensors and N, Kp, C."""
+    if obs.dim() != 4 or obs.shape[3] != 2 or obs.dtype != torch.float64:
+        raise ValueError(f"{who}: obs must be a float64 tensor (N, Kp, C, 2)")
+    require_gpu(obs.device)
+    N, Kp, C = (int(v) for v in obs.shape[:3])
+    if not 1 <= C <= _lib.TRI_MAX_VIEWS:
+        raise ValueError(f"{who}: C={C} cameras outside 1 .. SMIL_TRI_MAX_VIEWS={_lib.TRI_MAX_VIEWS}")
+    for name, t, shape in (("P", P, (C, 3, 4)), ("xyz", xyz, (N, Kp, 3))):
+        if t.dtype != torch.float64 or tuple(t.shape) != shape or t.device != obs.device:
+            raise ValueError(f"{who}: {name} must be a float64 tensor {shape} on {obs.device}")
+    if view_mask.dtype != torch.int32 or tuple(view_mask.shape) != (N, Kp) or view_mask.device != obs.device:
+        raise ValueError(f"{who}: view_mask must be an int32 tensor {(N, Kp)} of bits on {obs.device}")
+    if not float(f_scale) > 0.0:
+        raise ValueError(f"{who}: f_scale={f_scale} must be positive")
+    return P.contiguous(), obs.contiguous(), view_mask.contiguous(), xyz.contiguous(), N, Kp, C
+
+
+def refine_points_evaluate(P: torch.Tensor, obs: torch.Tensor, view_mask: torch.Tensor, xyz: torch.Tensor, *, f_scale: float = 5.0):
+    """One accumulation of the point refinement (smil_refine_points_evaluate, include/smilfit.h) at xyz (N,Kp,3) float64 over the views
+    of view_mask (N,Kp) int32 bits of obs (N,Kp,C,2) through P (C,3,4): ``(cost (N,Kp), g (N,Kp,3), H (N,Kp,3,3))``."""
+    P, obs, view_mask, xyz, N, Kp, C = _refine_points_inputs("refine_points_evaluate", P, obs, view_mask, xyz, f_scale)
+    dev = obs.device
+    cost = torch.empty(N, Kp, device=dev, dtype=torch.float64)
+    g = torch.empty(N, Kp, 3, device=dev, dtype=torch.float64)
+    H = torch.empty(N, Kp, 3, 3, device=dev, dtype=torch.float64)
+    _lib.check(_lib.load().smil_refine_points_evaluate(_ptr(P), _ptr(obs), _ptr(view_mask), _ptr(xyz), N, Kp, C, float(f_scale), _ptr(cost),
+                                                       _ptr(g), _ptr(H), _stream()), "smil_refine_points_evaluate")
+    return cost, g, H
+
+
+def refine_points(P: torch.Tensor, obs: torch.Tensor, view_mask: torch.Tensor, xyz0: torch.Tensor, *, f_scale: float = 5.0,
+                  max_steps: int = 50, want_view_err: bool = False):
+    """Robust Levenberg-Marquardt of every point over its views (smil_refine_points, include/smilfit.h): ``(xyz (N,Kp,3), status (N,Kp)
+    int32, n_accepted (N,Kp) int32, n_trials (N,Kp) int32, cost0 (N,Kp), cost (N,Kp), view_err (N,Kp,C) or None)``.  Asynchronous."""
+    if int(max_steps) < 1:
+        raise ValueError(f"refine_points: max_steps={max_steps} must be >= 1")
+    P, obs, view_mask, xyz0, N, Kp, C = _refine_points_inputs("refine_points", P, obs, view_mask, xyz0, f_scale)
+    dev = obs.device
+    xyz = torch.empty(N, Kp, 3, device=dev, dtype=torch.float64)
+    status, n_acc, n_trial = (torch.empty(N, Kp, device=dev, dtype=torch.int32) for _ in range(3))
+    cost0, cost = (torch.empty(N, Kp, device=dev, dtype=torch.float64) for _ in range(2))
+    view_err = torch.empty(N, Kp, C, device=dev, dtype=torch.float64) if want_view_err else None
+    _lib.check(_lib.load().smil_refine_points(_ptr(P), _ptr(obs), _ptr(view_mask), _ptr(xyz0), N, Kp, C, float(f_scale), int(max_steps),
+                                              _ptr(xyz), _ptr(status), _ptr(n_acc), _ptr(n_trial), _ptr(cost0), _ptr(cost), _ptr(view_err),
+                                              _stream()), "smil_refine_points")
+    return xyz, status, n_acc, n_trial, cost0, cost, view_err

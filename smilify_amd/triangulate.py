@@ -82,10 +82,15 @@ def projection_matrix_from_fov_camera(R, T, fov, aspect_ratio=1.0, image_size=51
 
 
 def triangulate_arrays(P, obs, scores=None, K=None, dist=None, confidence_threshold=0.3, min_views=2, reproj_threshold=15.0,
-                       use_ransac=True, keep_all_views=False, device=None) -> Dict[str, np.ndarray]:
+                       use_ransac=True, keep_all_views=False, device=None, refine=False) -> Dict[str, np.ndarray]:
     """The kernel on numpy arrays: P (C,3,4), obs (N,Kp,C,2), scores (N,Kp,C) or None, K (C,3,3) and dist (C,5) or None.  Returns
     ``xyz, status, views_used, mean_err, view_err, inlier_mask`` (uint32, bit c = camera c is in the final system) and
-    ``obs_undistorted`` (the valid views' points as they entered the systems, NaN for a dropped view) as numpy."""
+    ``obs_undistorted`` (the valid views' points as they entered the systems, NaN for a dropped view) as numpy.
+
+    ``refine=True`` (an extension, ``smilify_amd/refine_points.py``): every triangulated point is then moved from the DLT point to the
+    minimum of the soft_l1 reprojection cost over the views of its final system (``inlier_mask``).  ``status``, ``views_used`` and
+    ``inlier_mask`` stay, ``view_err`` and ``mean_err`` are those of the refined point over the same valid views as before, and the
+    dict gains ``refine_status``, ``refine_cost_initial`` and ``refine_cost_final`` (N,Kp)."""
     dev = engine.require_gpu(device or DEFAULT_DEVICE)
     up = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(dev)  # noqa: E731
     mode = (_lib.TRI_RANSAC if use_ransac else 0) | (_lib.TRI_KEEP_ALL_VIEWS if keep_all_views else 0)
@@ -98,8 +103,29 @@ def triangulate_arrays(P, obs, scores=None, K=None, dist=None, confidence_thresh
                              confidence_threshold=confidence_threshold, min_views=min_views, reproj_threshold=reproj_threshold,
                              mode=mode, want_view_err=True, want_inlier_mask=True, want_undistorted=True)
     xyz, status, used, mean_err, view_err, mask, undist = (t.cpu().numpy() for t in out)
-    return dict(xyz=xyz, status=status, views_used=used, mean_err=mean_err, view_err=view_err, inlier_mask=mask.view(np.uint32),
-                obs_undistorted=undist)
+    out = dict(xyz=xyz, status=status, views_used=used, mean_err=mean_err, view_err=view_err, inlier_mask=mask.view(np.uint32),
+               obs_undistorted=undist)
+    if refine:
+        _refine_in_place(np.asarray(P, np.float64).reshape(-1, 3, 4), out, dev)
+    return out
+
+
+def _refine_in_place(P: np.ndarray, out: Dict[str, np.ndarray], device) -> None:
+    """The refined points in place of the DLT points of ``out`` where the refinement ran (status 0 or 1), with their errors."""
+    from . import refine_points as rp
+
+    xyz, st = rp.refine_points_arrays(P, out["obs_undistorted"], out["inlier_mask"], out["xyz"], device=device)
+    moved = (out["status"] == 0) & ((st["status"] == _lib.REFINE_CONVERGED) | (st["status"] == _lib.REFINE_STEP_LIMIT))
+    out.update(refine_status=st["status"], refine_cost_initial=st["cost_initial"], refine_cost_final=st["cost_final"])
+    if not moved.any():
+        return
+    X, und = xyz[moved], out["obs_undistorted"][moved]
+    valid = ~np.isnan(und).any(axis=-1)  # the views that entered the hypotheses: mean_err runs over all of them
+    with np.errstate(all="ignore"):
+        h = np.einsum("cij,mj->mci", P[:, :, :3], X) + P[:, :, 3]
+        err = np.where(valid, np.linalg.norm(h[..., :2] / h[..., 2:3] - und, axis=-1), np.nan)
+    out["xyz"][moved], out["view_err"][moved] = X, err
+    out["mean_err"][moved] = np.where(valid, err, 0.0).sum(axis=-1) / valid.sum(axis=-1)
 
 
 def _one_problem(projections, points_2d):
@@ -176,11 +202,13 @@ def _dist5(dist) -> np.ndarray:
 def triangulate_all(cameras: Dict[str, dict], all_coords: Dict[str, np.ndarray], all_scores: Dict[str, np.ndarray], n_frames: int,
                     n_keypoints: int, confidence_threshold: float = 0.3, min_views: int = 2, reproj_threshold: float = 15.0,
                     undistort: bool = True, use_ransac: bool = True, verbose: bool = True,
-                    frame_indices: Optional[np.ndarray] = None, device=None) -> Tuple[np.ndarray, dict]:
+                    frame_indices: Optional[np.ndarray] = None, device=None, refine: bool = False) -> Tuple[np.ndarray, dict]:
     """Triangulate every keypoint of every frame (:830-978): ``cameras`` name -> {K, dist, R, t}, ``all_coords`` name ->
     (n_frames_cam, n_kp, 2), ``all_scores`` name -> (n_frames_cam, n_kp).  Returns ``tracks_3d (n_out, 1, n_keypoints, 3)`` float64,
     NaN where not triangulated, and the reference's ``stats`` dict.  Cameras are taken in ``sorted(all_coords)`` order; a frame
-    beyond a camera's own frame count is a dropped view."""
+    beyond a camera's own frame count is a dropped view.  ``refine=True`` (an extension): the points are refined as
+    ``triangulate_arrays(refine=True)`` describes, the error statistics are those of the refined points, and the stats gain
+    ``refined``, the number of points that moved."""
     start = time.time()
     names = sorted(all_coords.keys())
     C = len(names)
@@ -209,8 +237,11 @@ def triangulate_all(cameras: Dict[str, dict], all_coords: Dict[str, np.ndarray],
         if undistort:
             K = np.stack([np.asarray(cameras[name].get("K", np.eye(3)), np.float64).reshape(3, 3) for name in names])
             dist = np.stack([_dist5(cameras[name].get("dist")) for name in names])
-        out = triangulate_arrays(P, obs, scores, K, dist, confidence_threshold, min_views, reproj_threshold, use_ransac, device=device)
+        out = triangulate_arrays(P, obs, scores, K, dist, confidence_threshold, min_views, reproj_threshold, use_ransac, device=device,
+                                 refine=refine)
         ok = out["status"] == 0
+        if refine:
+            stats["refined"] = int((ok & (out["refine_status"] <= _lib.REFINE_STEP_LIMIT)).sum())
         tracks_3d[:, 0][ok] = out["xyz"][ok]
         stats["failed_insufficient_views"] = int((out["status"] == 1).sum())
         stats["failed_ransac"] = int((out["status"] == 2).sum())
