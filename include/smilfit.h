@@ -591,13 +591,15 @@ size_t smil_refine_workspace_bytes(int32_t C, int64_t max_count); /* max_count: 
 int smil_refine_evaluate(const double *pts_3d, const double *pts_2d, const int64_t *offsets_host, const int64_t *offsets_dev, int32_t C,
                          const double *params, int32_t n_params, double f_scale, double *cost, double *g, double *H, void *workspace,
                          void *stream);
-/* Levenberg-Marquardt from params0 (C,10), lambda = 1e-3 at the start.  Every (accumulate, step) pair evaluates each camera's candidate
- * and then, per camera: accept when the cost is finite and below the current one (the candidate, its g and H are taken over,
- * lambda <- max(lambda / 10, 1e-12)), else reject (lambda <- 10 lambda); the next candidate is current + delta with
- * (H + lambda diag H) delta = -g by Cholesky.  A factorisation that fails or a non-finite delta gives no step: lambda <- 10 lambda and
- * the candidate is the current point, which the next pair rejects.  A camera is done when an accepted step lowered the cost by less
- * than 1e-12 of it or when lambda > 1e12; its later launches do nothing.  At most max_steps pairs are enqueued, the first of which
- * evaluates params0 itself.  Outputs per camera: params (C,10), status (SMIL_REFINE_*), n_accepted (accepted steps), n_trials
+/* Levenberg-Marquardt from params0 (C,10).  THE RULES, which smil_refine_points below shares (one implementation,
+ * smilify_amd/csrc/lm.h): lambda = 1e-3 at the start.  Every evaluation is of a candidate: accepted when its cost is finite and below
+ * the current one (the candidate, its g and H are taken over, lambda <- max(lambda / 10, 1e-12)), else rejected (lambda <- 10 lambda);
+ * the next candidate is current + delta with (H + lambda diag H) delta = -g by Cholesky.  A factorisation that fails (a pivot that is
+ * not positive and finite) or a non-finite delta gives no step: lambda <- 10 lambda and the candidate is the current point, which the
+ * next evaluation rejects.  Done when an accepted step lowered the cost by less than 1e-12 of it or when lambda > 1e12.  The first
+ * evaluation is of the start itself and must be finite.
+ * Here an evaluation is one enqueued (accumulate, step) pair over all cameras, at most max_steps of them; a done camera's later
+ * launches do nothing.  Outputs per camera: params (C,10), status (SMIL_REFINE_*), n_accepted (accepted steps), n_trials
  * (evaluations, the first included), cost0 and cost (initial and final; NaN for a skipped camera), g (C,10) at params.
  * UNLIKE the rest of this header the call synchronises `stream`: it reads the done flags every 8 pairs and stops enqueuing once
  * every camera is done.  It must not be captured into a graph. */
@@ -629,11 +631,8 @@ int smil_refine_cameras(const double *pts_3d, const double *pts_2d, const int64_
  * (none: zeros). */
 int smil_refine_points_evaluate(const double *P, const double *obs, const uint32_t *view_mask, const double *xyz, int64_t N, int32_t Kp,
                                 int32_t C, double f_scale, double *cost, double *g, double *H, void *stream);
-/* Levenberg-Marquardt per problem, the loop of smil_refine_cameras rule for rule: lambda = 1e-3 at the start; a candidate is accepted iff
- * its cost is finite and below the current one (lambda <- max(lambda / 10, 1e-12)), else rejected (lambda <- 10 lambda); the next
- * candidate is current + delta with (H + lambda diag H) delta = -g by a 3 x 3 Cholesky; a factorisation that fails or a non-finite
- * delta gives no step and lambda <- 10 lambda; a problem is done when an accepted step lowers the cost by less than 1e-12 of it or
- * when lambda > 1e12.  The first of the at most max_steps evaluations is of xyz0.
+/* Levenberg-Marquardt per problem under THE RULES stated at smil_refine_cameras (the same code, with a 3 x 3 system).  The first of
+ * the at most max_steps evaluations is of xyz0.
  * UNLIKE smil_refine_cameras the loop runs INSIDE the kernel, bounded by max_steps: the problems are independent and there may be
  * millions of them, so nothing is gained by a launch per step, the call does not synchronise and it may be captured into a graph.
  * Outputs per problem: xyz (N,Kp,3), status, n_accepted (accepted steps), n_trials (evaluations, the first included; 0 for

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <vector>
@@ -98,6 +99,24 @@ int smil_colour_setup(const SmilModel *m, const float *verts_ndc, int N, int S, 
                       ColourSetup *out);
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// ---- argument checks the multi-view entry points share (triangulate.hip, refine.hip, refine_points.hip); SMIL_OK or the error set ----
+// (`why`: what the caller keeps in the ONE wave that holds a problem's C views)
+static inline int smil_check_views(const char *who, int32_t C, const char *why) {
+    if (C > SMIL_TRI_MAX_VIEWS) {
+        smil_set_error("%s: C=%d above SMIL_TRI_MAX_VIEWS=%d (%s)", who, C, SMIL_TRI_MAX_VIEWS, why);
+        return SMIL_E_UNSUPPORTED;
+    }
+    return SMIL_OK;
+}
+static inline int smil_check_grid(const char *who, int64_t N, int32_t Kp, int waves) {
+    SMIL_REQUIRE(Kp == 0 || N <= (int64_t)0x7FFFFFFF * waves / Kp, "%s: N Kp = %lld x %d problems exceed the grid", who, (long long)N, Kp);
+    return SMIL_OK;
+}
+static inline int smil_check_f_scale(const char *who, double f_scale) {
+    SMIL_REQUIRE(f_scale > 0.0 && std::isfinite(f_scale), "%s: f_scale=%g must be positive and finite", who, f_scale);
+    return SMIL_OK;
+}
 
 // ---- caller-owned workspaces: every region starts on a 256-byte boundary ----
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }

@@ -13,13 +13,14 @@
 //      and d(R X)/d r_k = r_k (a1 p + b1 q) + a e_k x X + b (e_k x p + r x (e_k x X)) with a1 = (cos(th) - a) / th^2 and
 //      b1 = (a - 2 b) / th^2; below th^2 = 1e-3 the four coefficients come from their series, so r = 0 gives R = I and the
 //      generators.  That keeps five coefficients and r in registers instead of four 3 x 3 matrices.
-//  * k_refine_step         one wave per camera.  The lanes add the partials in block order; lane 0 then accepts or rejects the
-//      candidate, solves (H + lambda diag H) delta = -g by a Cholesky factorisation in LDS and writes the next candidate.
+//  * k_refine_step         one wave per camera.  The lanes add the partials in block order; lane 0 then applies lm.h's rules (shared
+//      with refine_points.hip: soft_l1, accept / reject, the Cholesky solve with L and delta in LDS, the statuses) for the next candidate.
 //  * smil_refine_cameras   enqueues at most max_steps (accumulate, step) pairs and reads the done flags every REF_POLL pairs.
 //      There is no device-side loop whose trip count depends on the data and no host read inside a pair.
 #include <cmath>
 
 #include "common.h"
+#include "lm.h"
 
 #define REF_THREADS 256    // lanes of an accumulation workgroup: "one block's worth" of correspondences
 #define REF_MAX_BLOCKS 64  // workgroups per camera at most (200 000 correspondences: 13 per lane)
@@ -43,7 +44,7 @@ struct RefineArgs {
 
 // sin(th)/th, (1 - cos(th))/th^2 and the coefficients of their derivatives along r, from th^2
 __device__ __forceinline__ void rodrigues_coefficients(double t2, double &a, double &b, double &a1, double &b1) {
-    if (t2 < 1e-3) {  // the next terms are below 1e-12 / 9! of the first
+    if (t2 < 1e-3) {  // the next terms are below t2^4 / 9! < 3e-18 of the first
         a = 1.0 + t2 * (-1.0 / 6.0 + t2 * (1.0 / 120.0 - t2 * (1.0 / 5040.0)));
         b = 0.5 + t2 * (-1.0 / 24.0 + t2 * (1.0 / 720.0 - t2 * (1.0 / 40320.0)));
         a1 = -1.0 / 3.0 + t2 * (1.0 / 30.0 + t2 * (-1.0 / 840.0 + t2 * (1.0 / 45360.0)));
@@ -84,11 +85,10 @@ __global__ void __launch_bounds__(REF_THREADS) k_refine_accumulate(RefineArgs A)
         const double x = ((X0 + a * p0) + b * q0) + t0, y = ((X1 + a * p1) + b * q1) + t1, z = ((X2 + a * p2) + b * q2) + t2_;
         const double iz = 1.0 / z, xn = x * iz, yn = y * iz;  // (z <= 0 divides as IEEE does)
         const double fu = (fx * xn + cx) - o[0], fv = (fy * yn + cy) - o[1];
-        // soft_l1 of every scalar residual: rho = 2 (sqrt(1 + z) - 1) written without the cancellation, w = rho' = 1 / sqrt(1 + z)
-        const double su = fu * inv_fs, sv = fv * inv_fs, zu = su * su, zv = sv * sv;
-        const double hu = sqrt(1.0 + zu), hv = sqrt(1.0 + zv);
-        const double wu = 1.0 / hu, wv = 1.0 / hv;
-        acc[0] += 2.0 * zu / (hu + 1.0) + 2.0 * zv / (hv + 1.0);
+        double rho_u, rho_v, wu, wv;  // soft_l1 of every scalar residual
+        soft_l1(fu * inv_fs, rho_u, wu);
+        soft_l1(fv * inv_fs, rho_v, wv);
+        acc[0] += rho_u + rho_v;
 
         // rows of the Jacobian: d(u, v) / d(x, y, z) through d(x, y, z) / d(r, t), then the intrinsics
         const double ux = fx * iz, uz = -fx * xn * iz, vy = fy * iz, vz = -fy * yn * iz;
@@ -182,90 +182,36 @@ __global__ void __launch_bounds__(64) k_refine_init(RefineArgs A, const double *
         A.g[10 * (size_t)cam + i] = 0.0;
     }
     A.cost[cam] = A.cost0[cam] = __longlong_as_double(0x7FF8000000000000ll);
-    A.lambda[cam] = 1e-3;
+    A.lambda[cam] = LM_LAMBDA0;
     A.phase[cam] = skipped ? REF_DONE : REF_FRESH;
-    A.status[cam] = skipped ? SMIL_REFINE_SKIPPED : SMIL_REFINE_STEP_LIMIT;  // (the step limit, until the camera says otherwise)
+    A.status[cam] = skipped ? SMIL_REFINE_SKIPPED : lm_status(0);  // (the step limit, until the camera says otherwise)
     A.n_accept[cam] = A.n_trial[cam] = 0;
 }
 
 __global__ void __launch_bounds__(64) k_refine_step(RefineArgs A) {
-    __shared__ double s[REF_SLOTS], L[10][10], d[10];
+    __shared__ double s[REF_SLOTS], L[10 * 10], d[10];
     const int cam = blockIdx.x, np = A.np, nh = np * (np + 1) / 2;
     if (A.phase[cam] == REF_DONE) return;  // (block-uniform)
     sum_partials(A, cam, 1 + np + nh, s);
     if (threadIdx.x != 0) return;
     double *cur = A.cur + 10 * (size_t)cam, *cand = A.cand + 10 * (size_t)cam, *g = A.g + 10 * (size_t)cam, *H = A.H + 55 * (size_t)cam;
-    const double cost_new = 0.5 * A.f_scale * A.f_scale * s[0], cost_cur = A.cost[cam];
-    const bool fresh = A.phase[cam] == REF_FRESH;
-    const bool finite = fabs(cost_new) <= 1.79769313486231570e308;  // (false for NaN)
-    double lambda = A.lambda[cam];
-    bool done = false;
-    A.n_trial[cam] += 1;
-    if (fresh && !finite) {
-        A.cost[cam] = A.cost0[cam] = cost_new;
-        A.status[cam] = SMIL_REFINE_NONFINITE;
-        A.phase[cam] = REF_DONE;
-        return;
-    }
-    if (fresh || (finite && cost_new < cost_cur)) {
+    LmState st = {A.lambda[cam], A.cost[cam], A.cost0[cam], A.n_accept[cam], A.n_trial[cam], A.phase[cam] == REF_FRESH};
+    int r = lm_judge(st, 0.5 * A.f_scale * A.f_scale * s[0]);
+    if (r & LM_TAKE) {
         for (int i = 0; i < np; ++i) {
             cur[i] = cand[i];
             g[i] = s[1 + i];
         }
         for (int i = 0; i < nh; ++i) H[i] = s[1 + np + i];
-        A.cost[cam] = cost_new;
-        if (fresh) {
-            A.cost0[cam] = cost_new;
-            A.phase[cam] = REF_RUN;
-        } else {
-            A.n_accept[cam] += 1;
-            lambda = fmax(lambda / 10.0, 1e-12);
-            done = cost_cur - cost_new < 1e-12 * cost_cur;
-        }
-    } else {
-        lambda *= 10.0;
     }
-    done |= lambda > 1e12;
-    if (!done) {
-        // (H + lambda diag H) delta = -g: L L^T by rows, in LDS (runtime indices)
-        bool ok = true;
-        for (int i = 0; i < np; ++i) {
-            for (int j = 0; j <= i; ++j) {
-                double v = H[j * np - j * (j - 1) / 2 + (i - j)];
-                if (i == j) v += lambda * v;
-                for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
-                if (i == j) {
-                    ok &= v > 0.0 && v <= 1.79769313486231570e308;  // (false for NaN)
-                    L[i][i] = sqrt(v);
-                } else {
-                    L[i][j] = v / L[j][j];
-                }
-            }
-        }
-        for (int i = 0; i < np; ++i) {
-            double v = -g[i];
-            for (int k = 0; k < i; ++k) v -= L[i][k] * d[k];
-            d[i] = v / L[i][i];
-        }
-        for (int i = np - 1; i >= 0; --i) {
-            double v = d[i];
-            for (int k = i + 1; k < np; ++k) v -= L[k][i] * d[k];
-            d[i] = v / L[i][i];
-            ok &= fabs(d[i]) <= 1.79769313486231570e308;
-        }
-        if (ok) {
-            for (int i = 0; i < np; ++i) cand[i] = cur[i] + d[i];
-        } else {  // no step from this system: the next pair evaluates the current point again, which is a rejection
-            for (int i = 0; i < np; ++i) cand[i] = cur[i];
-            lambda *= 10.0;
-            done = lambda > 1e12;
-        }
-    }
-    A.lambda[cam] = lambda;
-    if (done) {
-        A.status[cam] = SMIL_REFINE_CONVERGED;
-        A.phase[cam] = REF_DONE;
-    }
+    if (!(r & LM_DONE)) r |= np == 10 ? lm_propose<10>(st, H, g, cur, cand, L, d) : lm_propose<6>(st, H, g, cur, cand, L, d);
+    A.lambda[cam] = st.lambda;
+    A.cost[cam] = st.cost_cur;
+    A.cost0[cam] = st.cost0;
+    A.n_accept[cam] = st.n_accept;
+    A.n_trial[cam] = st.n_trial;
+    A.phase[cam] = r & LM_DONE ? REF_DONE : REF_RUN;
+    if (r & LM_DONE) A.status[cam] = lm_status(r);
 }
 
 // ---- host ----
@@ -303,7 +249,7 @@ static int refine_check(const char *who, const double *pts3, const double *pts2,
     SMIL_REQUIRE(C > 0, "%s: bad size C=%d", who, C);
     SMIL_REQUIRE(C <= 65535, "%s: C=%d cameras exceed the grid", who, C);
     SMIL_REQUIRE(n_params == 6 || n_params == 10, "%s: n_params=%d must be 6 or 10", who, n_params);
-    SMIL_REQUIRE(f_scale > 0.0 && f_scale <= 1.79769313486231570e308, "%s: f_scale=%g must be positive and finite", who, f_scale);
+    if (const int rc = smil_check_f_scale(who, f_scale)) return rc;
     SMIL_REQUIRE(offsets && workspace, "%s: null argument", who);
     SMIL_REQUIRE(offsets[0] == 0, "%s: offsets[0]=%lld must be 0", who, (long long)offsets[0]);
     int64_t mx = 0;

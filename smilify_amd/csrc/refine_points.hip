@@ -2,16 +2,16 @@
 // of csrc/triangulate.hip) to the minimum of the soft_l1 reprojection cost over its views by a Levenberg-Marquardt in three unknowns,
 // all points at once.  Everything is float64.
 //
-// AN EXTENSION: the reference has no such function (its points stay the DLT points of triangulate_point_dlt).  The cost, the weights
-// and the LM rules are those of the camera refinement (csrc/refine.hip, smil_refine_cameras in include/smilfit.h), so the two compose
-// into a block-coordinate bundle adjustment (smilify_amd/refine_points.py).
+// AN EXTENSION: the reference has no such function (its points stay the DLT points of triangulate_point_dlt).  The soft_l1 cost and
+// weight, the accept / reject rule, the Cholesky solve and the statuses are lm.h's, the same code the camera refinement
+// (csrc/refine.hip) runs, so the two compose into a block-coordinate bundle adjustment (smilify_amd/refine_points.py).
 //
 //  * k_refine_points           one wave per problem, RPT_WAVES problems per workgroup, no barrier, no LDS, no atomics, nothing shared
 //      between problems.  Lane r is scalar residual r of the at most 2 C = 64: view r >> 1, component r & 1.  It keeps rows
 //      r & 1 and 2 of its view's projection matrix and its observed coordinate in registers.  One evaluation is the lane's residual and
 //      Jacobian row, then ten wave sums (cost, 3 of g, 6 of H); lanes of views outside the mask contribute exact zeros by SELECTION,
-//      so an unwritten, NaN or garbage observation of a dropped view never reaches a sum.  Every lane then runs the same 3 x 3 Cholesky
-//      and the same accept / reject rules in registers: after the butterfly sums all lanes hold the same bits, so the exit of the
+//      so an unwritten, NaN or garbage observation of a dropped view never reaches a sum.  Every lane then runs lm.h's rules and its
+//      solve at N = 3, unrolled, in registers: after the butterfly sums all lanes hold the same bits, so the exit of the
 //      loop is wave-uniform (and is made a scalar branch with readfirstlane).  Unlike the camera refinement the LM loop runs INSIDE
 //      the kernel, bounded by max_steps: the problems are independent and there are millions of them, a host loop of launches would
 //      cost a launch pair per step for no shared work (triangulate.hip's Jacobi sweeps are the precedent).
@@ -19,6 +19,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "lm.h"
 
 #define RPT_WAVES 4  // problems of one workgroup
 
@@ -77,14 +78,13 @@ __device__ __forceinline__ double rpt_residual(const RptLane &L, double X0, doub
 }
 
 // One accumulation at X: s[0] the cost, s[1 .. 3] g = J^T (w f), s[4 .. 9] the upper triangle of H = J^T diag(w) J (00 01 02 11 12 22);
-// soft_l1 on the scalar residual as in refine.hip.  Every lane returns the same bits.
+// lm.h's soft_l1 on the scalar residual.  Every lane returns the same bits.
 __device__ __forceinline__ void rpt_accumulate(const RptLane &L, double X0, double X1, double X2, double f_scale, double (&s)[10]) {
     double J[3];
     const double f = rpt_residual(L, X0, X1, X2, J);
-    const double sc = f / f_scale, z = sc * sc, h = sqrt(1.0 + z), w = 1.0 / h;
+    double v[10], w;
+    soft_l1(f / f_scale, v[0], w);
     const double wf = w * f;
-    double v[10];
-    v[0] = 2.0 * z / (h + 1.0);  // 2 (sqrt(1 + z) - 1) without its cancellation
 #pragma unroll
     for (int i = 0; i < 3; ++i) v[1 + i] = J[i] * wf;
     v[4] = (w * J[0]) * J[0]; v[5] = (w * J[0]) * J[1]; v[6] = (w * J[0]) * J[2];
@@ -94,38 +94,17 @@ __device__ __forceinline__ void rpt_accumulate(const RptLane &L, double X0, doub
     s[0] = 0.5 * f_scale * f_scale * s[0];
 }
 
-__device__ __forceinline__ bool rpt_finite(double v) { return fabs(v) <= 1.79769313486231570e308; }  // (false for NaN)
-
-// (H + lambda diag H) d = -g by a 3 x 3 Cholesky (rows, as refine.hip's); false when a pivot is not positive and finite or d is not finite.
-__device__ __forceinline__ bool rpt_solve(const double (&g)[3], const double (&H)[6], double lambda, double (&d)[3]) {
-    bool ok = true;
-    double v = H[0] + lambda * H[0];
-    ok &= v > 0.0 && rpt_finite(v);
-    const double l00 = sqrt(v), l10 = H[1] / l00, l20 = H[2] / l00;
-    v = (H[3] + lambda * H[3]) - l10 * l10;
-    ok &= v > 0.0 && rpt_finite(v);
-    const double l11 = sqrt(v), l21 = (H[4] - l20 * l10) / l11;
-    v = ((H[5] + lambda * H[5]) - l20 * l20) - l21 * l21;
-    ok &= v > 0.0 && rpt_finite(v);
-    const double l22 = sqrt(v);
-    const double y0 = -g[0] / l00, y1 = (-g[1] - l10 * y0) / l11, y2 = ((-g[2] - l20 * y0) - l21 * y1) / l22;
-    d[2] = y2 / l22;
-    d[1] = (y1 - l21 * d[2]) / l11;
-    d[0] = ((y0 - l10 * d[1]) - l20 * d[2]) / l00;
-    return ok && rpt_finite(d[0]) && rpt_finite(d[1]) && rpt_finite(d[2]);
-}
-
 __global__ void __launch_bounds__(64 * RPT_WAVES) k_refine_points(RefinePointsArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long prob = (long long)blockIdx.x * RPT_WAVES + wave;
     if (prob >= a.NP) return;  // (wave-uniform; the kernel has no barrier)
     const double nan = __longlong_as_double(0x7FF8000000000000ll);
     const RptLane L = rpt_load(a, prob, lane);
-    double cur[3], cand[3], g[3] = {0.0, 0.0, 0.0}, H[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double cur[3], cand[3], g[3] = {0.0, 0.0, 0.0}, H[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, Lc[9], d[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) cur[i] = cand[i] = a.xyz0[3 * prob + i];
-    double cost_cur = nan, cost0 = nan, lambda = 1e-3;
-    int status = SMIL_REFINE_STEP_LIMIT, n_accept = 0, n_trial = 0;
+    LmState st = {LM_LAMBDA0, nan, nan, 0, 0, true};
+    int status = lm_status(0);
 
     if (rpt_views(a, prob) < 2) {
         status = SMIL_REFINE_POINTS_FEW_VIEWS;
@@ -133,23 +112,8 @@ __global__ void __launch_bounds__(64 * RPT_WAVES) k_refine_points(RefinePointsAr
         for (int step = 0; step < a.max_steps; ++step) {
             double s[10];
             rpt_accumulate(L, cand[0], cand[1], cand[2], a.f_scale, s);
-            const double cost_new = s[0];
-            const bool finite = rpt_finite(cost_new);
-            bool done = false;
-            n_trial += 1;
-            if (step == 0 && __builtin_amdgcn_readfirstlane((int)!finite)) {  // (every lane holds the same cost: a scalar branch)
-                cost_cur = cost0 = cost_new;
-                status = SMIL_REFINE_NONFINITE;
-                break;
-            }
-            if (step == 0 || (finite && cost_new < cost_cur)) {
-                if (step == 0) {
-                    cost0 = cost_new;
-                } else {
-                    n_accept += 1;
-                    lambda = fmax(lambda / 10.0, 1e-12);
-                    done = cost_cur - cost_new < 1e-12 * cost_cur;
-                }
+            int r = lm_judge(st, s[0]);
+            if (r & LM_TAKE) {
 #pragma unroll
                 for (int i = 0; i < 3; ++i) {
                     cur[i] = cand[i];
@@ -157,25 +121,11 @@ __global__ void __launch_bounds__(64 * RPT_WAVES) k_refine_points(RefinePointsAr
                 }
 #pragma unroll
                 for (int i = 0; i < 6; ++i) H[i] = s[4 + i];
-                cost_cur = cost_new;
-            } else {
-                lambda *= 10.0;
             }
-            done |= lambda > 1e12;
-            if (!done) {
-                double d[3];
-                if (rpt_solve(g, H, lambda, d)) {
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) cand[i] = cur[i] + d[i];
-                } else {  // no step from this system: the next evaluation is of the current point again, which is a rejection
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) cand[i] = cur[i];
-                    lambda *= 10.0;
-                    done = lambda > 1e12;
-                }
-            }
-            if (__builtin_amdgcn_readfirstlane((int)done)) {  // the same bits in every lane: a scalar branch
-                status = SMIL_REFINE_CONVERGED;
+            if (!(r & LM_DONE)) r |= lm_propose<3>(st, H, g, cur, cand, Lc, d);
+            r = __builtin_amdgcn_readfirstlane(r);  // every lane holds the same cost, so the same result: a scalar branch
+            if (r & LM_DONE) {
+                status = lm_status(r);
                 break;
             }
         }
@@ -190,10 +140,10 @@ __global__ void __launch_bounds__(64 * RPT_WAVES) k_refine_points(RefinePointsAr
 #pragma unroll
         for (int i = 0; i < 3; ++i) a.xyz[3 * prob + i] = cur[i];
         a.status[prob] = status;
-        a.n_accept[prob] = n_accept;
-        a.n_trial[prob] = n_trial;
-        a.cost0[prob] = cost0;
-        a.cost[prob] = cost_cur;
+        a.n_accept[prob] = st.n_accept;
+        a.n_trial[prob] = st.n_trial;
+        a.cost0[prob] = st.cost0;
+        a.cost[prob] = st.cost_cur;
     }
 }
 
@@ -219,13 +169,10 @@ __global__ void __launch_bounds__(64 * RPT_WAVES) k_refine_points_evaluate(Refin
 // What both entry points check, in this order, before a device is touched.  *NP = N Kp; zero: nothing to do.
 static int refine_points_check(const char *who, int64_t N, int32_t Kp, int32_t C, double f_scale, long long *NP) {
     SMIL_REQUIRE(C >= 1, "%s: bad size C=%d", who, C);
-    if (C > SMIL_TRI_MAX_VIEWS) {
-        smil_set_error("%s: C=%d above SMIL_TRI_MAX_VIEWS=%d (a problem's residuals are the lanes of one wave)", who, C, SMIL_TRI_MAX_VIEWS);
-        return SMIL_E_UNSUPPORTED;
-    }
-    SMIL_REQUIRE(f_scale > 0.0 && f_scale <= 1.79769313486231570e308, "%s: f_scale=%g must be positive and finite", who, f_scale);
+    if (const int rc = smil_check_views(who, C, "a problem's residuals are the lanes of one wave")) return rc;
+    if (const int rc = smil_check_f_scale(who, f_scale)) return rc;
     SMIL_REQUIRE(N >= 0 && Kp >= 0, "%s: bad sizes N=%lld Kp=%d", who, (long long)N, Kp);
-    SMIL_REQUIRE(Kp == 0 || N <= (int64_t)0x7FFFFFFF * RPT_WAVES / Kp, "%s: N Kp = %lld x %d problems exceed the grid", who, (long long)N, Kp);
+    if (const int rc = smil_check_grid(who, N, Kp, RPT_WAVES)) return rc;
     *NP = (long long)N * Kp;
     return SMIL_OK;
 }

@@ -268,11 +268,8 @@ extern "C" int smil_triangulate(const double *P, const double *K, const double *
                                 double reproj_threshold, int32_t mode, double *xyz, int32_t *status, int32_t *views_used, double *mean_err,
                                 double *view_err, uint32_t *inlier_mask, double *obs_undistorted, void *stream_) {
     SMIL_REQUIRE(N > 0 && Kp > 0 && C > 0, "smil_triangulate: bad sizes N=%lld Kp=%d C=%d", (long long)N, Kp, C);
-    if (C > SMIL_TRI_MAX_VIEWS) {
-        smil_set_error("smil_triangulate: C=%d above SMIL_TRI_MAX_VIEWS=%d (a problem's rows stay in one wave)", C, SMIL_TRI_MAX_VIEWS);
-        return SMIL_E_UNSUPPORTED;
-    }
-    SMIL_REQUIRE(N <= (int64_t)0x7FFFFFFF * TRI_WAVES / Kp, "smil_triangulate: N Kp = %lld x %d problems exceed the grid", (long long)N, Kp);
+    if (const int rc = smil_check_views("smil_triangulate", C, "a problem's rows stay in one wave")) return rc;
+    if (const int rc = smil_check_grid("smil_triangulate", N, Kp, TRI_WAVES)) return rc;
     SMIL_REQUIRE(min_views >= 1, "smil_triangulate: min_views=%d must be >= 1", min_views);
     SMIL_REQUIRE((mode & ~(SMIL_TRI_RANSAC | SMIL_TRI_KEEP_ALL_VIEWS)) == 0, "smil_triangulate: unknown mode bits %d", mode);
     SMIL_REQUIRE(P && obs && xyz && status && views_used && mean_err, "smil_triangulate: null argument");

@@ -951,6 +951,18 @@ def group_points_backward(d_out: torch.Tensor, idx: torch.Tensor, N: int, D: int
     return d_feat
 
 
+def upload_f64(x, device):
+    """x (array-like or None) as a contiguous float64 tensor on device: how the numpy-level wrappers hand arrays to the functions below."""
+    return None if x is None else torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(device)
+
+
+def _require_f64(who, name, t, shape, device):
+    """t contiguous, or the ValueError of the multi-view entry points for a tensor that is not float64 of this shape on this device."""
+    if t.dtype != torch.float64 or tuple(t.shape) != shape or t.device != device:
+        raise ValueError(f"{who}: {name} must be a float64 tensor {shape} on {device}")
+    return t.contiguous()
+
+
 def triangulate(P: torch.Tensor, obs: torch.Tensor, scores: Optional[torch.Tensor], pairs: Optional[torch.Tensor], *,
                 K: Optional[torch.Tensor] = None, dist: Optional[torch.Tensor] = None, confidence_threshold: float = 0.3,
                 min_views: int = 2, reproj_threshold: float = 15.0, mode: int = _lib.TRI_RANSAC, want_view_err: bool = False,
@@ -968,13 +980,7 @@ def triangulate(P: torch.Tensor, obs: torch.Tensor, scores: Optional[torch.Tenso
     if min(N, Kp, C) < 1 or int(min_views) < 1:
         raise ValueError(f"triangulate: bad sizes N={N} Kp={Kp} C={C} min_views={min_views}")
 
-    def f64(name, t, shape):
-        if t is None:
-            return None
-        if t.dtype != torch.float64 or tuple(t.shape) != shape or t.device != obs.device:
-            raise ValueError(f"triangulate: {name} must be a float64 tensor {shape} on {obs.device}")
-        return t.contiguous()
-
+    f64 = lambda name, t, shape: None if t is None else _require_f64("triangulate", name, t, shape, obs.device)  # noqa: E731
     P, K, dist = f64("P", P, (C, 3, 4)), f64("K", K, (C, 3, 3)), f64("dist", dist, (C, 5))
     scores = f64("scores", scores, (N, Kp, C))
     if P is None or (K is None) != (dist is None):
@@ -1008,14 +1014,13 @@ def _refine_inputs(who, pts_3d, pts_2d, offsets, params, n_params, f_scale):
         raise ValueError(f"{who}: offsets must be a non-decreasing int64 table (C + 1) that starts at 0")
     C, total = len(offsets) - 1, int(offsets[-1])
     require_gpu(params.device)
-    for name, t, shape in (("pts_3d", pts_3d, (total, 3)), ("pts_2d", pts_2d, (total, 2)), ("params", params, (C, 10))):
-        if t.dtype != torch.float64 or tuple(t.shape) != shape or t.device != params.device:
-            raise ValueError(f"{who}: {name} must be a float64 tensor {shape} on {params.device}")
+    pts_3d, pts_2d, params = (_require_f64(who, name, t, shape, params.device) for name, t, shape in
+                              (("pts_3d", pts_3d, (total, 3)), ("pts_2d", pts_2d, (total, 2)), ("params", params, (C, 10))))
     if int(n_params) not in (6, 10) or not float(f_scale) > 0.0:
         raise ValueError(f"{who}: n_params={n_params} must be 6 or 10 and f_scale={f_scale} positive")
     lib = _lib.load()
     ws = torch.empty(int(lib.smil_refine_workspace_bytes(C, int(np.diff(offsets).max()))), dtype=torch.uint8, device=params.device)
-    return pts_3d.contiguous(), pts_2d.contiguous(), params.contiguous(), offsets, torch.from_numpy(offsets).to(params.device), C, ws
+    return pts_3d, pts_2d, params, offsets, torch.from_numpy(offsets).to(params.device), C, ws
 
 
 def refine_evaluate(pts_3d: torch.Tensor, pts_2d: torch.Tensor, offsets, params: torch.Tensor, *, n_params: int = 10,
@@ -1058,14 +1063,12 @@ def _refine_points_inputs(who, P, obs, view_mask, xyz, f_scale):
     N, Kp, C = (int(v) for v in obs.shape[:3])
     if not 1 <= C <= _lib.TRI_MAX_VIEWS:
         raise ValueError(f"{who}: C={C} cameras outside 1 .. SMIL_TRI_MAX_VIEWS={_lib.TRI_MAX_VIEWS}")
-    for name, t, shape in (("P", P, (C, 3, 4)), ("xyz", xyz, (N, Kp, 3))):
-        if t.dtype != torch.float64 or tuple(t.shape) != shape or t.device != obs.device:
-            raise ValueError(f"{who}: {name} must be a float64 tensor {shape} on {obs.device}")
+    P, xyz = _require_f64(who, "P", P, (C, 3, 4), obs.device), _require_f64(who, "xyz", xyz, (N, Kp, 3), obs.device)
     if view_mask.dtype != torch.int32 or tuple(view_mask.shape) != (N, Kp) or view_mask.device != obs.device:
         raise ValueError(f"{who}: view_mask must be an int32 tensor {(N, Kp)} of bits on {obs.device}")
     if not float(f_scale) > 0.0:
         raise ValueError(f"{who}: f_scale={f_scale} must be positive")
-    return P.contiguous(), obs.contiguous(), view_mask.contiguous(), xyz.contiguous(), N, Kp, C
+    return P, obs.contiguous(), view_mask.contiguous(), xyz, N, Kp, C
 
 
 def refine_points_evaluate(P: torch.Tensor, obs: torch.Tensor, view_mask: torch.Tensor, xyz: torch.Tensor, *, f_scale: float = 5.0):

@@ -21,7 +21,6 @@ import copy
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
-import torch
 
 from . import _lib, engine
 from . import triangulate as tri
@@ -139,7 +138,7 @@ def evaluate_cost(params, correspondences, optimize_intrinsics: bool = True, f_s
     block are zero)."""
     dev = engine.require_gpu(device or tri.DEFAULT_DEVICE)
     p3, p2, offsets = _pack_batch(correspondences)
-    up = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(dev)  # noqa: E731
+    up = lambda x: engine.upload_f64(x, dev)  # noqa: E731
     out = engine.refine_evaluate(up(p3), up(p2), offsets, up(np.asarray(params, np.float64).reshape(-1, 10)),
                                  n_params=10 if optimize_intrinsics else 6, f_scale=f_scale)
     return tuple(t.cpu().numpy() for t in out)
@@ -168,7 +167,7 @@ def optimize_cameras(cameras: Dict[str, dict], correspondences: Dict[str, Tuple[
     dev = engine.require_gpu(device or tri.DEFAULT_DEVICE)
     p3, p2, offsets = _pack_batch([correspondences[n] for n in names])
     x0 = np.stack([_params10(cameras[n]) for n in names])
-    up = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(dev)  # noqa: E731
+    up = lambda x: engine.upload_f64(x, dev)  # noqa: E731
     out = engine.refine_cameras(up(p3), up(p2), offsets, up(x0), n_params=10 if optimize_intrinsics else 6, f_scale=f_scale,
                                 max_steps=max_steps)
     params, status, n_acc, n_trial, cost0, cost, g = (t.cpu().numpy() for t in out)

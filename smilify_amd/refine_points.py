@@ -36,7 +36,7 @@ def _upload(P, obs, view_mask, xyz, device):
         raise ValueError("refine_points: obs must be (N, Kp, C, 2)")
     if obs.shape[2] > _lib.TRI_MAX_VIEWS:
         raise ValueError(f"refine_points: {obs.shape[2]} cameras above SMIL_TRI_MAX_VIEWS={_lib.TRI_MAX_VIEWS}")
-    up = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(dev)  # noqa: E731
+    up = lambda x: engine.upload_f64(x, dev)  # noqa: E731
     mask = np.ascontiguousarray(np.asarray(view_mask).astype(np.uint32, copy=False)).view(np.int32)
     return up(np.asarray(P, np.float64).reshape(-1, 3, 4)), up(obs), torch.from_numpy(mask.copy()).to(dev), up(xyz)
 

@@ -92,7 +92,7 @@ def triangulate_arrays(P, obs, scores=None, K=None, dist=None, confidence_thresh
     ``inlier_mask`` stay, ``view_err`` and ``mean_err`` are those of the refined point over the same valid views as before, and the
     dict gains ``refine_status``, ``refine_cost_initial`` and ``refine_cost_final`` (N,Kp)."""
     dev = engine.require_gpu(device or DEFAULT_DEVICE)
-    up = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(dev)  # noqa: E731
+    up = lambda x: engine.upload_f64(x, dev)  # noqa: E731
     mode = (_lib.TRI_RANSAC if use_ransac else 0) | (_lib.TRI_KEEP_ALL_VIEWS if keep_all_views else 0)
     obs = np.asarray(obs, np.float64)
     if obs.ndim != 4 or obs.shape[3] != 2:

@@ -5,6 +5,9 @@ import os
 
 import numpy as np
 
+import lm_ref
+from lm_ref import rel_err
+
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CONVERGED, STEP_LIMIT, FEW_VIEWS, NONFINITE = 0, 1, 2, 3
 GROUPS = ("ring12", "v2", "v3", "v12", "v32", "par2")
@@ -73,67 +76,18 @@ def evaluate_mp(P, obs, mask, X, f_scale=5.0, digits=40):
         return float(fs * fs * cost / 2), np.array([float(x) for x in g]), np.array([[float(x) for x in row] for row in H])
 
 
-def rel_err(x, ref):
-    """max |x - ref| / max |ref|: the error of a scalar, vector or matrix in units of its largest entry."""
-    x, ref = np.asarray(x, np.float64), np.asarray(ref, np.float64)
-    return float(np.abs(x - ref).max() / np.abs(ref).max())
-
-
 def errors(got, exact):
     return tuple(rel_err(a, b) for a, b in zip(got, exact))
 
 
 def lm(P, obs, mask, xyz0, f_scale=5.0, max_steps=50):
-    """The kernel's Levenberg-Marquardt, rule for rule (include/smilfit.h, smil_refine_points).  Returns a dict: xyz, status,
-    n_accepted, n_trials, cost0, cost, and margin: the smallest |cost_new - cost_cur| / cost_cur over its accept / reject decisions
-    (how far the closest decision is from going the other way)."""
-    x0 = np.asarray(xyz0, np.float64).copy()
-    out = dict(xyz=x0.copy(), status=STEP_LIMIT, n_accepted=0, n_trials=0, cost0=np.nan, cost=np.nan, margin=np.inf)
+    """The kernel's Levenberg-Marquardt (lm_ref.lm; include/smilfit.h, smil_refine_points).  Returns a dict: xyz, status, n_accepted,
+    n_trials, cost0, cost, and margin: the smallest |cost_new - cost_cur| / cost_cur over its accept / reject decisions (how far the
+    closest decision is from going the other way)."""
     if len(views_of(mask, len(P))) < 2:
-        out["status"] = FEW_VIEWS
-        return out
-    cur, cand, lam = x0.copy(), x0.copy(), 1e-3
-    cost_cur, g, H = np.nan, None, None
-    for step in range(max_steps):
-        cost_new, g_new, H_new = evaluate(P, obs, mask, cand, f_scale)
-        out["n_trials"] += 1
-        done = False
-        if step == 0 and not np.isfinite(cost_new):
-            out.update(status=NONFINITE, cost0=cost_new, cost=cost_new)
-            return out
-        if step > 0 and np.isfinite(cost_new):
-            out["margin"] = min(out["margin"], abs(cost_new - cost_cur) / cost_cur)
-        if step == 0 or (np.isfinite(cost_new) and cost_new < cost_cur):
-            if step == 0:
-                out["cost0"] = cost_new
-            else:
-                out["n_accepted"] += 1
-                lam = max(lam / 10.0, 1e-12)
-                done = cost_cur - cost_new < 1e-12 * cost_cur
-            cur, g, H, cost_cur = cand.copy(), g_new, H_new, cost_new
-        else:
-            lam *= 10.0
-        done = done or lam > 1e12
-        if not done:
-            A = H + lam * np.diag(np.diag(H))
-            try:
-                with np.errstate(all="ignore"):
-                    L = np.linalg.cholesky(A)
-                    d = np.linalg.solve(L.T, np.linalg.solve(L, -g))
-                ok = bool(np.isfinite(d).all() and np.isfinite(L).all())
-            except np.linalg.LinAlgError:
-                ok = False
-            cand = cur.copy()
-            if ok:
-                cand = cur + d
-            else:
-                lam *= 10.0
-                done = lam > 1e12
-        if done:
-            out["status"] = CONVERGED
-            break
-    out.update(xyz=cur, cost=cost_cur)
-    return out
+        return dict(xyz=np.asarray(xyz0, np.float64).copy(), status=FEW_VIEWS, n_accepted=0, n_trials=0, cost0=np.nan, cost=np.nan, margin=np.inf)
+    out = lm_ref.lm(lambda x: evaluate(P, obs, mask, x, f_scale), xyz0, 3, max_steps)
+    return dict(xyz=out["x"], **{k: out[k] for k in ("status", "n_accepted", "n_trials", "cost0", "cost", "margin")})
 
 
 def distance(a, b):

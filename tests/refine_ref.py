@@ -6,6 +6,9 @@ import os
 
 import numpy as np
 
+import lm_ref
+from lm_ref import rel_err
+
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 MIN_POINTS = 20
 CONVERGED, STEP_LIMIT, SKIPPED, NONFINITE = 0, 1, 2, 3
@@ -146,60 +149,13 @@ def block(g, H, n_params):
     return g, H
 
 
-def rel_err(x, ref):
-    """max |x - ref| / max |ref|: the error of a vector or matrix in units of its largest entry."""
-    x, ref = np.asarray(x, np.float64), np.asarray(ref, np.float64)
-    return float(np.abs(x - ref).max() / np.abs(ref).max())
-
-
 def lm(params10, p3, p2, n_params=10, f_scale=5.0, max_steps=100):
-    """The kernel's Levenberg-Marquardt, rule for rule (include/smilfit.h, smil_refine_cameras).  Returns a dict: params (10),
-    status, n_accepted, n_trials, cost0, cost, g (10), lambda."""
-    x0 = np.asarray(params10, np.float64).copy()
-    out = dict(params=x0.copy(), status=STEP_LIMIT, n_accepted=0, n_trials=0, cost0=np.nan, cost=np.nan, g=np.zeros(10), lam=1e-3)
+    """The kernel's Levenberg-Marquardt (lm_ref.lm; include/smilfit.h, smil_refine_cameras).  Returns a dict: params (10), status,
+    n_accepted, n_trials, cost0, cost, g (10), lam, margin."""
     if len(p3) < MIN_POINTS:
-        out["status"] = SKIPPED
-        return out
-    n = n_params
-    cur, cand, lam = x0.copy(), x0.copy(), 1e-3
-    cost_cur, g, H = np.nan, None, None
-    for step in range(max_steps):
-        cost_new, g_new, H_new = evaluate(cand, p3, p2, n, f_scale)
-        out["n_trials"] += 1
-        done = False
-        if step == 0 and not np.isfinite(cost_new):
-            out.update(status=NONFINITE, cost0=cost_new, cost=cost_new)
-            return out
-        if step == 0 or (np.isfinite(cost_new) and cost_new < cost_cur):
-            if step == 0:
-                out["cost0"] = cost_new
-            else:
-                out["n_accepted"] += 1
-                lam = max(lam / 10.0, 1e-12)
-                done = cost_cur - cost_new < 1e-12 * cost_cur
-            cur, g, H, cost_cur = cand.copy(), g_new, H_new, cost_new
-        else:
-            lam *= 10.0
-        done = done or lam > 1e12
-        if not done:
-            A = H[:n, :n] + lam * np.diag(np.diag(H[:n, :n]))
-            try:
-                with np.errstate(all="ignore"):
-                    L = np.linalg.cholesky(A)
-                    d = np.linalg.solve(L.T, np.linalg.solve(L, -g[:n]))
-                ok = bool(np.isfinite(d).all() and np.isfinite(L).all())
-            except np.linalg.LinAlgError:
-                ok = False
-            cand = cur.copy()
-            if ok:
-                cand[:n] = cur[:n] + d
-            else:
-                lam *= 10.0
-                done = lam > 1e12
-        if done:
-            out["status"] = CONVERGED
-            break
-    out.update(params=cur, cost=cost_cur, g=g, lam=lam)
+        return dict(params=np.asarray(params10, np.float64).copy(), status=SKIPPED, n_accepted=0, n_trials=0, cost0=np.nan, cost=np.nan, g=np.zeros(10), lam=1e-3, margin=np.inf)
+    out = lm_ref.lm(lambda x: evaluate(x, p3, p2, n_params, f_scale), params10, n_params, max_steps)
+    out["params"] = out.pop("x")
     return out
 
 
