@@ -19,6 +19,7 @@
 //    lanes on pairs that do not exist and 100 v_med3 per face on the selection; it is gone.
 //      list    faces whose tile box contains the tile (via the 64-face group boxes), with their nearest vertex depth; tiles
 //              that may truncate (list > K) order it NEAR TO FAR by the first radix digit of that depth (counting sort).
+//              A binned list of up to LIST_LDS_ROWS * 64 entries is read from memory once and sorted out of LDS.
 //      pass 1  lane = pair.  Per DCHUNK-face chunk: two lanes per face stage its record and its pixel box inside the tile
 //              (shrunk to the pixels that are still open), a prefix sum lays the boxes end to end, and the wave sweeps that
 //              pair list 64 at a time (a start-bit map gives each pair its face with two v_mbcnt and two ds_bpermute; face
@@ -76,6 +77,9 @@
 #endif
 #ifndef SELR
 #define SELR 6              // compact records a lane holds once the selection runs in registers (the stream is then at most SELR * 64 long)
+#endif
+#ifndef LIST_LDS_ROWS
+#define LIST_LDS_ROWS 8     // 64-entry rows of a binned tile list that the list phase keeps in LDS (longer lists: read three times from memory)
 #endif
 #ifndef REC_CAP
 #define REC_CAP 65536       // pair records one (sub-)tile may produce
@@ -1319,7 +1323,55 @@ __global__ void __launch_bounds__(64, WAVES_PER_SIMD) k_raster_dense(RasterArgs 
         TSUB(1)
         const uint2 *const list_src = binned ? a.lists + (size_t)n * a.list_cap + td.x : slist;
         int list_total;
-        if (binned) {
+        // A binned list of at most LIST_LDS_ROWS rows of 64 entries is read from memory ONCE: a tile that cannot truncate sends the ids
+        // straight on to `slist2`; one that can leaves the entries in LDS (the record and histogram areas are free until pass 1), where
+        // the sort's counting pass and its scatter pass find them.  Before, the bounds, the count and the scatter each read the list from
+        // memory, four rows per dependent round trip.  Longer lists, and lists built here, go through memory as before.
+        const bool list_lds = LIST_LDS_ROWS > 0 && binned && td.y <= (uint32_t)(LIST_LDS_ROWS * WAVE);  // (wave-uniform)
+        uint2 *const llist = reinterpret_cast<uint2 *>(&lds);
+        static_assert(LIST_LDS_ROWS * WAVE * sizeof(uint2) <= offsetof(DenseLds, pixt), "the list lives in the record and histogram areas");
+        // the head of the ordered list (the faces of pass 1's first three chunks) also stays in LDS: `psel` is free until the first chunk
+        // is staged, and pass 1's first vertex ids are then requested while the stores to `slist2` are still on their way
+        uint32_t *const head = reinterpret_cast<uint32_t *>(lds.psel);
+        static_assert(3 * DCHUNK * sizeof(uint32_t) <= sizeof(lds.psel), "the list's head lives in psel");
+        if (list_lds) {
+            list_total = (int)td.y;
+            kmin = 0u;
+            kmax = 0u;  // a tile that cannot truncate uses neither bound (nbits0, b1, shift1 and the depth clamp are the sort's and the select's)
+            if (list_total > K) {
+                uint32_t lo = 0x7F7FFFFFu, hi = 0u;
+                for (int i0 = 0; i0 < list_total; i0 += 4 * WAVE) {
+                    uint2 e[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) e[u] = at(list_src, (uint32_t)min(i0 + u * WAVE + lane, list_total - 1));
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        lo = min(lo, e[u].y); hi = max(hi, e[u].y);
+                        if (i0 + u * WAVE + lane < list_total) llist[i0 + u * WAVE + lane] = e[u];
+                    }
+                }
+                for (int o = 32; o > 0; o >>= 1) {
+                    lo = min(lo, (uint32_t)__shfl_xor((int)lo, o, WAVE));
+                    hi = max(hi, (uint32_t)__shfl_xor((int)hi, o, WAVE));
+                }
+                kmin = lo;
+                kmax = __float_as_uint((__uint_as_float(hi) + __uint_as_float(it.w) * 1.000001f) * 1.0000005f) + 1u;  // (as below)
+            } else {  // at most K faces: the order of the list is kept
+                for (int i0 = 0; i0 < list_total; i0 += 4 * WAVE) {
+                    uint2 e[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) e[u] = at(list_src, (uint32_t)min(i0 + u * WAVE + lane, list_total - 1));
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int pos = i0 + u * WAVE + lane;
+                        if (pos < list_total) {
+                            slist2[pos] = e[u].x;
+                            if (pos < 3 * DCHUNK) head[pos] = e[u].x;
+                        }
+                    }
+                }
+            }
+        } else if (binned) {
             // every depth of the tile lies between the nearest vertex of its nearest face and the farthest vertex of any: the entries
             // carry the nearest depth only (8 bytes), and farthest <= nearest + (largest depth extent of a face of the image, from
             // the setup kernel with the work item) bounds the other end - an upper bound is all the key range needs
@@ -1349,14 +1401,71 @@ __global__ void __launch_bounds__(64, WAVES_PER_SIMD) k_raster_dense(RasterArgs 
         const uint32_t krange = kmax - kmin;
         const int nbits0 = krange ? 32 - __clz(krange) : 0;
         const int b1 = min(SEL1_BITS, nbits0), shift1 = nbits0 - b1;
-        __syncthreads();  // the list stores are visible to the loads below
         // tiles that may truncate walk their faces near to far (see sort_list_near_to_far); the others keep the id order
         const uint32_t *const lst = slist2;
-        if (may_truncate) {
-            sort_list_near_to_far(list_src, slist2, list_total, kmin, shift1, b1, lds, lane);
-        } else {  // at most K faces: the order of the list is kept
-            for (int i = lane; i < list_total; i += WAVE) slist2[i] = at(list_src, (uint32_t)i).x;
-            __syncthreads();
+        // The staging loads of pass 1 form a chain list entry -> vertex indices -> vertex coordinates.  The first two links are
+        // fetched ahead: while chunk k is evaluated the indices of chunk k + 1 and the list entries of chunk k + 2 are in
+        // flight (four registers), so a chunk starts with one memory round trip instead of three.
+        const int slot_ = lane & (DCHUNK - 1);
+        auto list_at = [&](int c) { return (int)lst[min(c + slot_, list_total - 1)]; };
+        int f_nx;            // list entry of chunk k + 2
+        int ia, ib, ic;      // vertex ids of chunk k + 1 ...
+        int ja, jb, jc;      // ... and of chunk k
+        auto fetch_ids = [&](int f0, int f1) {
+            ja = face_vertex(a.faces, xf_n, a.F, f0, 0); jb = face_vertex(a.faces, xf_n, a.F, f0, 1); jc = face_vertex(a.faces, xf_n, a.F, f0, 2);
+            ia = face_vertex(a.faces, xf_n, a.F, f1, 0); ib = face_vertex(a.faces, xf_n, a.F, f1, 1); ic = face_vertex(a.faces, xf_n, a.F, f1, 2);
+        };
+        // what a (sub-)tile's pass 1 starts from, through the ordered list in memory
+        auto first_ids = [&]() { f_nx = list_at(2 * DCHUNK); fetch_ids(list_at(0), list_at(DCHUNK)); };
+        if (list_lds) {
+            if (may_truncate) {
+                // the same (row, lane) order of the LDS atomics as sort_list_near_to_far: the same faces at the same positions
+                const int n_buckets = 1 << b1;
+                auto digit_of = [&](const uint2 &e) { return (int)(((e.y - kmin) >> shift1) & (uint32_t)(n_buckets - 1)); };
+                lds.start[lane] = 0;
+                lds_fence();
+                for (int i0 = 0; i0 < list_total; i0 += 4 * WAVE) {
+                    uint2 e[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) e[u] = llist[min(i0 + u * WAVE + lane, list_total - 1)];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+                        if (i0 + u * WAVE + lane < list_total) atomicAdd(&lds.start[digit_of(e[u])], 1);
+                }
+                lds_fence();
+                const int c = lane < n_buckets ? lds.start[lane] : 0;
+                const int incl = wave_scan_add(c);
+                lds_fence();
+                if (lane < n_buckets) lds.bstart[lane] = (uint16_t)min(incl - c, 65535);
+                lds.start[lane] = incl - c;  // running cursor of every bucket
+                lds_fence();
+                for (int i0 = 0; i0 < list_total; i0 += 4 * WAVE) {
+                    uint2 e[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) e[u] = llist[min(i0 + u * WAVE + lane, list_total - 1)];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+                        if (i0 + u * WAVE + lane < list_total) {
+                            const int pos = atomicAdd(&lds.start[digit_of(e[u])], 1);
+                            slist2[pos] = e[u].x;
+                            if (pos < 3 * DCHUNK) head[pos] = e[u].x;
+                        }
+                }
+            }
+            // (the barrier that makes `slist2` visible is the one in front of pass 1, ahead of every read of it)
+            lds_fence();
+            auto head_at = [&](int c) { return (int)head[min(c + slot_, list_total - 1)]; };
+            f_nx = head_at(2 * DCHUNK);
+            fetch_ids(head_at(0), head_at(DCHUNK));
+        } else {
+            __syncthreads();  // the list stores are visible to the loads below
+            if (may_truncate) {
+                sort_list_near_to_far(list_src, slist2, list_total, kmin, shift1, b1, lds, lane);
+            } else {  // at most K faces: the order of the list is kept
+                for (int i = lane; i < list_total; i += WAVE) slist2[i] = at(list_src, (uint32_t)i).x;
+                __syncthreads();
+            }
+            first_ids();
         }
         TMARK(0)
         TSUB(3)
@@ -1367,7 +1476,15 @@ __global__ void __launch_bounds__(64, WAVES_PER_SIMD) k_raster_dense(RasterArgs 
         // exist) and halve whenever pass 1 finds that the records do not fit; span * list_total <= REC_CAP always fits.
         int span = p_end - p_begin;
         while (span > 1 && (long long)span * list_total > 4ll * REC_CAP) span >>= 1;
-        for (int p_lo = p_begin; p_lo < p_end;) {
+        int p_lo = p_begin;
+        // next sub-tile (false: none left): its first vertex ids are requested here, so that they are defined on every way to pass 1
+        auto next_sub_tile = [&]() -> bool {
+            p_lo += span;
+            if (p_lo >= p_end) return false;
+            first_ids();
+            return true;
+        };
+        for (;;) {
             const bool mine = lane >= p_lo && lane < p_lo + span;  // this lane's pixel belongs to the sub-tile
             const int sy0 = p_lo >> 3, sy1 = (p_lo + span - 1) >> 3;                       // its rows ...
             const int sx0 = span >= 8 ? 0 : (p_lo & 7), sx1 = span >= 8 ? 7 : ((p_lo & 7) + span - 1);  // ... and columns
@@ -1401,19 +1518,9 @@ __global__ void __launch_bounds__(64, WAVES_PER_SIMD) k_raster_dense(RasterArgs 
                 if (c < 2 * WAVE) return (uint32_t)__builtin_amdgcn_readlane((int)cst1, c - WAVE);
                 return (uint32_t)__builtin_amdgcn_readfirstlane((int)scfirst[c]);
             };
-            // The staging loads form a chain list entry -> vertex indices -> vertex coordinates.  The first two links are
-            // fetched ahead: while chunk k is evaluated the indices of chunk k + 1 and the list entries of chunk k + 2 are in
-            // flight (four registers), so a chunk starts with one memory round trip instead of three.
-            const int slot_ = lane & (DCHUNK - 1);
-            auto list_at = [&](int c) { return (int)lst[min(c + slot_, list_total - 1)]; };
             // (round 4: one more link ahead - the VERTICES of chunk k + 1 are requested before chunk k is evaluated and wait in nine
             // registers, so a chunk starts with the drain of the previous sweep's stores only, not with a vertex fetch behind it)
-            int f_nx = list_at(2 * DCHUNK);
-            int ia, ib, ic;      // vertex ids of chunk k + 1 ...
-            int ja, jb, jc;      // ... and of chunk k
-            Tri9 tv_nx;          // vertices of chunk k (requested one chunk ahead)
-            { const int f_ = list_at(0); ja = face_vertex(a.faces, xf_n, a.F, f_, 0); jb = face_vertex(a.faces, xf_n, a.F, f_, 1); jc = face_vertex(a.faces, xf_n, a.F, f_, 2); }
-            { const int f_ = list_at(DCHUNK); ia = face_vertex(a.faces, xf_n, a.F, f_, 0); ib = face_vertex(a.faces, xf_n, a.F, f_, 1); ic = face_vertex(a.faces, xf_n, a.F, f_, 2); }
+            Tri9 tv_nx;          // vertices of chunk k (requested one chunk ahead); its ids were requested before the barrier above
             tv_nx = load_tri(a, vn, xv_n, ja, jb, jc);
             for (int c0 = 0; c0 < list_total; c0 += DCHUNK) {
                 if (may_truncate) {
@@ -1437,13 +1544,17 @@ __global__ void __launch_bounds__(64, WAVES_PER_SIMD) k_raster_dense(RasterArgs 
                 }
                 const int m = min(DCHUNK, list_total - c0);
                 int cf, packed2, packed = 0;
+                // (the lane index as the staging sees it is opaque to the compiler: what it derives from it - LDS addresses, the table
+                // offsets - is recomputed per chunk, a few instructions, and not kept for the whole kernel in registers that then spill)
+                int lane_c = lane;
+                asm volatile("" : "+v"(lane_c));
                 const int i0 = ja, i1 = jb, i2 = jc;
                 const Tri9 tv = tv_nx;                       // this chunk's vertices (in flight since the chunk before)
                 ja = ia; jb = ib; jc = ic;
                 tv_nx = load_tri(a, vn, xv_n, ja, jb, jc);  // chunk c0 + DCHUNK
                 ia = face_vertex(a.faces, xf_n, a.F, f_nx, 0); ib = face_vertex(a.faces, xf_n, a.F, f_nx, 1); ic = face_vertex(a.faces, xf_n, a.F, f_nx, 2);  // chunk c0 + 2 DCHUNK
                 f_nx = list_at(c0 + 3 * DCHUNK);
-                stage_faces(a, tv, i0, i1, i2, m, lds.rec, lane, cx, cy, fS, tx, ty, ox0, ox1, oy0, oy1, open_px, cf, packed2, sxy, sid, c0, a.list_stride);
+                stage_faces(a, tv, i0, i1, i2, m, lds.rec, lane_c, cx, cy, fS, tx, ty, ox0, ox1, oy0, oy1, open_px, cf, packed2, sxy, sid, c0, a.list_stride);
                 set_chunk_start(c0 / DCHUNK, (uint32_t)vbase);
                 chunks_done = c0 / DCHUNK + 1;
                 lds_fence();
@@ -1460,7 +1571,7 @@ __global__ void __launch_bounds__(64, WAVES_PER_SIMD) k_raster_dense(RasterArgs 
                 // (start bits at or below its lane) - 1, two v_mbcnt and one ds_bpermute away.
                 const unsigned long long nonempty = __ballot(cf > 0);
                 STAT(31, __popcll(nonempty))  // staged faces that have any open pixel in their box
-                lds.start[lane] = 0;
+                lds.start[lane_c] = 0;
                 lds_fence();
                 if (cf > 0) {
                     atomicOr(reinterpret_cast<uint32_t *>(lds.start) + (off >> 5), 1u << (off & 31));
@@ -1543,13 +1654,14 @@ __global__ void __launch_bounds__(64, WAVES_PER_SIMD) k_raster_dense(RasterArgs 
             if (!fits) {  // wave-uniform: try again with half the pixels
                 span >>= 1;
                 __syncthreads();
+                first_ids();
                 continue;
             }
             set_chunk_start(chunks_done, (uint32_t)vbase);  // (chunks behind an early exit hold no records)
             STAT(21, vbase) STAT(26, 1) STAT(27, list_total) STAT(28, chunks_done) STAT(29, (list_total + DCHUNK - 1) / DCHUNK) STAT(30, __popcll(open_px))
             __syncthreads();  // also: record stores of other lanes are visible from here on
             TMARK(1)
-            HOOK_STOP_AFTER(1, { p_lo += span; continue; }) HOOK_STOP_AFTER(2, { p_lo += span; continue; })
+            HOOK_STOP_AFTER(1, { if (!next_sub_tile()) break; continue; }) HOOK_STOP_AFTER(2, { if (!next_sub_tile()) break; continue; })
 
             // ---------------- select + pass 2 ---------------------------------------------------------------------
             // K-th smallest depth of every pixel that has more than K candidates, and log2 of every kept blend factor summed
@@ -1825,7 +1937,7 @@ __global__ void __launch_bounds__(64, WAVES_PER_SIMD) k_raster_dense(RasterArgs 
             }
             TMARK(2)
             TSUB(5)
-            HOOK_STOP_AFTER(3, { p_lo += span; continue; })
+            HOOK_STOP_AFTER(3, { if (!next_sub_tile()) break; continue; })
             STAT(22, n_cmp) STAT(23, __popcll(__ballot(trunc))) STAT(24, __popcll(__ballot(lds.plog[lane] != 0.0)))
             STAT(40, any_trunc ? 1 : 0) STAT(41, may_truncate ? 1 : 0) STAT(42, any_trunc ? vbase : 0) STAT(43, may_truncate ? vbase : 0) STAT(44, __popcll(__ballot(tie_cut != 0x7FFFFFFF)))
             const double plog_px = lds.plog[lane];
@@ -2010,7 +2122,7 @@ __global__ void __launch_bounds__(64, WAVES_PER_SIMD) k_raster_dense(RasterArgs 
             __syncthreads();
             TMARK(4)
             TSUB(7)
-            p_lo += span;
+            if (!next_sub_tile()) break;
         }
         if (tie_acc != 0ull && lane == 0) {
             atomicOr(&a.tie_mask[(size_t)part * 2u * a.item_cap + item_at], tie_acc);  // (pieces of one tile add their bits)
