@@ -118,6 +118,10 @@ static inline int smil_check_f_scale(const char *who, double f_scale) {
     return SMIL_OK;
 }
 
+// (project.hip) the camera argument of every entry point that takes one.  frames != 0: the cameras are those of `frames` frames
+// x cam->views views (a negative count fails: the caller's own argument was missing)
+int check_cameras(const SmilCameras *cam, const char *who, int frames = 0);
+
 // ---- caller-owned workspaces: every region starts on a 256-byte boundary ----
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -133,8 +137,9 @@ struct Workspace {
     }
 };
 
-// Compute units and LDS per workgroup (on MI355X all 160 KB of a CU) of the current device, asked once per device (lbs.hip: one
-// mutex-guarded table).  256 CUs and 64 KB when the device cannot be asked.
+// Compute units and LDS per workgroup (on MI355X all 160 KB of a CU) of the current device, asked once per device (model.hip: one
+// mutex-guarded table of SMIL_MAX_DEVICES entries).  256 CUs and 64 KB when the device cannot be asked.
+#define SMIL_MAX_DEVICES 16
 struct DeviceLimits { int cus; size_t lds_block; };
 DeviceLimits smil_device_limits();
 
@@ -264,29 +269,5 @@ __device__ __forceinline__ void fix_record_max(unsigned int *slot, float m) {
     if ((threadIdx.x & 63) == 0) atomicMax(slot, __float_as_uint(m));
 }
 
-// ---- FoV-perspective camera of image n (project.hip; also read by the fused LBS backward in lbs.hip) ----
-#define SMIL_ZNEAR 0.001f  // Renderer.DEFAULT_ZNEAR (p3d_renderer.py:24)
-
-struct CamParams {
-    float R[9];
-    float T[3];
-    float k00, k11, tanh_;  // tan(fov/2)
-};
-
-__device__ __forceinline__ CamParams load_camera(const SmilCameras &c, int n) {
-    CamParams p;
-    const float *R = c.R + (size_t)(n % c.nR) * 9;
-    const float *T = c.T + (size_t)(n % c.nT) * 3;
-    for (int i = 0; i < 9; ++i) p.R[i] = R[i];
-    for (int i = 0; i < 3; ++i) p.T[i] = T[i];
-    const float fov = c.fov[n % c.nFov];
-    const float asp = c.aspect ? c.aspect[n % c.nAspect] : 1.0f;
-    const float t = tanf((fov * 0.017453292519943295f) / 2.0f);
-    const float max_y = t * SMIL_ZNEAR;
-    const float max_x = max_y * asp;
-    p.k00 = 2.0f * SMIL_ZNEAR / (max_x - (-max_x));
-    p.k11 = 2.0f * SMIL_ZNEAR / (max_y - (-max_y));
-    p.tanh_ = t;
-    return p;
-}
-
+// ---- FoV-perspective camera of an image: parameters, projection forward and backward (project.hip, lbs.hip) ----
+#include "camera.h"

@@ -10,9 +10,9 @@
 // coalesced; the per-frame joint transforms (J x 48 B) are staged in LDS by each workgroup.
 #include <algorithm>
 
-#include "common.h"
 #include <atomic>
-#include <mutex>
+
+#include "skin.h"
 
 #define FRAMES_PER_BLOCK 4  // one wavefront per frame in the chain kernels: frames per block of a large batch ...
 // ... and of a small one (round 4: blocks of four frames ran 13 -> 21 us (k_pose_fwd) and 21 -> 36 us (k_chain_bwd) from one frame to
@@ -21,10 +21,6 @@
 #define SMALL_BATCH_FRAMES 256
 #endif
 static inline int frames_per_block(int B) { return B <= SMALL_BATCH_FRAMES ? 1 : FRAMES_PER_BLOCK; }
-
-__device__ __forceinline__ void vertex_upstream(const float *__restrict__ d_verts_b, const float *sDJ,
-                                                const int *__restrict__ colptr, const int *__restrict__ row,
-                                                const float *__restrict__ cval, int v, bool regress, float dv[3]);
 
 struct Mat34 {
     float r[9];
@@ -345,13 +341,8 @@ __global__ void __launch_bounds__(256) k_vposed_bwd(const float *__restrict__ d_
     const float w[4] = {w4.x, w4.y, w4.z, w4.w};
     float T[9];
     for (int i = 0; i < 9; ++i) T[i] = 0.f;
-    for (int k = 0; k < SMIL_MAX_BONES; ++k) {
-        if (w[k] == 0.f) continue;
-        const float *Ak = sA + 12 * ((ids >> (8 * k)) & 0xFF);
-        for (int m = 0; m < 3; ++m) { T[3 * m] += w[k] * Ak[4 * m]; T[3 * m + 1] += w[k] * Ak[4 * m + 1]; T[3 * m + 2] += w[k] * Ak[4 * m + 2]; }
-    }
-    float *o = d_vposed + ((size_t)b * V + v) * 3;
-    for (int n = 0; n < 3; ++n) o[n] = T[n] * dv[0] + T[3 + n] * dv[1] + T[6 + n] * dv[2];
+    for (int k = 0; k < SMIL_MAX_BONES; ++k) blend_bone<3, false>(T, sA, ids, k, w[k]);
+    skin_point_bwd(T, dv, d_vposed + ((size_t)b * V + v) * 3);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -374,16 +365,10 @@ __global__ void __launch_bounds__(256) k_skin_fwd(const float *__restrict__ A, c
     const float w[4] = {w4.x, w4.y, w4.z, w4.w};
     float T[12];
     for (int i = 0; i < 12; ++i) T[i] = 0.f;
-    for (int k = 0; k < SMIL_MAX_BONES; ++k) {
-        if (w[k] == 0.f) continue;
-        const float *Ak = sA + 12 * ((ids >> (8 * k)) & 0xFF);
-        for (int i = 0; i < 12; ++i) T[i] += w[k] * Ak[i];
-    }
+    for (int k = 0; k < SMIL_MAX_BONES; ++k) blend_bone<4, false>(T, sA, ids, k, w[k]);
     const float *vp = v_posed + ((size_t)(nS == 1 ? 0 : b) * V + v) * 3;
-    const float x = vp[0], y = vp[1], z = vp[2];
-    float ox = T[0] * x + T[1] * y + T[2] * z + T[3];
-    float oy = T[4] * x + T[5] * y + T[6] * z + T[7];
-    float oz = T[8] * x + T[9] * y + T[10] * z + T[11];
+    float ox, oy, oz;
+    skin_point(T, vp[0], vp[1], vp[2], ox, oy, oz);
     if (trans) { ox += trans[3 * b]; oy += trans[3 * b + 1]; oz += trans[3 * b + 2]; }
     float *o = verts + ((size_t)b * V + v) * 3;
     o[0] = ox; o[1] = oy; o[2] = oz;
@@ -406,7 +391,7 @@ __global__ void __launch_bounds__(1024) k_regress_joints(const int *__restrict__
         for (int e = rowptr[j] + lane; e < rowptr[j + 1]; e += WAVE) {
             const float w = val[e];
             const float *p = vb + 3 * col[e];
-            a0 += (p[0] - t0) * w; a1 += (p[1] - t1) * w; a2 += (p[2] - t2) * w;
+            a0 += regress_joint_term(p[0], t0, w); a1 += regress_joint_term(p[1], t1, w); a2 += regress_joint_term(p[2], t2, w);
         }
         a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2);
         if (lane == 0) {
@@ -420,8 +405,11 @@ __global__ void __launch_bounds__(1024) k_regress_joints(const int *__restrict__
 // ---------------------------------------------------------------------------------------------
 // skinning + joint regression + projection of one frame in one workgroup: the posed vertices are kept in LDS for the joint
 // regressor (a gather) and projected through the frame's cameras as they are produced, so `verts` is written once and never
-// read back by the forward pass (k_skin_fwd + k_regress_joints + k_project read it twice).  Same arithmetic, in the same
-// order, as those three kernels: the outputs are bit-identical.
+// read back by the forward pass (k_skin_fwd + k_regress_joints + k_project read it twice).  The routes agree to rounding only
+// (tests/test_gpu_lbs_fused.py: 1e-6 of the largest entry).  `verts` and `ndc` come from the helpers k_skin_fwd and k_project
+// call (skin.h, camera.h), in the same order, but the compiler contracts their sums of products kernel by kernel
+// (fp-contract=fast): the last bit may differ.  For `joints` and `yx` the order differs as well: a regressor row is summed over
+// sixteen lanes here (row_sum16) and over the 64 strided lanes of a wave in k_regress_joints (wave_sum).
 // ---------------------------------------------------------------------------------------------
 #define FWD_FUSED_THREADS 512
 #define FWD_FUSED_MAX_VIEWS 32
@@ -453,7 +441,7 @@ __global__ void __launch_bounds__(NT, FWD_MIN_WAVES) k_skin_project_fwd(SkinProj
     float *vL = smem;                              // (V,3) posed vertices of the frame: what the joint regressor gathers from (models with
                                                    // static joints keep none: any mesh size fits - round 4, the mouse)
     float *sA = smem + (((a.regress ? 3 * V : 0) + 3) & ~3);  // (J,12)
-    float *sCam = sA + 12 * J;                     // (views,16)
+    float *sCam = sA + 12 * J;                     // (views,16): staged_camera
     // the joint regressor (CSR) is staged once per workgroup when it fits: a joint is then LDS reads only (from memory every joint
     // is a chain of two round trips, seven joints deep per wave - measured: 126 -> see profiles/r3_small_kernels.md)
     int *sRow = reinterpret_cast<int *>(sCam + 16 * views);  // (J+1)
@@ -470,13 +458,7 @@ __global__ void __launch_bounds__(NT, FWD_MIN_WAVES) k_skin_project_fwd(SkinProj
     const float *const valp = reg_lds ? sVal : a.val;
     for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
         for (int i = tid; i < 12 * J; i += NT) sA[i] = a.A[(size_t)b * J * 12 + i];
-        if (tid < views) {
-            const CamParams cp = load_camera(a.cam, b * views + tid);
-            float *o = sCam + 16 * tid;
-            for (int i = 0; i < 9; ++i) o[i] = cp.R[i];
-            for (int i = 0; i < 3; ++i) o[9 + i] = cp.T[i];
-            o[12] = cp.k00; o[13] = cp.k11;
-        }
+        if (tid < views) stage_camera(staged_camera(sCam, tid), a.cam, b * views + tid);
         __syncthreads();
         const float *vpb = a.v_skin + (size_t)(a.nS == 1 ? 0 : b) * V * 3;
         const float tx = a.trans ? a.trans[3 * b] : 0.f, ty = a.trans ? a.trans[3 * b + 1] : 0.f, tz = a.trans ? a.trans[3 * b + 2] : 0.f;
@@ -500,31 +482,19 @@ __global__ void __launch_bounds__(NT, FWD_MIN_WAVES) k_skin_project_fwd(SkinProj
 #pragma unroll
                 for (int i = 0; i < 12; ++i) T[i] = 0.f;
 #pragma unroll
-                for (int k = 0; k < SMIL_MAX_BONES; ++k) {
-                    if (w[k] == 0.f) continue;
-                    const float4 *Ak = reinterpret_cast<const float4 *>(sA) + 3 * ((ids[u] >> (8 * k)) & 0xFF);  // (three 16-byte LDS reads per bone)
-#pragma unroll
-                    for (int m_ = 0; m_ < 3; ++m_) {
-                        const float4 r = Ak[m_];
-                        T[4 * m_] += w[k] * r.x; T[4 * m_ + 1] += w[k] * r.y; T[4 * m_ + 2] += w[k] * r.z; T[4 * m_ + 3] += w[k] * r.w;
-                    }
-                }
-                const float x = P[u][0], y = P[u][1], z = P[u][2];
-                float ox = T[0] * x + T[1] * y + T[2] * z + T[3];
-                float oy = T[4] * x + T[5] * y + T[6] * z + T[7];
-                float oz = T[8] * x + T[9] * y + T[10] * z + T[11];
+                for (int k = 0; k < SMIL_MAX_BONES; ++k) blend_bone<4, true>(T, sA, ids[u], k, w[k]);
+                float ox, oy, oz;
+                skin_point(T, P[u][0], P[u][1], P[u][2], ox, oy, oz);
                 if (a.trans) { ox += tx; oy += ty; oz += tz; }
                 if (a.regress) { vL[3 * v] = ox; vL[3 * v + 1] = oy; vL[3 * v + 2] = oz; }
                 float *o = a.verts + ((size_t)b * V + v) * 3;
                 o[0] = ox; o[1] = oy; o[2] = oz;
                 if (a.ndc)
                     for (int view = 0; view < views; ++view) {
-                        const float *cp = sCam + 16 * view;
-                        const float vx = ox * cp[0] + oy * cp[3] + oz * cp[6] + cp[9];
-                        const float vy = ox * cp[1] + oy * cp[4] + oz * cp[7] + cp[10];
-                        const float vz = ox * cp[2] + oy * cp[5] + oz * cp[8] + cp[11];
+                        float xn, yn, vz;
+                        camera_project(staged_camera(sCam, view), ox, oy, oz, xn, yn, vz);
                         float *q = a.ndc + ((size_t)(b * views + view) * V + v) * 3;
-                        q[0] = vx * cp[12] / vz; q[1] = vy * cp[13] / vz; q[2] = vz;
+                        q[0] = xn; q[1] = yn; q[2] = vz;
                     }
             }
         }
@@ -543,7 +513,7 @@ __global__ void __launch_bounds__(NT, FWD_MIN_WAVES) k_skin_project_fwd(SkinProj
                     for (int e = rowp[j] + sub; e < rowp[j + 1]; e += 16) {
                         const float w = valp[e];
                         const float *p = vL + 3 * colp[e];
-                        q0 += (p[0] - t0) * w; q1 += (p[1] - t1) * w; q2 += (p[2] - t2) * w;
+                        q0 += regress_joint_term(p[0], t0, w); q1 += regress_joint_term(p[1], t1, w); q2 += regress_joint_term(p[2], t2, w);
                     }
                 q0 = row_sum16(q0) + t0; q1 = row_sum16(q1) + t1; q2 = row_sum16(q2) + t2;
                 if (live && sub == 0) { float *o = a.joints + ((size_t)b * J + j) * 3; o[0] = q0; o[1] = q1; o[2] = q2; }
@@ -553,13 +523,9 @@ __global__ void __launch_bounds__(NT, FWD_MIN_WAVES) k_skin_project_fwd(SkinProj
             }
             if (a.yx && live)
                 for (int view = sub; view < views; view += 16) {
-                    const float *cp = sCam + 16 * view;
-                    const float vx = q0 * cp[0] + q1 * cp[3] + q2 * cp[6] + cp[9];
-                    const float vy = q0 * cp[1] + q1 * cp[4] + q2 * cp[7] + cp[10];
-                    const float vz = q0 * cp[2] + q1 * cp[5] + q2 * cp[8] + cp[11];
-                    const float xn = vx * cp[12] / vz, yn = vy * cp[13] / vz;
-                    float *q = a.yx + ((size_t)(b * views + view) * J + j) * 2;
-                    q[0] = hS - hS * yn; q[1] = hS - hS * xn;
+                    float xn, yn, vz;
+                    camera_project(staged_camera(sCam, view), q0, q1, q2, xn, yn, vz);
+                    ndc_to_yx(hS, xn, yn, a.yx + ((size_t)(b * views + view) * J + j) * 2);
                 }
         }
         __syncthreads();  // the next frame overwrites vL, sA, sCam
@@ -568,28 +534,9 @@ __global__ void __launch_bounds__(NT, FWD_MIN_WAVES) k_skin_project_fwd(SkinProj
 
 #define FWD_REG_LDS_MAX 4096  // regressor non-zeros staged in LDS (32 KB)
 static int fwd_fused_nnz_lds(const SmilModel *m) { return (!m->static_joints && m->jreg_nnz <= FWD_REG_LDS_MAX) ? m->jreg_nnz : 0; }
-#define SMIL_MAX_DEVICES 16
 static int current_device_slot() {  // index of the current device into per-device tables (0 when it cannot be told)
     int dev = 0;
     return (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < SMIL_MAX_DEVICES) ? dev : 0;
-}
-// (common.h) the grids of the persistent kernels of every file; what a workgroup may take of the CU's LDS
-DeviceLimits smil_device_limits() {
-    static std::mutex mu;
-    static DeviceLimits table[SMIL_MAX_DEVICES];
-    static bool known[SMIL_MAX_DEVICES] = {};
-    int dev = 0;
-    DeviceLimits q = {256, 64 * 1024};
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SMIL_MAX_DEVICES) return q;
-    std::lock_guard<std::mutex> lock(mu);
-    if (!known[dev]) {
-        int cus = 0, lds = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) q.cus = cus;
-        if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess && lds > 0) q.lds_block = (size_t)lds;
-        table[dev] = q;
-        known[dev] = true;
-    }
-    return table[dev];
 }
 // LDS a fused per-frame kernel may ask for so that TWO workgroups fit a CU: meshes beyond it take the separate kernels
 static size_t fused_lds_limit() { return smil_device_limits().lds_block / 2; }
@@ -605,14 +552,10 @@ extern "C" int smil_lbs_forward(const SmilModel *m, const SmilLbsInputs *in, con
     return lbs_forward_impl(m, in, out, nullptr, nullptr, nullptr, (hipStream_t)stream_);
 }
 
-extern "C" int smil_project2(const SmilCameras *cam, const float *pts_a, int32_t Pa, float *ndc_a, float *yx_a, const float *pts_b,
-                             int32_t Pb, float *ndc_b, float *yx_b, void *stream);
-
 extern "C" int smil_lbs_forward_project(const SmilModel *m, const SmilLbsInputs *in, const SmilLbsOutputs *out, const SmilCameras *cam,
                                         float *ndc, float *yx, void *stream_) {
     SMIL_REQUIRE(cam && (ndc || yx), "smil_lbs_forward_project: cameras and at least one of ndc / yx are required");
-    SMIL_REQUIRE(in && cam->N > 0 && cam->views > 0 && cam->N == in->B * cam->views, "smil_lbs_forward_project: %d images for %d frames x %d views",
-                 cam->N, in ? in->B : 0, cam->views);
+    if (int rc = check_cameras(cam, "smil_lbs_forward_project", in ? in->B : -1)) return rc;
     return lbs_forward_impl(m, in, out, cam, ndc, yx, (hipStream_t)stream_);
 }
 
@@ -723,21 +666,6 @@ static int lbs_forward_impl(const SmilModel *m, const SmilLbsInputs *in, const S
 // backward
 // =============================================================================================
 
-// total upstream gradient on a posed vertex: d_verts + J_regressor (CSC gather) d_joints
-__device__ __forceinline__ void vertex_upstream(const float *__restrict__ d_verts_b, const float *sDJ,
-                                                const int *__restrict__ colptr, const int *__restrict__ row,
-                                                const float *__restrict__ cval, int v, bool regress, float dv[3]) {
-    dv[0] = dv[1] = dv[2] = 0.f;
-    if (d_verts_b) { dv[0] = d_verts_b[3 * v]; dv[1] = d_verts_b[3 * v + 1]; dv[2] = d_verts_b[3 * v + 2]; }
-    if (regress) {
-        for (int e = colptr[v]; e < colptr[v + 1]; ++e) {
-            const float w = cval[e];
-            const float *dj = sDJ + 3 * row[e];
-            dv[0] += w * dj[0]; dv[1] += w * dj[1]; dv[2] += w * dj[2];
-        }
-    }
-}
-
 // d_A[b][j] = sum_{v in bone j} w (dv (x) [v_posed;1]).  One block per frame, one wave per bone
 // (strided); deterministic (no atomics).
 #ifndef SKIN_BWD_THREADS
@@ -765,11 +693,7 @@ __global__ void __launch_bounds__(1024) k_skin_bwd_transforms(
             const float w = bone_w[e];
             float dv[3];
             vertex_upstream(dvb, sDJ, colptr, row, cval, v, reg, dv);
-            const float x = vpb[3 * v], y = vpb[3 * v + 1], z = vpb[3 * v + 2];
-            for (int r = 0; r < 3; ++r) {
-                const float g = w * dv[r];
-                acc[4 * r] += g * x; acc[4 * r + 1] += g * y; acc[4 * r + 2] += g * z; acc[4 * r + 3] += g;
-            }
+            bone_accumulate(acc, w, dv, vpb[3 * v], vpb[3 * v + 1], vpb[3 * v + 2]);
         }
         for (int i = 0; i < 12; ++i) acc[i] = wave_sum(acc[i]);
         if (lane == 0)
@@ -1081,24 +1005,12 @@ __global__ void __launch_bounds__(1024) k_shape_bwd(
             const uint32_t ids = skin_idx[v];
             const float4 w4 = skin_w[v];
             const float w[4] = {w4.x, w4.y, w4.z, w4.w};
-            float T[9];
+            float T[9], dvp[3];
             for (int i = 0; i < 9; ++i) T[i] = 0.f;
-            for (int k = 0; k < SMIL_MAX_BONES; ++k) {
-                if (w[k] == 0.f) continue;
-                const float *Ak = sA + 12 * ((ids >> (8 * k)) & 0xFF);
-                for (int m = 0; m < 3; ++m) {
-                    T[3 * m] += w[k] * Ak[4 * m]; T[3 * m + 1] += w[k] * Ak[4 * m + 1]; T[3 * m + 2] += w[k] * Ak[4 * m + 2];
-                }
-            }
-            float dvp[3];
-            for (int n = 0; n < 3; ++n) dvp[n] = T[n] * dv[0] + T[3 + n] * dv[1] + T[6 + n] * dv[2];
-            if (reg_r) {
-                for (int e = colptr[v]; e < colptr[v + 1]; ++e) {
-                    const float wv = cval[e];
-                    const float *dr = sDR + 3 * row[e];
-                    dvp[0] += wv * dr[0]; dvp[1] += wv * dr[1]; dvp[2] += wv * dr[2];
-                }
-            }
+            for (int k = 0; k < SMIL_MAX_BONES; ++k) blend_bone<3, false>(T, sA, ids, k, w[k]);
+            skin_point_bwd(T, dv, dvp);
+            if (reg_r)
+                for (int e = colptr[v]; e < colptr[v + 1]; ++e) regressor_gather_term(cval[e], sDR + 3 * row[e], dvp);
             if (up_vshaped) { dvp[0] += up_vshaped[3 * v]; dvp[1] += up_vshaped[3 * v + 1]; dvp[2] += up_vshaped[3 * v + 2]; }
             if (d_vshaped && k0 == 0) {  // = gradient on del_v: v_shaped = v_template + blend + del_v
                 float *o = d_vshaped + ((size_t)b * V + v) * 3;
@@ -1180,21 +1092,6 @@ struct LbsBwdNdcArgs {
     int B, V, J, nS, nB_used, regress, trans_after, bone_slots;
 };
 
-__device__ __forceinline__ void project_point_bwd(const float *cp /* 15 floats: R, T, k00, k11, - */, float x, float y, float z,
-                                                  float dxn, float dyn, float &gx, float &gy, float &gz, float &fsum) {
-    const float vx = x * cp[0] + y * cp[3] + z * cp[6] + cp[9];
-    const float vy = x * cp[1] + y * cp[4] + z * cp[7] + cp[10];
-    const float vz = x * cp[2] + y * cp[5] + z * cp[8] + cp[11];
-    const float iz = 1.0f / vz;
-    const float xn = vx * cp[12] * iz, yn = vy * cp[13] * iz;
-    const float dvx = dxn * cp[12] * iz, dvy = dyn * cp[13] * iz;
-    const float dvz = -(xn * dxn + yn * dyn) * iz;
-    gx += cp[0] * dvx + cp[1] * dvy + cp[2] * dvz;
-    gy += cp[3] * dvx + cp[4] * dvy + cp[5] * dvz;
-    gz += cp[6] * dvx + cp[7] * dvy + cp[8] * dvz;
-    fsum += dxn * xn + dyn * yn;
-}
-
 // Every loop over the thread's vertices works on NDC_UNR of them at a time, loads first: with two workgroups per CU the time of
 // a frame is its chain of memory round trips, and one round trip then covers NDC_UNR vertices (measured on 4096 STICK frames:
 // 308 us with one vertex per round trip, see profiles/r3_small_kernels.md).
@@ -1216,7 +1113,7 @@ __global__ void __launch_bounds__(NT, NDC_BWD_MIN_WAVES) k_lbs_bwd_ndc(LbsBwdNdc
     float *vpL = dvL + 3 * V;           // (V,3) the vertices the skinning transforms were applied to (v_shaped / v_posed)   [VPL]
     float *sA = smem + (((VPL ? 6 : 3) * V + 3) & ~3);  // (J,12), 16-byte aligned
     float *sDJ = sA + 12 * J;           // (J,3) gradient on the posed joints
-    float *sCam = sDJ + 3 * J;          // (views,16)
+    float *sCam = sDJ + 3 * J;          // (views,16): staged_camera
     float *sFov = sCam + 16 * views;    // (views) raw fov sums of the frame's images
     float *red = sFov + views;          // (NW,12)
     int *sBone = reinterpret_cast<int *>(red + NW * 12);  // (bone_slots,3) {first entry, end, bone} in the order the waves take them
@@ -1236,11 +1133,7 @@ __global__ void __launch_bounds__(NT, NDC_BWD_MIN_WAVES) k_lbs_bwd_ndc(LbsBwdNdc
         // ---- phase 0: the frame's transforms, cameras and joint gradient ----
         for (int i = tid; i < 12 * J; i += NT) sA[i] = a.A[(size_t)b * J * 12 + i];
         if (tid < views) {
-            const CamParams cp = load_camera(a.cam, b * views + tid);
-            float *o = sCam + 16 * tid;
-            for (int i = 0; i < 9; ++i) o[i] = cp.R[i];
-            for (int i = 0; i < 3; ++i) o[9 + i] = cp.T[i];
-            o[12] = cp.k00; o[13] = cp.k11;
+            stage_camera(staged_camera(sCam, tid), a.cam, b * views + tid);
             sFov[tid] = 0.f;
         }
         __syncthreads();
@@ -1254,7 +1147,7 @@ __global__ void __launch_bounds__(NT, NDC_BWD_MIN_WAVES) k_lbs_bwd_ndc(LbsBwdNdc
                     float fsum = 0.f;
                     if (j < J && a.d_yx) {
                         const size_t o = (size_t)(b * views + view) * J + j;
-                        project_point_bwd(sCam + 16 * view, x, y, z, -h * a.d_yx[o * 2 + 1], -h * a.d_yx[o * 2], gx, gy, gz, fsum);
+                        fsum += camera_project_bwd(staged_camera(sCam, view), x, y, z, -h * a.d_yx[o * 2 + 1], -h * a.d_yx[o * 2], gx, gy, gz);
                     }
                     if (a.d_fov_img && a.d_yx) {
                         const float r = wave_sum(fsum);
@@ -1278,7 +1171,7 @@ __global__ void __launch_bounds__(NT, NDC_BWD_MIN_WAVES) k_lbs_bwd_ndc(LbsBwdNdc
         else
             for (int view = 0; view < views; ++view) {
                 const int n = b * views + view;
-                const float *cp = sCam + 16 * view;
+                const CamParams &cp = staged_camera(sCam, view);
                 const float sc = a.d_ndc_scale ? a.d_ndc_scale[n] : 0.f;
                 const float2 *dn = reinterpret_cast<const float2 *>(a.d_ndc) + (size_t)n * V;
                 float fsum = 0.f;
@@ -1296,13 +1189,9 @@ __global__ void __launch_bounds__(NT, NDC_BWD_MIN_WAVES) k_lbs_bwd_ndc(LbsBwdNdc
                         const int v = v0 + u * NT;
                         if (v >= V) continue;
                         float dxn = raw[u].x, dyn = raw[u].y;
-                        if (sc != 0.f) {  // x * 2^32 + y in two's complement: a negative y borrowed one from the high word
-                            const int qy = __float_as_int(raw[u].x), qx = __float_as_int(raw[u].y) - (qy >> 31);
-                            dxn = sc > 0.f ? (float)qx * sc : 0.f;
-                            dyn = sc > 0.f ? (float)qy * sc : 0.f;
-                        }
+                        if (sc != 0.f) unpack_d_ndc(raw[u], sc, dxn, dyn);
                         float gx = 0.f, gy = 0.f, gz = 0.f;
-                        project_point_bwd(cp, X[u][0], X[u][1], X[u][2], dxn, dyn, gx, gy, gz, fsum);
+                        fsum += camera_project_bwd(cp, X[u][0], X[u][1], X[u][2], dxn, dyn, gx, gy, gz);
                         if (view > 0) { gx += dvL[3 * v]; gy += dvL[3 * v + 1]; gz += dvL[3 * v + 2]; }
                         dvL[3 * v] = gx; dvL[3 * v + 1] = gy; dvL[3 * v + 2] = gz;
                     }
@@ -1317,12 +1206,11 @@ __global__ void __launch_bounds__(NT, NDC_BWD_MIN_WAVES) k_lbs_bwd_ndc(LbsBwdNdc
             for (int view = 0; view < views; ++view) {
                 const size_t n = (size_t)b * views + view;
                 const uint32_t first = a.cd.range[2 * n], cnt = a.cd.range[2 * n + 1];
-                const float *cp = sCam + 16 * view;
                 for (uint32_t e = tid; e < cnt; e += NT) {
                     const int v = a.cd.vertex[first + e];
                     const float dz = a.cd.dz[first + e];
                     if (v < 0 || v >= V || dz == 0.f) continue;
-                    atomicAdd(&dvL[3 * v], dz * cp[2]); atomicAdd(&dvL[3 * v + 1], dz * cp[5]); atomicAdd(&dvL[3 * v + 2], dz * cp[8]);
+                    clip_depth_bwd(staged_camera(sCam, view), dz, dvL + 3 * v);
                 }
             }
             __syncthreads();
@@ -1363,31 +1251,18 @@ __global__ void __launch_bounds__(NT, NDC_BWD_MIN_WAVES) k_lbs_bwd_ndc(LbsBwdNdc
                     const float *dj0 = sDJ + 3 * (first[u].x & 0xFFFF);
                     dv[0] += w0 * dj0[0]; dv[1] += w0 * dj0[1]; dv[2] += w0 * dj0[2];
                     if (n_ent > 1)  // (rare: a vertex that several joints regress from)
-                        for (int e = a.colptr[v] + 1; e < a.colptr[v + 1]; ++e) {
-                            const float w = a.cval[e];
-                            const float *dj = sDJ + 3 * a.row[e];
-                            dv[0] += w * dj[0]; dv[1] += w * dj[1]; dv[2] += w * dj[2];
-                        }
+                        for (int e = a.colptr[v] + 1; e < a.colptr[v + 1]; ++e) regressor_gather_term(a.cval[e], sDJ + 3 * a.row[e], dv);
                     dvL[3 * v] = dv[0]; dvL[3 * v + 1] = dv[1]; dvL[3 * v + 2] = dv[2];
                 }
                 if (!a.trans_after) { term[9] += dv[0]; term[10] += dv[1]; term[11] += dv[2]; }
                 if (a.nB_used == 0) continue;
                 const float w[4] = {w4[u].x, w4[u].y, w4[u].z, w4[u].w};
-                float T[9];
+                float T[9], dvp[3];
 #pragma unroll
                 for (int i = 0; i < 9; ++i) T[i] = 0.f;
 #pragma unroll
-                for (int k = 0; k < SMIL_MAX_BONES; ++k) {
-                    if (w[k] == 0.f) continue;
-                    const float4 *Ak = reinterpret_cast<const float4 *>(sA) + 3 * ((ids[u] >> (8 * k)) & 0xFF);  // (three 16-byte LDS reads per bone)
-#pragma unroll
-                    for (int m = 0; m < 3; ++m) {
-                        const float4 r = Ak[m];
-                        T[3 * m] += w[k] * r.x; T[3 * m + 1] += w[k] * r.y; T[3 * m + 2] += w[k] * r.z;
-                    }
-                }
-                float dvp[3];
-#pragma unroll
+                for (int k = 0; k < SMIL_MAX_BONES; ++k) blend_bone<3, true>(T, sA, ids[u], k, w[k]);
+#pragma unroll  // (= skin_point_bwd, written out: through the helper the NBT = 6 variants spill 12 to 20 bytes more per lane)
                 for (int n = 0; n < 3; ++n) dvp[n] = T[n] * dv[0] + T[3 + n] * dv[1] + T[6 + n] * dv[2];
 #pragma unroll
                 for (int k = 0; k < NBT; ++k)
@@ -1454,11 +1329,7 @@ __global__ void __launch_bounds__(NT, NDC_BWD_MIN_WAVES) k_lbs_bwd_ndc(LbsBwdNdc
             {
                 const int vid = l0.vid;
                 const float x = VPL ? vpL[3 * vid] : x0, y = VPL ? vpL[3 * vid + 1] : y0, z = VPL ? vpL[3 * vid + 2] : z0;
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    const float g = l0.w * dvL[3 * vid + r];
-                    acc[4 * r] += g * x; acc[4 * r + 1] += g * y; acc[4 * r + 2] += g * z; acc[4 * r + 3] += g;
-                }
+                bone_accumulate(acc, l0.w, dvL + 3 * vid, x, y, z);
             }
             if (s0.e0 + WAVE >= s0.e1) {  // the bone's last segment
                 float q[3];
@@ -1538,8 +1409,7 @@ extern "C" int smil_lbs_backward_ndc(const SmilModel *m, const SmilLbsInputs *in
     SMIL_REQUIRE(d_ndc || d_yx_joints, "smil_lbs_backward_ndc: no upstream gradient");
     SMIL_REQUIRE(!g->d_verts && !g->d_joints && !g->d_del_v && !g->up_v_shaped,
                  "smil_lbs_backward_ndc: d_verts / d_joints / d_del_v / up_v_shaped belong to smil_lbs_backward");
-    SMIL_REQUIRE(cam->N > 0 && cam->views > 0 && cam->N == in->B * cam->views, "smil_lbs_backward_ndc: %d images for %d frames x %d views",
-                 cam->N, in->B, cam->views);
+    if (int rc = check_cameras(cam, "smil_lbs_backward_ndc", in->B)) return rc;
     SMIL_REQUIRE(smil_lbs_backward_ndc_supported(m, g->d_beta ? in->nB_used : 0, cam->views),
                  "smil_lbs_backward_ndc: not available for this model / call (pose blend shapes, more than %d shape coefficients or %d views, "
                  "or a mesh beyond 80 KB of LDS): use smil_project_backward + smil_lbs_backward", NDC_BWD_MAX_BETAS, NDC_BWD_MAX_VIEWS);

@@ -1,6 +1,7 @@
 // Model constants: upload + derived tables (CSC regressor, per-bone vertex lists, joint depths).
 #include <algorithm>
 #include <cstring>
+#include <mutex>
 #include <numeric>
 #include <string>
 
@@ -23,6 +24,25 @@ extern "C" const char *smil_version(void) { return "smilfit 0.3 (gfx950) instrum
 #else
 extern "C" const char *smil_version(void) { return "smilfit 0.3 (gfx950)"; }
 #endif
+
+// (common.h) the grids of the persistent kernels of every file; what a workgroup may take of the CU's LDS
+DeviceLimits smil_device_limits() {
+    static std::mutex mu;
+    static DeviceLimits table[SMIL_MAX_DEVICES];
+    static bool known[SMIL_MAX_DEVICES] = {};
+    int dev = 0;
+    DeviceLimits q = {256, 64 * 1024};
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SMIL_MAX_DEVICES) return q;
+    std::lock_guard<std::mutex> lock(mu);
+    if (!known[dev]) {
+        int cus = 0, lds = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) q.cus = cus;
+        if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess && lds > 0) q.lds_block = (size_t)lds;
+        table[dev] = q;
+        known[dev] = true;
+    }
+    return table[dev];
+}
 
 template <typename T>
 static int upload(SmilModel *m, T **dst, const T *src, size_t n) {

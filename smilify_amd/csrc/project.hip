@@ -17,19 +17,11 @@ struct ProjectSet {
 
 __device__ __forceinline__ void project_point(const SmilCameras &c, const CamParams &cp, const ProjectSet &s, int b, int n, int p) {
     const float *X = s.pts + ((size_t)b * s.P + p) * 3;
-    const float x = X[0], y = X[1], z = X[2];
-    const float vx = x * cp.R[0] + y * cp.R[3] + z * cp.R[6] + cp.T[0];
-    const float vy = x * cp.R[1] + y * cp.R[4] + z * cp.R[7] + cp.T[1];
-    const float vz = x * cp.R[2] + y * cp.R[5] + z * cp.R[8] + cp.T[2];
-    const float xn = vx * cp.k00 / vz;
-    const float yn = vy * cp.k11 / vz;
+    float xn, yn, vz;
+    camera_project(cp, X[0], X[1], X[2], xn, yn, vz);
     const size_t o = (size_t)n * s.P + p;
     if (s.ndc) { s.ndc[o * 3] = xn; s.ndc[o * 3 + 1] = yn; s.ndc[o * 3 + 2] = vz; }
-    if (s.yx) {
-        const float h = 0.5f * (float)c.S;
-        s.yx[o * 2] = h - h * yn;
-        s.yx[o * 2 + 1] = h - h * xn;
-    }
+    if (s.yx) ndc_to_yx(0.5f * (float)c.S, xn, yn, s.yx + o * 2);
 }
 
 // grid (N, blocks of set 0 + blocks of set 1)
@@ -43,8 +35,10 @@ __global__ void __launch_bounds__(256) k_project(SmilCameras c, ProjectSet s0, P
     if (p < s.P) project_point(c, cp, s, b, n, p);
 }
 
-static int check_cameras(const SmilCameras *cam, const char *who) {
+int check_cameras(const SmilCameras *cam, const char *who, int frames) {
     SMIL_REQUIRE(cam, "%s: null camera argument", who);
+    SMIL_REQUIRE(frames == 0 || (frames > 0 && cam->N > 0 && cam->views > 0 && cam->N == frames * cam->views),
+                 "%s: %d images for %d frames x %d views", who, cam->N, frames > 0 ? frames : 0, cam->views);
     SMIL_REQUIRE(cam->N > 0 && cam->views > 0 && cam->N % cam->views == 0 && cam->S > 0, "%s: bad sizes N=%d views=%d S=%d", who, cam->N,
                  cam->views, cam->S);
     SMIL_REQUIRE(cam->R && cam->T && cam->fov && cam->nR > 0 && cam->nT > 0 && cam->nFov > 0, "%s: camera tables missing", who);
@@ -101,6 +95,9 @@ __global__ void __launch_bounds__(256) k_project_bwd(SmilCameras c, ProjectBwdSe
         const CamParams cp = load_camera(c, n);
         float fsum = 0.f;
         if (live) {
+            // The arithmetic of camera_project_bwd and unpack_d_ndc (camera.h), written out in this kernel's own order, the
+            // view-space point ahead of the loads of the upstream rows: with either helper called here the compiler contracts
+            // the sums of products below with other partners (fp-contract=fast) and the last bit of d_pts moves.
             const float vx = x * cp.R[0] + y * cp.R[3] + z * cp.R[6] + cp.T[0];
             const float vy = x * cp.R[1] + y * cp.R[4] + z * cp.R[7] + cp.T[1];
             const float vz = x * cp.R[2] + y * cp.R[5] + z * cp.R[8] + cp.T[2];
@@ -111,7 +108,7 @@ __global__ void __launch_bounds__(256) k_project_bwd(SmilCameras c, ProjectBwdSe
             if (s.d_ndc) {
                 const float2 raw = reinterpret_cast<const float2 *>(s.d_ndc)[o];
                 const float sc = s.d_ndc_scale ? s.d_ndc_scale[n] : 0.f;
-                if (sc != 0.f) {  // x * 2^32 + y in two's complement: a negative y borrowed one from the high word
+                if (sc != 0.f) {  // (= unpack_d_ndc) x * 2^32 + y in two's complement: a negative y borrowed one from the high word
                     const int qy = __float_as_int(raw.x), qx = __float_as_int(raw.y) - (qy >> 31);
                     dxn = sc > 0.f ? (float)qx * sc : 0.f;
                     dyn = sc > 0.f ? (float)qy * sc : 0.f;
@@ -146,8 +143,9 @@ __global__ void __launch_bounds__(256) k_project_bwd(SmilCameras c, ProjectBwdSe
 extern "C" int smil_project_backward(const SmilCameras *cam, const float *pts, int32_t P, const float *d_ndc,
                                      const float *d_yx, float *d_pts, float *d_fov_img, int32_t accumulate, const float *d_ndc_scale,
                                      void *stream) {
-    SMIL_REQUIRE(cam && pts, "smil_project_backward: null argument");
-    SMIL_REQUIRE(cam->N > 0 && cam->views > 0 && cam->N % cam->views == 0 && P > 0, "smil_project_backward: bad sizes");
+    if (int rc = check_cameras(cam, "smil_project_backward")) return rc;
+    SMIL_REQUIRE(pts, "smil_project_backward: null argument");
+    SMIL_REQUIRE(P > 0, "smil_project_backward: bad sizes");
     SMIL_REQUIRE(d_ndc || d_yx, "smil_project_backward: no upstream gradient");
     const ProjectBwdSet s0 = {pts, d_ndc, d_yx, d_pts, P, ceil_div(P, 256), accumulate, d_ndc_scale}, none = {nullptr, nullptr, nullptr, nullptr, 0, 0, 0, nullptr};
     hipLaunchKernelGGL(k_project_bwd, dim3(cam->N / cam->views, s0.blocks), dim3(256), 0, (hipStream_t)stream, *cam, s0, none, d_fov_img);
@@ -158,8 +156,9 @@ extern "C" int smil_project_backward(const SmilCameras *cam, const float *pts, i
 extern "C" int smil_project_backward2(const SmilCameras *cam, const float *pts_a, int32_t Pa, const float *d_ndc_a, const float *d_yx_a,
                                       float *d_pts_a, const float *pts_b, int32_t Pb, const float *d_ndc_b, const float *d_yx_b,
                                       float *d_pts_b, float *d_fov_img, const float *d_ndc_scale_a, void *stream) {
-    SMIL_REQUIRE(cam && pts_a && pts_b && d_pts_a && d_pts_b, "smil_project_backward2: null argument");
-    SMIL_REQUIRE(cam->N > 0 && cam->views > 0 && cam->N % cam->views == 0 && Pa > 0 && Pb > 0, "smil_project_backward2: bad sizes");
+    if (int rc = check_cameras(cam, "smil_project_backward2")) return rc;
+    SMIL_REQUIRE(pts_a && pts_b && d_pts_a && d_pts_b, "smil_project_backward2: null argument");
+    SMIL_REQUIRE(Pa > 0 && Pb > 0, "smil_project_backward2: bad sizes");
     SMIL_REQUIRE((d_ndc_a || d_yx_a) && (d_ndc_b || d_yx_b), "smil_project_backward2: no upstream gradient");
     const ProjectBwdSet s0 = {pts_a, d_ndc_a, d_yx_a, d_pts_a, Pa, ceil_div(Pa, 256), 0, d_ndc_scale_a},
                         s1 = {pts_b, d_ndc_b, d_yx_b, d_pts_b, Pb, ceil_div(Pb, 256), 0, nullptr};
@@ -182,14 +181,15 @@ __global__ void __launch_bounds__(64) k_clip_depth_bwd(SmilCameras c, SmilClipDe
         const int v = cd.vertex[first + e];
         const float dz = cd.dz[first + e];
         if (v < 0 || v >= V || dz == 0.f) continue;
-        atomicAdd(dv + 3 * v, dz * cp.R[2]); atomicAdd(dv + 3 * v + 1, dz * cp.R[5]); atomicAdd(dv + 3 * v + 2, dz * cp.R[8]);
+        clip_depth_bwd(cp, dz, dv + 3 * v);
     }
 }
 
 extern "C" int smil_clip_depth_backward(const SmilCameras *cam, const SmilClipDepth *cd, int32_t N, int32_t V, float *d_verts, void *stream) {
-    SMIL_REQUIRE(cam && cd && d_verts, "smil_clip_depth_backward: null argument");
+    if (int rc = check_cameras(cam, "smil_clip_depth_backward")) return rc;
+    SMIL_REQUIRE(cd && d_verts, "smil_clip_depth_backward: null argument");
     SMIL_REQUIRE(cd->vertex && cd->dz && cd->range && cd->counter, "smil_clip_depth_backward: incomplete SmilClipDepth");
-    SMIL_REQUIRE(N > 0 && V > 0 && cam->views > 0 && N == cam->N && N % cam->views == 0, "smil_clip_depth_backward: bad sizes");
+    SMIL_REQUIRE(V > 0 && N == cam->N, "smil_clip_depth_backward: bad sizes");
     hipLaunchKernelGGL(k_clip_depth_bwd, dim3(N), dim3(64), 0, (hipStream_t)stream, *cam, *cd, V, d_verts);
     SMIL_LAUNCH_CHECK();
     return SMIL_OK;

@@ -141,7 +141,11 @@ def test_forward_with_projection_equals_forward_then_projection(key, views, tran
     ndc_ref, yx_ref = eng.project_verts_and_joints(cams, ref["verts"], ref["joints"])
     for want in (dict(ndc=True, yx=True), dict(ndc=True, yx=False), dict(ndc=False, yx=True)):
         got = eng.lbs_forward(dm, beta, theta, project=dict(cams=cams, **want), **kw)
-        for k in ("verts", "joints", "A", "new_J"):
+        for k in ("A", "new_J"):  # (the same kernel on both routes)
+            assert torch.equal(got[k], ref[k]), k
+        # verts / ndc: the same helpers in the same order (csrc/skin.h, camera.h), contracted kernel by kernel: not bit-equal on
+        # the MI355X; joints / yx: a regressor row summed over 16 lanes here, over a wave's 64 there
+        for k in ("verts", "joints"):
             _close(got[k], ref[k], 1e-6, k)
         assert ("ndc" in got) == want["ndc"] and ("yx" in got) == want["yx"]
         if want["ndc"]:
