@@ -53,9 +53,10 @@ int smil_model_create(const SmilModelDesc *desc, SmilModel **out);
 void smil_model_destroy(SmilModel *m);
 int smil_model_dims(const SmilModel *m, int32_t dims[4]); /* V,F,J,nB */
 const char *smil_last_error(void);
-const char *smil_version(void);   /* "smilfit 0.3 (gfx950)".  0.3 = the layout of rounds 5 - 6: SmilLbsGrads carries clip_depth in front of
+const char *smil_version(void);   /* "smilfit 0.4 (gfx950; 0.3 + SmilCameras.principal)".  0.3 = the layout of rounds 5 - 6: SmilLbsGrads carries clip_depth in front of
                                     * beta_rows (which must hold 2 * B * nB_used + 16 floats), SmilRasterSettings ends in {tie_rule, clip_depth,
-                                    * image0}, smil_window_terms exists.  Callers zero-initialise every struct they pass and rebuild against
+                                    * image0}, smil_window_terms exists.  0.4: SmilCameras ends in {principal, nPrincipal} (a zero-initialised
+                                    * struct means what it meant in 0.3).  Callers zero-initialise every struct they pass and rebuild against
                                     * this header when the number changes: there is no binary compatibility across it. */
 
 /* ------------------------------------------------------------------------------------------
@@ -155,6 +156,9 @@ int smil_lbs_backward(const SmilModel *m, const SmilLbsInputs *in, const SmilLbs
  * Cameras + projection.  Replaces FoVPerspectiveCameras as configured by Renderer
  * (p3d_renderer.py:34-38,112-120) and transform_points_screen(...)[..., [1,0]] (:137).
  * Image n = frame * views + view.  A table with k rows is indexed n % k (k = 1, views or N).
+ * With `principal` the cameras are pytorch3d's PerspectiveCameras (NDC) instead: the same R, T, K00 = 1 / (aspect tan(fov/2)),
+ * K11 = 1 / tan(fov/2) and a principal point added to x_ndc, y_ndc - what a calibrated pinhole (cx, cy off centre) or a crop
+ * window of a larger frame needs.
  * ---------------------------------------------------------------------------------------- */
 typedef struct {
     int32_t N;          /* images = frames * views */
@@ -168,6 +172,13 @@ typedef struct {
     int32_t nFov;
     const float *aspect; /* (nAspect,) or NULL = 1 */
     int32_t nAspect;
+    const float *principal; /* (nPrincipal,2) principal point (px, py) in NDC, or NULL = centred (0, 0): pytorch3d's PerspectiveCameras,
+                               x_ndc = K00 x_view / z_view + px, y_ndc = K11 y_view / z_view + py; the screen transform is unchanged
+                               (x_s = S/2 - (S/2) x_ndc).  Under the OpenCV conversion R = R_cv^T diag(-1,-1,1) a pinhole u = fx x/z + cx
+                               on an S x S image has px = 1 - 2 cx / S, py = 1 - 2 cy / S.  Values outside [-1, 1] are valid (a crop
+                               window whose principal point lies outside it).  A constant of the fit: no entry point returns a
+                               gradient on it, and the backward entry points' results do not depend on it. */
+    int32_t nPrincipal;     /* > 0 when principal is given */
 } SmilCameras;
 
 /* pts (frames,P,3) world -> ndc (N,P,3) = (x_ndc, y_ndc, z_view); yx (N,P,2) = (y_s, x_s) px. Either
@@ -201,7 +212,9 @@ int smil_fov_reduce(const SmilCameras *cam, const float *d_fov_img, float *d_fov
  * + Renderer's two projections of one fit iteration (fitter.py:270-290, p3d_renderer.py:137-146).  Skinning, joint regression and
  * both projections are ONE kernel per frame and `verts` is written once and not read back where the model's joints are static
  * (nothing is gathered from the frame's vertices: any mesh size) or the frame's vertices fit half a CU's LDS (3 V floats <= 80 KB);
- * otherwise the separate kernels run.  Outputs are those of the separate calls. */
+ * otherwise the separate kernels run.  Outputs are those of the separate calls: to rounding (1e-6 of the largest entry) through the
+ * fused kernel, and BIT FOR BIT where the separate kernels run - which they always do for cameras with a principal point: with a
+ * table this call is specified to return exactly what smil_lbs_forward followed by smil_project returns. */
 int smil_lbs_forward_project(const SmilModel *m, const SmilLbsInputs *in, const SmilLbsOutputs *out, const SmilCameras *cam,
                              float *ndc, float *yx, void *stream);
 

@@ -79,7 +79,7 @@ class ClipDepth(Structure):
 class Cameras(Structure):
     _fields_ = [("N", c_int32), ("views", c_int32), ("S", c_int32), ("R", c_void_p), ("nR", c_int32),
                 ("T", c_void_p), ("nT", c_int32), ("fov", c_void_p), ("nFov", c_int32), ("aspect", c_void_p),
-                ("nAspect", c_int32)]
+                ("nAspect", c_int32), ("principal", c_void_p), ("nPrincipal", c_int32)]
 
 
 class RasterSettings(Structure):

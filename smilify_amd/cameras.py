@@ -5,7 +5,9 @@
 * ``FoVCameras`` - the small mutable holder behind ``Renderer.cameras``: the reference assigns
   ``renderer.cameras.fov = self.fov`` every forward (smal_fitter/fitter.py:285).
 * ``opencv_to_fov_camera`` - the OpenCV/SLEAP -> FoV-camera conversion of
-  smal_fitter/sleap_data/sleap_multiview_dataset.py:197-223.
+  smal_fitter/sleap_data/sleap_multiview_dataset.py:197-223 (it keeps fx, fy and drops cx, cy, as the reference does).
+* ``opencv_to_pinhole_camera`` / ``crop_intrinsics`` / ``crop_points_yx`` - the same conversion with the principal point kept, and
+  square crop windows of a larger frame (an extension: the reference loses the crop offset, sleap_multiview_dataset.py:938-948).
 """
 from __future__ import annotations
 
@@ -42,12 +44,14 @@ def look_at_view_transform(dist=1.0, elev=0.0, azim=0.0, degrees: bool = True, d
 
 
 class FoVCameras:
-    """Mutable camera table: ``R (n,3,3)``, ``T (n,3)``, ``fov (n,)`` degrees, ``aspect_ratio (n,)`` or None."""
+    """Mutable camera table: ``R (n,3,3)``, ``T (n,3)``, ``fov (n,)`` degrees, ``aspect_ratio (n,)`` or None,
+    ``principal_point (k,2)`` = ``(px, py)`` in NDC or None (centred)."""
 
     def __init__(self, R: torch.Tensor, T: torch.Tensor, fov: torch.Tensor, aspect_ratio: Optional[torch.Tensor] = None,
-                 znear: float = 0.001, zfar: float = 1000.0):
+                 znear: float = 0.001, zfar: float = 1000.0, principal_point: Optional[torch.Tensor] = None):
         self.R, self.T, self.fov, self.aspect_ratio = R, T, fov, aspect_ratio
         self.znear, self.zfar = znear, zfar
+        self.principal_point = principal_point
 
     def __len__(self) -> int:
         return int(max(self.R.shape[0], self.T.shape[0], self.fov.numel()))
@@ -61,3 +65,40 @@ def opencv_to_fov_camera(R_cv: np.ndarray, t_cv: np.ndarray, K: np.ndarray, imag
     aspect = float((width * fy) / (height * fx + 1e-12))
     flip = np.diag([-1.0, -1.0, 1.0]).astype(np.float32)
     return (np.asarray(R_cv, np.float32).T @ flip).astype(np.float32), (flip @ np.asarray(t_cv, np.float32)).astype(np.float32), fov_y, aspect
+
+
+def crop_intrinsics(K: np.ndarray, window, S) -> np.ndarray:
+    """Intrinsics of the ``S`` x ``S`` image that shows the square ``window = (x0, y0, side)`` of the source image (source pixels; may be
+    fractional and may reach past the image): with ``s = S / side``, ``fx' = s fx``, ``fy' = s fy``, ``cx' = s (cx - x0)``,
+    ``cy' = s (cy - y0)``.  float64."""
+    x0, y0, side = (float(w) for w in window)
+    s = float(S) / side
+    K2 = np.array(K, dtype=np.float64, copy=True)
+    K2[0, 0], K2[1, 1] = s * K2[0, 0], s * K2[1, 1]
+    K2[0, 2], K2[1, 2] = s * (K2[0, 2] - x0), s * (K2[1, 2] - y0)
+    return K2
+
+
+def crop_points_yx(yx, window, S):
+    """2-D targets ``(..., 2)`` in ``(y, x)`` source pixels -> pixels of the ``S`` x ``S`` image of ``window = (x0, y0, side)``:
+    what ``crop_intrinsics`` does to a projection.  numpy array or torch tensor, returned as given."""
+    x0, y0, side = (float(w) for w in window)
+    s = float(S) / side
+    if isinstance(yx, torch.Tensor):
+        return (yx - yx.new_tensor([y0, x0])) * s
+    yx = np.asarray(yx)
+    return (yx - np.array([y0, x0], dtype=yx.dtype if yx.dtype.kind == "f" else np.float64)) * s
+
+
+def opencv_to_pinhole_camera(R_cv: np.ndarray, t_cv: np.ndarray, K: np.ndarray, S, window=None):
+    """``(R, T, fov_y_degrees, aspect_ratio, principal_point)`` of the camera that reproduces the whole pinhole calibration
+    ``u = fx x / z + cx``, ``v = fy y / z + cy`` on an ``S`` x ``S`` image: the first four exactly as ``opencv_to_fov_camera(R_cv, t_cv, K,
+    (S, S))`` returns them, and ``principal_point = (1 - 2 cx / S, 1 - 2 cy / S)`` float64, the NDC offset under that function's
+    ``R = R_cv^T diag(-1, -1, 1)`` (``Renderer.set_camera_parameters(..., principal_point=)``).  ``window = (x0, y0, side)``: the
+    calibration is of a larger source image and the ``S`` x ``S`` image shows that square of it (``crop_intrinsics``); the principal
+    point of such a camera may lie outside [-1, 1]."""
+    if window is not None:
+        K = crop_intrinsics(K, window, S)
+    R, T, fov_y, aspect = opencv_to_fov_camera(R_cv, t_cv, K, (S, S))
+    pp = np.array([1.0 - 2.0 * float(K[0, 2]) / float(S), 1.0 - 2.0 * float(K[1, 2]) / float(S)], dtype=np.float64)
+    return R, T, fov_y, aspect, pp

@@ -623,7 +623,10 @@ static int lbs_forward_impl(const SmilModel *m, const SmilLbsInputs *in, const S
         nS_skin = B;
     }
     const float *trans_after = (in->trans_after_joints && in->trans) ? in->trans : nullptr;
-    if (cam && cam->views <= FWD_FUSED_MAX_VIEWS && fwd_fused_lds_bytes(m, cam->views) <= fused_lds_limit()) {
+    // Cameras with a principal point take the separate kernels below: with a table this entry point returns the BITS of
+    // smil_lbs_forward followed by smil_project (tests/test_gpu_pinhole.py), which the fused kernel cannot give - it contracts the
+    // skinning's sums of products its own way and sums a regressor row over sixteen lanes (see its head)
+    if (cam && !cam->principal && cam->views <= FWD_FUSED_MAX_VIEWS && fwd_fused_lds_bytes(m, cam->views) <= fused_lds_limit()) {
         // skinning, joint regression and both projections in one kernel per frame (the frame's vertices stay in LDS)
         SkinProjectArgs a;
         a.cam = *cam;
@@ -654,7 +657,7 @@ static int lbs_forward_impl(const SmilModel *m, const SmilLbsInputs *in, const S
                            out->verts, trans_after, out->joints, V, J);
         SMIL_LAUNCH_CHECK();
     }
-    if (cam) {  // (a mesh or a camera rig beyond the fused kernel's LDS: the projection as its own launch)
+    if (cam) {  // (a mesh or a camera rig beyond the fused kernel's LDS, or cameras with a principal point: the projection as its own launch)
         if (ndc && yx) return smil_project2(cam, out->verts, V, ndc, nullptr, out->joints, J, nullptr, yx, stream);
         if (ndc) return smil_project(cam, out->verts, V, ndc, nullptr, stream);
         return smil_project(cam, out->joints, J, nullptr, yx, stream);

@@ -6,6 +6,7 @@
 //   X_view = X_world R + T ;  x_ndc = X_view.x K00 / z , y_ndc = X_view.y K11 / z , z = X_view.z
 //   K00 = 2 znear / (2 aspect tan(fov/2) znear) , K11 = 2 znear / (2 tan(fov/2) znear)
 //   x_s = S/2 - (S/2) x_ndc ; y_s likewise ; the reference returns (y_s, x_s).
+// With a principal point (SmilCameras.principal; pytorch3d's PerspectiveCameras in NDC): x_ndc = X_view.x K00 / z + px, y likewise.
 #include "common.h"
 
 // One or two point sets (e.g. the vertices -> NDC for the rasteriser and the joints -> screen for the 2-D loss) per launch.
@@ -15,24 +16,32 @@ struct ProjectSet {
     int P, blocks;     // points per frame; thread blocks (of 256 points) this set occupies in grid.x
 };
 
+template <bool PP>
 __device__ __forceinline__ void project_point(const SmilCameras &c, const CamParams &cp, const ProjectSet &s, int b, int n, int p) {
     const float *X = s.pts + ((size_t)b * s.P + p) * 3;
     float xn, yn, vz;
-    camera_project(cp, X[0], X[1], X[2], xn, yn, vz);
+    camera_project<PP>(cp, X[0], X[1], X[2], xn, yn, vz);
     const size_t o = (size_t)n * s.P + p;
     if (s.ndc) { s.ndc[o * 3] = xn; s.ndc[o * 3 + 1] = yn; s.ndc[o * 3 + 2] = vz; }
     if (s.yx) ndc_to_yx(0.5f * (float)c.S, xn, yn, s.yx + o * 2);
 }
 
-// grid (N, blocks of set 0 + blocks of set 1)
+// grid (N, blocks of set 0 + blocks of set 1).  PP: the cameras carry a principal point (camera.h)
+template <bool PP>
 __global__ void __launch_bounds__(256) k_project(SmilCameras c, ProjectSet s0, ProjectSet s1) {
     const int n = blockIdx.x;  // image on x: gridDim.y stops at 65 535
     const int b = n / c.views;
-    const CamParams cp = load_camera(c, n);
+    const CamParams cp = load_camera<PP>(c, n);
     const bool second = (int)blockIdx.y >= s0.blocks;
     const ProjectSet &s = second ? s1 : s0;
     const int p = ((int)blockIdx.y - (second ? s0.blocks : 0)) * blockDim.x + threadIdx.x;
-    if (p < s.P) project_point(c, cp, s, b, n, p);
+    if (p < s.P) project_point<PP>(c, cp, s, b, n, p);
+}
+
+static void launch_project(const SmilCameras *cam, const ProjectSet &s0, const ProjectSet &s1, hipStream_t stream) {
+    const dim3 grid(cam->N, s0.blocks + s1.blocks);
+    if (cam->principal) hipLaunchKernelGGL(k_project<true>, grid, dim3(256), 0, stream, *cam, s0, s1);
+    else hipLaunchKernelGGL(k_project<false>, grid, dim3(256), 0, stream, *cam, s0, s1);
 }
 
 int check_cameras(const SmilCameras *cam, const char *who, int frames) {
@@ -43,6 +52,7 @@ int check_cameras(const SmilCameras *cam, const char *who, int frames) {
                  cam->views, cam->S);
     SMIL_REQUIRE(cam->R && cam->T && cam->fov && cam->nR > 0 && cam->nT > 0 && cam->nFov > 0, "%s: camera tables missing", who);
     SMIL_REQUIRE(!cam->aspect || cam->nAspect > 0, "%s: aspect table empty", who);
+    SMIL_REQUIRE(!cam->principal || cam->nPrincipal > 0, "%s: principal-point table empty (nPrincipal=%d)", who, cam->nPrincipal);
     return SMIL_OK;
 }
 
@@ -50,7 +60,7 @@ extern "C" int smil_project(const SmilCameras *cam, const float *pts, int32_t P,
     if (int rc = check_cameras(cam, "smil_project")) return rc;
     SMIL_REQUIRE(pts && P > 0, "smil_project: bad points argument (P=%d)", P);
     const ProjectSet s0 = {pts, ndc, yx, P, ceil_div(P, 256)}, none = {nullptr, nullptr, nullptr, 0, 0};
-    hipLaunchKernelGGL(k_project, dim3(cam->N, s0.blocks), dim3(256), 0, (hipStream_t)stream, *cam, s0, none);
+    launch_project(cam, s0, none, (hipStream_t)stream);
     SMIL_LAUNCH_CHECK();
     return SMIL_OK;
 }
@@ -60,7 +70,7 @@ extern "C" int smil_project2(const SmilCameras *cam, const float *pts_a, int32_t
     if (int rc = check_cameras(cam, "smil_project2")) return rc;
     SMIL_REQUIRE(pts_a && Pa > 0 && pts_b && Pb > 0, "smil_project2: bad points arguments (Pa=%d Pb=%d)", Pa, Pb);
     const ProjectSet s0 = {pts_a, ndc_a, yx_a, Pa, ceil_div(Pa, 256)}, s1 = {pts_b, ndc_b, yx_b, Pb, ceil_div(Pb, 256)};
-    hipLaunchKernelGGL(k_project, dim3(cam->N, s0.blocks + s1.blocks), dim3(256), 0, (hipStream_t)stream, *cam, s0, s1);
+    launch_project(cam, s0, s1, (hipStream_t)stream);
     SMIL_LAUNCH_CHECK();
     return SMIL_OK;
 }
@@ -75,7 +85,8 @@ struct ProjectBwdSet {
 };
 
 // grid (frames, blocks of set 0 + blocks of set 1): each thread owns one world point and walks the views of its frame, so
-// d_pts needs no atomics; the per-image fov term is block-reduced and added once per block.
+// d_pts needs no atomics; the per-image fov term is block-reduced and added once per block.  A principal point (c.principal) does
+// not enter: xn, yn below are recomputed from the world point, unshifted, which is what dvz and the fov sum take (camera.h).
 __global__ void __launch_bounds__(256) k_project_bwd(SmilCameras c, ProjectBwdSet s0, ProjectBwdSet s1, float *__restrict__ d_fov_img) {
     __shared__ float red[16];
     const int b = blockIdx.x;

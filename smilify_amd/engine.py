@@ -133,7 +133,9 @@ class DeviceModel:
 
 @dataclass
 class CameraSet:
-    """FoV-perspective cameras; tables with k rows are indexed ``image % k`` (k = 1, views or N)."""
+    """FoV-perspective cameras; tables with k rows are indexed ``image % k`` (k = 1, views or N).  With ``principal`` (k,2), the
+    principal point ``(px, py)`` in NDC, they are pytorch3d's ``PerspectiveCameras``: ``x_ndc = K00 x / z + px`` (None: centred).  The
+    table is a constant: it carries no gradient."""
 
     R: torch.Tensor  # (nR,3,3)
     T: torch.Tensor  # (nT,3)
@@ -141,6 +143,7 @@ class CameraSet:
     aspect: Optional[torch.Tensor]
     views: int
     S: int
+    principal: Optional[torch.Tensor] = None  # (nPrincipal,2) float32, contiguous
 
     def struct(self, N: int) -> _lib.Cameras:
         c = _lib.Cameras()
@@ -152,7 +155,18 @@ class CameraSet:
             c.aspect, c.nAspect = self.aspect.data_ptr(), self.aspect.numel()
         else:
             c.aspect, c.nAspect = None, 0
-        for name, k in (("R", c.nR), ("T", c.nT), ("fov", c.nFov)):
+        tables = [("R", c.nR), ("T", c.nT), ("fov", c.nFov)]
+        if self.principal is not None:
+            pp = self.principal
+            if pp.requires_grad:
+                raise NotImplementedError("the principal point carries no gradient: pass a tensor that does not require one")
+            if pp.dim() != 2 or pp.shape[1] != 2 or pp.dtype != torch.float32 or not pp.is_contiguous():
+                raise _lib.SmilError(f"camera table principal must be a contiguous float32 (k,2) tensor, got {tuple(pp.shape)} {pp.dtype}")
+            c.principal, c.nPrincipal = pp.data_ptr(), pp.shape[0]
+            tables.append(("principal", c.nPrincipal))
+        else:
+            c.principal, c.nPrincipal = None, 0
+        for name, k in tables:
             if k not in (1, self.views, N):
                 raise _lib.SmilError(f"camera table {name} has {k} rows; expected 1, views={self.views} or N={N}")
         return c
@@ -588,7 +602,7 @@ def render_colour(model: DeviceModel, cams: CameraSet, verts: torch.Tensor, mesh
         def rows(t):  # camera tables with one row per image follow the slice; shared / per-view ones stay
             return t if t is None or t.shape[0] != N or n1 - n0 == N else t[n0:n1].contiguous()
         part = CameraSet(rows(cams.R), rows(cams.T), rows(cams.fov.reshape(-1)), rows(None if cams.aspect is None else cams.aspect.reshape(-1)),
-                         views, S)
+                         views, S, rows(cams.principal))
         c = part.struct(n1 - n0)
         _lib.check(lib.smil_render_colour(model.handle, ctypes.byref(c), _ptr(verts[f0:f1]), _ptr(verts_ndc[n0:n1]), rgb,
                                           _ptr(image[n0:n1]), _ptr(None if p2f is None else p2f[n0:n1]), _ptr(ws), _stream()),

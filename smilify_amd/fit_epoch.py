@@ -122,7 +122,8 @@ versioned = lambda t: None if t is None else (t.data_ptr(), t._version)  # noqa:
 addressed = lambda t: None if t is None else (t.data_ptr(), tuple(t.shape))  # noqa: E731  (what a captured launch bakes in)
 weights_part = lambda weights: tuple(float(w) for w in weights)  # noqa: E731
 masks_part = lambda f: versioned(f.global_mask) + versioned(f.rotation_mask)  # noqa: E731
-cameras_part = lambda renderer, stamp: (stamp(renderer.cameras.R), stamp(renderer.cameras.T), stamp(renderer.cameras.aspect_ratio))  # noqa: E731
+cameras_part = lambda renderer, stamp: (stamp(renderer.cameras.R), stamp(renderer.cameras.T), stamp(renderer.cameras.aspect_ratio),  # noqa: E731
+                                        stamp(getattr(renderer.cameras, "principal_point", None)))
 raster_part = lambda renderer: bytes(renderer.raster_settings)  # noqa: E731  (the whole struct: blur, sigma, K, clipping plane, tie rule)
 
 

@@ -52,8 +52,10 @@ class Evaluation:
         # launches is part of what a captured iteration and the kernel traces pin - do not move this to the top
         cam, fov = f.renderer.cameras, f.fov.detach().reshape(-1).contiguous()
         self.img_idx = None if self.idx is None else (self.idx[:, None] * f.views + torch.arange(f.views, device=dev)[None]).reshape(-1)
+        pp = f.renderer._principal()
         self.cams = engine.CameraSet(self.camera(cam.R), self.camera(cam.T), self.camera(fov),
-                                     None if cam.aspect_ratio is None else self.camera(cam.aspect_ratio.reshape(-1)), f.views, f.image_size)
+                                     None if cam.aspect_ratio is None else self.camera(cam.aspect_ratio.reshape(-1)), f.views, f.image_size,
+                                     None if pp is None else self.camera(pp))
         self.lbs = self.g_lbs = self.d_fov_sel = self.yx = self.tj = self.vis = self.d_yx = self.d_ndc = self.d_ndc_scale = None
         self.loss_img = self.pscale = self.cd = None  # (all of these stay None when no term needs the mesh)
 

@@ -148,10 +148,11 @@ class SMALFitter(nn.Module):
     _sil_sum = property(lambda self: self._cache.sil_sum)
     _vis_dev = property(lambda self: self._cache.vis)
 
-    def set_cameras(self, R, T, fov=None, aspect_ratio=None):
-        """Install per-view or per-image cameras; ``fov`` (if given) replaces the trainable parameter."""
+    def set_cameras(self, R, T, fov=None, aspect_ratio=None, principal_point=None):
+        """Install per-view or per-image cameras; ``fov`` (if given) replaces the trainable parameter.  ``principal_point``: ``(k,2)``
+        NDC offsets ``(px, py)`` of calibrated pinhole cameras or crop windows (``Renderer.set_camera_parameters``); a constant of the fit."""
         f = self.fov.data if fov is None else fov
-        self.renderer.set_camera_parameters(R, T, f, aspect_ratio)
+        self.renderer.set_camera_parameters(R, T, f, aspect_ratio, principal_point)
         if fov is not None:
             self.fov = nn.Parameter(self.renderer.cameras.fov.clone())
         self._cache.invalidate("tables")  # a captured iteration holds the old camera tables' addresses
@@ -315,7 +316,8 @@ class SMALFitter(nn.Module):
                         return t_ if t_ is None or t_.shape[0] != self.num_images * views else t_.index_select(0, img_rows)
                     fov = self.fov.detach().reshape(-1)
                     self.renderer.cameras = FoVCameras(table(cam_all.R, 9), table(cam_all.T, 3), table(fov, 1),
-                                                       table(cam_all.aspect_ratio, 1), cam_all.znear, cam_all.zfar)
+                                                       table(cam_all.aspect_ratio, 1), cam_all.znear, cam_all.zfar,
+                                                       table(getattr(cam_all, "principal_point", None), 2))
                     faces_b = self.smal_model.faces[None].expand(n, -1, -1)
                     colour = self.renderer.colour
                     out = self.renderer(verts.contiguous(), canon, faces_b, render_texture=colour)

@@ -40,7 +40,7 @@ class _RenderFunction(torch.autograd.Function):
     def forward(ctx, dm, cams, S, rs, joints_only, vertices, points, fov):
         v = vertices.detach().float().contiguous()
         p = points.detach().float().contiguous()
-        cams = engine.CameraSet(cams.R, cams.T, fov.detach().float().contiguous(), cams.aspect, cams.views, S)
+        cams = engine.CameraSet(cams.R, cams.T, fov.detach().float().contiguous(), cams.aspect, cams.views, S, cams.principal)
         _, yx = engine.project(cams, p, want_ndc=False)
         ctx.dm, ctx.cams, ctx.S, ctx.rs, ctx.joints_only = dm, cams, S, rs, joints_only
         if joints_only:
@@ -98,8 +98,10 @@ class Renderer(torch.nn.Module):
         self._bound_model = dm
         self._bound_faces_ok = {}
 
-    def set_camera_parameters(self, R, T, fov, aspect_ratio=None):
-        """Same contract as reference p3d_renderer.py:72-125 (fov squeezed to 1-D, scalar aspect broadcast)."""
+    def set_camera_parameters(self, R, T, fov, aspect_ratio=None, principal_point=None):
+        """Same contract as reference p3d_renderer.py:72-125 (fov squeezed to 1-D, scalar aspect broadcast).  ``principal_point``
+        (an extension): ``(k,2)`` or ``(2,)`` values ``(px, py)`` in NDC, k = 1, views or images - the cameras become pytorch3d's
+        ``PerspectiveCameras``, ``x_ndc = K00 x / z + px`` (``cameras.opencv_to_pinhole_camera``).  A constant: no gradient."""
         dev = self.device
         R = R.to(device=dev, dtype=torch.float32).reshape(-1, 3, 3).contiguous()
         T = T.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
@@ -114,7 +116,17 @@ class Renderer(torch.nn.Module):
             aspect_ratio = aspect_ratio.to(device=dev, dtype=torch.float32).reshape(-1)
             if aspect_ratio.numel() == 1 and fov.numel() > 1:
                 aspect_ratio = aspect_ratio.expand_as(fov).contiguous()
-        self.cameras = FoVCameras(R, T, fov, aspect_ratio, self.DEFAULT_ZNEAR, self.DEFAULT_ZFAR)
+        self.cameras = FoVCameras(R, T, fov, aspect_ratio, self.DEFAULT_ZNEAR, self.DEFAULT_ZFAR, self._principal_table(principal_point))
+
+    def _principal_table(self, principal_point) -> Optional[torch.Tensor]:
+        if principal_point is None:
+            return None
+        if isinstance(principal_point, torch.Tensor) and principal_point.requires_grad:
+            raise NotImplementedError("the principal point carries no gradient: pass a tensor that does not require one")
+        pp = torch.as_tensor(principal_point).to(device=self.device, dtype=torch.float32)
+        if pp.numel() == 0 or pp.numel() % 2 or (pp.dim() > 1 and pp.shape[-1] != 2):
+            raise ValueError(f"principal_point must be (k,2) values (px, py), got shape {tuple(pp.shape)}")
+        return pp.reshape(-1, 2).contiguous()
 
     def _device_model(self, faces: torch.Tensor, V: int) -> engine.DeviceModel:
         """Face table on the GPU for the mesh topology passed to ``forward`` (the reference rasterises whatever faces it is
@@ -149,7 +161,17 @@ class Renderer(torch.nn.Module):
     def _camera_set(self) -> engine.CameraSet:
         cam = self.cameras
         return engine.CameraSet(cam.R.contiguous(), cam.T.contiguous(), cam.fov.detach().float().reshape(-1).contiguous(),
-                                None if cam.aspect_ratio is None else cam.aspect_ratio.contiguous(), self.views, self.image_size)
+                                None if cam.aspect_ratio is None else cam.aspect_ratio.contiguous(), self.views, self.image_size,
+                                self._principal())
+
+    def _principal(self) -> Optional[torch.Tensor]:
+        """``cameras.principal_point`` as the kernels take it (the holder is mutable: callers may have assigned any tensor)."""
+        pp = getattr(self.cameras, "principal_point", None)
+        if pp is None:
+            return None
+        if pp.requires_grad:
+            raise NotImplementedError("the principal point carries no gradient: pass a tensor that does not require one")
+        return pp.contiguous()
 
     def render_colour(self, vertices, faces) -> torch.Tensor:
         """The reference's colour branch (p3d_renderer.py:54-70,148-150: hard rasteriser, K = 1, + HardPhongShader, point light at
@@ -167,9 +189,10 @@ class Renderer(torch.nn.Module):
         B = vertices.shape[0]
         views = self.views
         N = B * views
+        pp = self._principal()
         cs = engine.CameraSet(cam.R.contiguous(), cam.T.contiguous(), cam.fov, None if cam.aspect_ratio is None else cam.aspect_ratio.contiguous(),
-                              views, self.image_size)
-        for name, k in (("R", cam.R.shape[0]), ("T", cam.T.shape[0]), ("fov", cam.fov.numel())):
+                              views, self.image_size, pp)
+        for name, k in (("R", cam.R.shape[0]), ("T", cam.T.shape[0]), ("fov", cam.fov.numel())) + (() if pp is None else (("principal_point", pp.shape[0]),)):
             if k not in (1, views, N):
                 raise ValueError(f"cameras.{name} has {k} entries for {N} images")
         dm = None if joints_only else self._device_model(faces, vertices.shape[1])

@@ -66,19 +66,23 @@ def get_projection_matrix(cam: dict) -> np.ndarray:
     return np.asarray(cam["K"], np.float64) @ np.hstack([np.asarray(cam["R"], np.float64), np.asarray(cam["t"], np.float64).reshape(3, 1)])
 
 
-def projection_matrix_from_fov_camera(R, T, fov, aspect_ratio=1.0, image_size=512) -> np.ndarray:
+def projection_matrix_from_fov_camera(R, T, fov, aspect_ratio=1.0, image_size=512, principal_point=None) -> np.ndarray:
     """The 3 x 4 pixel projection of one FoV camera of this library: ``X_view = X R + T`` (row vectors),
     ``x_ndc = X_view.x / (aspect tan(fov / 2) X_view.z)``, ``y_ndc = X_view.y / (tan(fov / 2) X_view.z)`` and the screen transform
     ``x = W/2 - (W/2) x_ndc``, ``y = H/2 - (H/2) y_ndc`` of ``Renderer.forward(..., joints_only=True)``, whose output is ``(y, x)``.
     ``P @ [X, 1]`` is ``(x w, y w, w)``: tracks triangulated through it live in the frame the fitter renders in.  fov in degrees;
-    image_size an int or ``(H, W)``."""
+    image_size an int or ``(H, W)``.  ``principal_point = (px, py)``: the camera's NDC offset (``x_ndc + px``, ``y_ndc + py``; None:
+    centred), so that a camera handed to the renderer with it and to ``triangulate_all`` describes the same pixels."""
     R = np.asarray(torch.as_tensor(R).detach().cpu().numpy(), np.float64).reshape(3, 3)
     T = np.asarray(torch.as_tensor(T).detach().cpu().numpy(), np.float64).reshape(3)
     H, W = (image_size, image_size) if np.isscalar(image_size) else image_size
     t = np.tan(np.radians(float(fov)) / 2.0)
     k00, k11 = 1.0 / (float(aspect_ratio) * t), 1.0 / t
     rows = np.hstack([R.T, T[:, None]])  # row i: X_view[i] = rows[i] . [X, 1]
-    return np.stack([0.5 * W * (rows[2] - k00 * rows[0]), 0.5 * H * (rows[2] - k11 * rows[1]), rows[2]])
+    if principal_point is None:
+        return np.stack([0.5 * W * (rows[2] - k00 * rows[0]), 0.5 * H * (rows[2] - k11 * rows[1]), rows[2]])
+    px, py = (float(v) for v in np.asarray(torch.as_tensor(principal_point).detach().cpu().numpy(), np.float64).reshape(2))
+    return np.stack([0.5 * W * ((1.0 - px) * rows[2] - k00 * rows[0]), 0.5 * H * ((1.0 - py) * rows[2] - k11 * rows[1]), rows[2]])
 
 
 def triangulate_arrays(P, obs, scores=None, K=None, dist=None, confidence_threshold=0.3, min_views=2, reproj_threshold=15.0,
