@@ -94,9 +94,9 @@ __device__ __forceinline__ float camera_project_bwd(const CamParams &cp, float x
 }
 
 // One point's row of d_ndc (N,P,2) of an image whose factor `scale` is not 0 (0: the row is two plain floats, and the caller
-// takes them as they are): what the fused rasteriser left (the encoder: the two `pack` lambdas at raster.hip:2078-2081 and
-// :2500-2503), x and y as two 32-bit fixed-point numbers in one 64-bit word, x * 2^32 + y in two's complement - a negative y
-// borrowed one from the high word - times `scale`; under a negative factor the row reads as zero.
+// takes them as they are): what the fused rasteriser left (the encoder: `pack_fx2`, raster_common.h), x and y as two 32-bit
+// fixed-point numbers in one 64-bit word, x * 2^32 + y in two's complement - a negative y borrowed one from the high word - times
+// `scale`; under a negative factor the row reads as zero.
 __device__ __forceinline__ void unpack_d_ndc(const float2 &raw, float scale, float &dxn, float &dyn) {
     const int qy = __float_as_int(raw.x), qx = __float_as_int(raw.y) - (qy >> 31);
     dxn = scale > 0.f ? (float)qx * scale : 0.f;

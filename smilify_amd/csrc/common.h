@@ -44,7 +44,7 @@ void smil_set_error(const char *fmt, ...);
 struct SmilModel {
     int V = 0, F = 0, J = 0, nB = 0;
     int max_depth = 0;
-    int max_valence = 0;          // most faces sharing one vertex (bounds the gradient a vertex can receive, raster.hip)
+    int max_valence = 0;          // most faces sharing one vertex (bounds the gradient a vertex can receive: k_raster_setup's img_bound)
     bool static_joints = false;
     int jreg_nnz = 0;
     int bone_nnz = 0;
@@ -97,6 +97,10 @@ struct ColourSetup {
 size_t smil_colour_setup_bytes(const SmilModel *m, int N, int S);
 int smil_colour_setup(const SmilModel *m, const float *verts_ndc, int N, int S, float z_clip, void *workspace, hipStream_t stream,
                       ColourSetup *out);
+
+// the two paths share the setup kernel's 8x8-pixel tiles and its pixel centres (pixel index i of a flipped axis, S pixels)
+constexpr int TILE = 8;
+__device__ __forceinline__ float pix_to_ndc(int i, int S) { return -1.0f + (2.0f * (float)i + 1.0f) / (float)S; }
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 

@@ -26,12 +26,9 @@
 
 #include "common.h"
 
-#define CTILE 8
 #define COLOUR_WAVES_PER_CU 28  // single-wave workgroups per CU of the tile kernel's grid (7 per SIMD: what its 67 VGPRs allow)
 #define C_EPS 1e-8f              // pytorch3d kEpsilon of the rasteriser
 #define N_EPS 1e-6f              // F.normalize eps of the normals and the light / view directions
-
-__device__ __forceinline__ float cpix_to_ndc(int i, int S) { return -1.0f + (2.0f * (float)i + 1.0f) / (float)S; }
 
 // ---------------------------------------------------------------------------------------------
 // per-frame vertex normals (Meshes.verts_normals_packed)
@@ -106,20 +103,21 @@ __global__ void __launch_bounds__(64) k_colour_tiles(ColourArgs a) {
     const uint32_t excl = incl - cnt;
     if (lane >= nk) incl = 0xFFFFFFFFu;
 
-    const int xl = lane & (CTILE - 1), yl = lane >> 3;
+    const int xl = lane & (TILE - 1), yl = lane >> 3;
     for (uint32_t t = blockIdx.x; t < total; t += gridDim.x) {
         const int k = __popcll(__ballot(incl <= t));  // (lanes >= nk never count)
         const uint32_t slot = t - (uint32_t)read_lane((int)excl, k);
         const int part = k % cs.n_parts, cls = k / cs.n_parts;
+        // (k_raster_setup's own formula, from (class, slot); the silhouette kernels' `item_at` starts from the item's number in its partition)
         const size_t idx = (size_t)(2 * part + (cls >> 1)) * cs.item_cap + ((cls & 1) ? cs.item_cap - 1u - slot : slot);
         const uint4 it = cs.items[idx];
         const int img = (int)(it.x / (uint32_t)n_tiles), tile = (int)(it.x % (uint32_t)n_tiles);
         const int tx = tile % tiles_x, ty = tile / tiles_x;
-        const int xo = tx * CTILE + xl, yo = ty * CTILE + yl;
+        const int xo = tx * TILE + xl, yo = ty * TILE + yl;
         const bool in_img = xo < S && yo < S;
         // pixel centre relative to the tile's centre (column xo holds image x index S - 1 - xo, as on the silhouette path)
-        const float cx = cpix_to_ndc(S - 1 - (tx * CTILE + CTILE / 2), S), cy = cpix_to_ndc(S - 1 - (ty * CTILE + CTILE / 2), S);
-        const float dx = cpix_to_ndc(S - 1 - xo, S) - cx, dy = cpix_to_ndc(S - 1 - yo, S) - cy;
+        const float cx = pix_to_ndc(S - 1 - (tx * TILE + TILE / 2), S), cy = pix_to_ndc(S - 1 - (ty * TILE + TILE / 2), S);
+        const float dx = pix_to_ndc(S - 1 - xo, S) - cx, dy = pix_to_ndc(S - 1 - yo, S) - cy;
 
         const float *vn = a.verts_ndc + (size_t)img * V * 3;
         const float *xv_n = cs.xv + (size_t)img * cs.clip_vx * 3;
@@ -317,7 +315,7 @@ extern "C" int smil_render_colour(const SmilModel *m, const SmilCameras *cam, co
     a.verts_ndc = verts_ndc; a.verts_world = verts_world; a.normals = normals; a.faces = m->faces; a.cam = *cam;
     a.rgb[0] = rgb[0]; a.rgb[1] = rgb[1]; a.rgb[2] = rgb[2];
     a.image = image; a.pix_to_face = pix_to_face;
-    a.N = N; a.V = V; a.F = m->F; a.S = S; a.tiles_x = ceil_div(S, CTILE); a.views = cam->views; a.z_clip = 0.5f * SMIL_ZNEAR;
+    a.N = N; a.V = V; a.F = m->F; a.S = S; a.tiles_x = ceil_div(S, TILE); a.views = cam->views; a.z_clip = 0.5f * SMIL_ZNEAR;
     hipLaunchKernelGGL(k_colour_tiles, dim3((unsigned int)smil_device_limits().cus * COLOUR_WAVES_PER_CU), dim3(64), 0, stream, a);
     SMIL_LAUNCH_CHECK();
     return SMIL_OK;

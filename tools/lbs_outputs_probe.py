@@ -89,7 +89,7 @@ def get_tables(key):
 
 
 def pack_rows(d_ndc, g):
-    """(N,V,2) floats -> the fused rasteriser's packed rows (x * 2^32 + y, two's complement, raster.hip's `pack`) and their
+    """(N,V,2) floats -> the fused rasteriser's packed rows (x * 2^32 + y, two's complement: `pack_fx2`, csrc/raster_common.h) and their
     per-image factors; image 1 keeps plain floats (factor 0) and the last image a negative factor."""
     N = d_ndc.shape[0]
     scale = (2.0 ** -20) * (1.0 + torch.rand(N, generator=g))

@@ -50,9 +50,9 @@ if args.quick:
         print(f"tie_rule {args.tie_rule}: {st['tie_pixels']} pixels replayed ({st['tie_pixels'] / N:.1f} per image, {st['tie_pixels'] / max(st['tiles'], 1):.2f} per touched tile)")
     print(f"images {N}  time/launch {dt*1e3:.3f} ms  {dt/N*1e6:.2f} us/image  [SMIL_RESIDENT={os.environ.get('SMIL_RESIDENT')} SMIL_WRAP={os.environ.get('SMIL_WRAP')}]")
     sys.exit(0)
-# the workspace as raster.hip's raster_layout() lays it out: RasterCounters (656 bytes, padded to 768), then the tile boxes (N, FT)
+# the workspace as raster_layout() (raster.hip, host side) lays it out: RasterCounters (656 bytes, padded to 768), then the tile boxes (N, FT)
 ws = dm._ws
-FT = (dm.F + 63) // 64 * 64 + 2048  # rows of the per-image face tables (raster.hip: faces_padded(F) + CLIP_FX)
+FT = (dm.F + 63) // 64 * 64 + 2048  # rows of the per-image face tables (raster_common.h: faces_padded(F) + CLIP_FX)
 ctr = ws[:128].view(torch.int32).cpu().numpy().reshape(8, 4).sum(0)  # (partition, cost class) counters
 n_work = int(ctr[:4].sum())
 tb = ws[768:768 + N * FT * 4].view(torch.int32).reshape(N, FT).cpu().numpy().astype(np.uint32)
