@@ -209,6 +209,9 @@ static int raster_common(const SmilModel *m, const float *verts_ndc, int N, int 
         SMIL_REQUIRE(rs->clip_depth->vertex && rs->clip_depth->dz && rs->clip_depth->range && rs->clip_depth->counter && rs->clip_depth->capacity >= 0 &&
                      rs->image0 >= 0, "raster: incomplete SmilClipDepth");
     raster_layout(m, N, S, (char *)workspace, q, a);
+    // the per-image tables tbox / fzr / gbox are read behind the setup kernel by k_raster_tie_replay and by tiles of images that are
+    // never binned; otherwise only an image whose lists do not fit needs them, and the kernel finds that out itself
+    q.store_tables = (rs->tie_rule != SMIL_TIE_DEPTH_FACE_ID || q.list_cap == 0u) ? 1 : 0;
     const int tiles_x = ceil_div(S, TILE);
     if (rs->tie_rule) SMIL_HIP(hipMemsetAsync(a.tie_mask, 0, (size_t)2 * N_PARTS * a.item_cap * sizeof(unsigned long long), stream));
     q.verts_ndc = a.verts_ndc = verts_ndc; q.faces = a.faces = m->faces;
@@ -258,6 +261,7 @@ static size_t colour_setup_layout(const SmilModel *m, int N, int S, char *base, 
     q->clip = clip; q->faces = m->faces; q->tbox = tbox; q->gbox = gbox; q->items = items;
     q->item_cap = item_cap; q->fzr = fzr; q->ctr = c; q->V = m->V; q->F = m->F; q->S = S; q->tiles_x = tiles_x;
     q->sqrt_blur = 0.f; q->inv_sigma = 1.f; q->lists = lists; q->list_cap = list_cap;
+    q->store_tables = 1;  // (k_colour_tiles reads the tile boxes and depth ranges)
     return w.used;
 }
 

@@ -239,6 +239,9 @@ __device__ __forceinline__ int wave_scan_add(int x) {
 #ifndef SETUP_THREADS
 #define SETUP_THREADS 1024
 #endif
+#ifndef SETUP_REG_ROUNDS
+#define SETUP_REG_ROUNDS 6    // rounds of SETUP_THREADS faces whose tile box and nearest depth k_raster_setup keeps in registers between its two
+#endif                        // passes (two registers a round; STICK takes six rounds); a mesh with more rounds goes through the tables in memory
 #ifndef LIST_CAP_PER_FACE
 #define LIST_CAP_PER_FACE 8   // (tile, face) list entries an image may have per face at S <= 256 (a face's blurred box covers ~4 tiles there,
                               // ~8 at 512^2: the blur radius is a fixed fraction of the image); doubled above 256
@@ -255,6 +258,9 @@ struct SetupArgs {
                         // tile's depth range, and farthest <= nearest + the image's largest face extent bounds that as well)
     uint32_t list_cap;  // entries per image (0: no binning)
     uint32_t *cd_counter;  // SmilClipDepth.counter of a gradient call with image0 == 0: reset here (block 0), or NULL
+    int store_tables;   // tbox / fzr / gbox have a reader behind this kernel (tie_rule 1, the colour path, image sizes that are never binned):
+                        // store them for every image.  0: only an image whose lists do not fit stores them (for build_list), and a mesh
+                        // of more than SETUP_REG_ROUNDS rounds, whose pass 2 reads them back
     int copies;         // (round 5) per-tile counters / list cursors are kept in this many copies (1, 2 or 4: what fits 48 KB of LDS), a
                         // face using copy (face id % copies): consecutive faces hit the same tiles, and LDS atomics of one wave
                         // instruction on ONE address execute one after the other - the two atomic passes were two thirds of this kernel

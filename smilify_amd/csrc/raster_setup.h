@@ -15,7 +15,7 @@ __global__ void __launch_bounds__(SETUP_THREADS, 8) k_raster_setup(SetupArgs q) 
     __shared__ uint32_t s_straddle;
     __shared__ uint32_t s_zext;   // bits of the largest depth extent (farthest - nearest vertex) of a rendered face
     if (threadIdx.x == 0) { s_maxpx = 0u; s_straddle = 0u; s_zext = 0u; }
-    uint32_t my_px = 0u, my_straddle = 0u;
+    uint32_t my_px = 0u;
     float my_zext = 0.f;
     // per tile: entries << 32 | cost (counted), or a touched-tile bitmap when the image has too many tiles; behind it the tiles'
     // list cursors
@@ -46,15 +46,28 @@ __global__ void __launch_bounds__(SETUP_THREADS, 8) k_raster_setup(SetupArgs q) 
     __shared__ uint32_t s_ncut, s_unclipped;
     __shared__ int s_cut[CLIP_CUTS];
     if (threadIdx.x == 0) { s_ncut = 0u; s_unclipped = 0u; }
-    for (int i = threadIdx.x; i < FT - F; i += blockDim.x) q.tbox[(size_t)n * FT + F + i] = 0x0000FFFFu;  // (ids F .. FT-1: empty unless a cut face fills them)
+    // A face's tile box and nearest depth stay in the registers of the thread that computed them - pass 2 walks the faces with the same
+    // f = round * blockDim.x + threadIdx.x - when the mesh has at most SETUP_REG_ROUNDS rounds (block-uniform).  The tables tbox / fzr /
+    // gbox are then stored only for a reader behind this kernel: every image when the host says so (store_tables), else an image
+    // whose lists turn out not to fit (write_tables below, for build_list).  The front parts of cut faces (ids from FP on) are
+    // emitted by whichever thread cut their face: their rows always go through memory.
+    const bool in_regs = FP <= SETUP_REG_ROUNDS * (int)blockDim.x;
+    const bool store = q.store_tables != 0 || !in_regs;
+    uint32_t rbox[SETUP_REG_ROUNDS], rzn[SETUP_REG_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < SETUP_REG_ROUNDS; ++r) { rbox[r] = 0x0000FFFFu; rzn[r] = 0u; }
+    if (store)
+        for (int i = threadIdx.x; i < FT - F; i += blockDim.x) q.tbox[(size_t)n * FT + F + i] = 0x0000FFFFu;  // (ids F .. FT-1: empty unless a cut face fills them)
     __syncthreads();
     TSETUP(1)
     float *const xv_n = q.clip.xv + (size_t)n * CLIP_VX * 3;
     int *const xf_n = q.clip.xf + (size_t)n * CLIP_FX * 3;
     // one face (an original one or the front part of a cut one): validity, blurred pixel box -> tile box, cost / entry per tile
-    auto emit = [&](int fid, float x0, float y0, float z0, float x1, float y1, float z1, float x2, float y2, float z2) -> uint32_t {
+    auto emit = [&](int fid, float x0, float y0, float z0, float x1, float y1, float z1, float x2, float y2, float z2, float &znear) -> uint32_t {
         uint32_t box = 0x0000FFFFu;  // empty: tx0 = ty0 = 255 > tx1 = ty1 = 0
         const float zmin = fminf(fminf(z0, z1), z2), zmax = fmaxf(fmaxf(z0, z1), z2);
+        znear = zmin;
+        if (store || fid >= FP) q.fzr[(size_t)n * FT + fid] = make_float2(zmin, zmax);
         const float area = edge_fn(x0, y0, x1, y1, x2, y2);
         const bool finite = (x0 == x0) && (x1 == x1) && (x2 == x2) && (y0 == y0) && (y1 == y1) && (y2 == y2);
         // zmin < 1e-8: the rasteriser's own rule; zmax < z_clip: the face lies entirely nearer than MeshRasterizer's
@@ -71,12 +84,12 @@ __global__ void __launch_bounds__(SETUP_THREADS, 8) k_raster_setup(SetupArgs q) 
             xi_lo = max(xi_lo, 0); yi_lo = max(yi_lo, 0);
             xi_hi = min(xi_hi, S - 1); yi_hi = min(yi_hi, S - 1);
             if (xi_lo <= xi_hi && yi_lo <= yi_hi) {
-                my_px = max(my_px, (uint32_t)((xi_hi - xi_lo + 1) * (yi_hi - yi_lo + 1)));
                 my_zext = fmaxf(my_zext, zmax - zmin);
                 // output column xo = S-1-xi
                 const int tx0 = (S - 1 - xi_hi) / TILE, tx1 = (S - 1 - xi_lo) / TILE;
                 const int ty0 = (S - 1 - yi_hi) / TILE, ty1 = (S - 1 - yi_lo) / TILE;
                 box = (uint32_t)tx0 | ((uint32_t)ty0 << 8) | ((uint32_t)tx1 << 16) | ((uint32_t)ty1 << 24);
+                if (store || fid >= FP) q.tbox[(size_t)n * FT + fid] = box;  // (ahead of the tile loop: the address does not live through it)
                 const int xo0 = S - 1 - xi_hi, xo1 = S - 1 - xi_lo, yo0 = S - 1 - yi_hi, yo1 = S - 1 - yi_lo;
                 for (int ty = ty0; ty <= ty1; ++ty)
                     for (int tx = tx0; tx <= tx1; ++tx) {
@@ -89,19 +102,32 @@ __global__ void __launch_bounds__(SETUP_THREADS, 8) k_raster_setup(SetupArgs q) 
                             atomicOr(&tbits[t >> 5], 1u << (t & 31));
                         }
                     }
+                my_px = max(my_px, (uint32_t)((xo1 - xo0 + 1) * (yo1 - yo0 + 1)));  // (behind the tile loop: not live through it)
             }
         }
-        q.tbox[(size_t)n * FT + fid] = box;
-        q.fzr[(size_t)n * FT + fid] = make_float2(zmin, zmax);
+        if ((store || fid >= FP) && box == 0x0000FFFFu) q.tbox[(size_t)n * FT + fid] = box;
         return box;
+    };
+    // union of a wave's 64 boxes -> the box of group `grp`: the tile kernel skips whole groups of faces with one test (images that are not binned)
+    // (in DPP: a smallest value is 255 - the largest of 255 - x; no lane-index register for ds_bpermute lives through the rounds)
+    auto wave_box = [&](uint32_t box) -> uint32_t {
+        const uint32_t gx0 = 255u - wave_max_u32(255u - (box & 0xFFu)), gy0 = 255u - wave_max_u32(255u - ((box >> 8) & 0xFFu));
+        const uint32_t gx1 = wave_max_u32((box >> 16) & 0xFFu), gy1 = wave_max_u32(box >> 24);
+        return gx0 | (gy0 << 8) | (gx1 << 16) | (gy1 << 24);
+    };
+    auto group_box = [&](uint32_t box, int grp) {
+        const uint32_t g = wave_box(box);
+        if ((threadIdx.x & (WAVE - 1)) == 0 && grp < FP / WAVE) q.gbox[(size_t)n * n_groups + grp] = g;
     };
     // (the vertex ids of the NEXT round's face are requested before this round's vertices are gathered: a round is one memory
     // round trip - ids -> vertices was two - and an image is a chain of F / blockDim.x rounds)
     int nx0 = 0, nx1 = 0, nx2 = 0;
+    uint32_t wave_px = 0u, wave_zext = 0u;
     if ((int)threadIdx.x < F) { nx0 = q.faces[3 * threadIdx.x]; nx1 = q.faces[3 * threadIdx.x + 1]; nx2 = q.faces[3 * threadIdx.x + 2]; }
     for (int f0 = 0; f0 < FP; f0 += blockDim.x) {  // every wave handles 64 consecutive faces per round
         const int f = f0 + threadIdx.x;
         uint32_t box = 0x0000FFFFu;
+        float znear = 0.f;
         const int ii[3] = {nx0, nx1, nx2};
         {
             const int fn = min(f + (int)blockDim.x, F - 1);
@@ -116,29 +142,38 @@ __global__ void __launch_bounds__(SETUP_THREADS, 8) k_raster_setup(SetupArgs q) 
                                 (Z[0] == Z[0]) && (Z[1] == Z[1]) && (Z[2] == Z[2]);
             bool cut = false;
             if (finite && (nb == 1 || nb == 2)) {  // crosses the plane: set aside for the cut loop below (rare: kept out of this loop's registers)
-                ++my_straddle;
+                atomicAdd(&s_straddle, 1u);  // (rare: straight to LDS, no register across the rounds)
                 const uint32_t c = q.clip.xv ? atomicAdd(&s_ncut, 1u) : (uint32_t)CLIP_CUTS;
                 if (c < (uint32_t)CLIP_CUTS) {
                     s_cut[c] = f;
                     cut = true;
-                    q.tbox[(size_t)n * FT + f] = 0x0000FFFFu;  // the face itself is replaced by its front part
-                    q.fzr[(size_t)n * FT + f] = make_float2(fminf(fminf(Z[0], Z[1]), Z[2]), fmaxf(fmaxf(Z[0], Z[1]), Z[2]));
+                    if (store) {
+                        q.tbox[(size_t)n * FT + f] = 0x0000FFFFu;  // the face itself is replaced by its front part
+                        q.fzr[(size_t)n * FT + f] = make_float2(fminf(fminf(Z[0], Z[1]), Z[2]), fmaxf(fmaxf(Z[0], Z[1]), Z[2]));
+                    }
                 } else {
                     atomicAdd(&s_unclipped, 1u);  // beyond the tables: rendered whole, or dropped when a vertex is nearer than 1e-8 (counted)
                 }
             }
-            if (!cut) box = emit(f, X[0], Y[0], Z[0], X[1], Y[1], Z[1], X[2], Y[2], Z[2]);
+            if (!cut) box = emit(f, X[0], Y[0], Z[0], X[1], Y[1], Z[1], X[2], Y[2], Z[2], znear);
         }
-        // union of the wave's 64 boxes: the tile kernel skips whole groups of faces with one test (images that are not binned)
-        int gx0 = box & 0xFF, gy0 = (box >> 8) & 0xFF, gx1 = (box >> 16) & 0xFF, gy1 = box >> 24;
-        for (int o = 32; o > 0; o >>= 1) {
-            gx0 = min(gx0, __shfl_xor(gx0, o, WAVE)); gy0 = min(gy0, __shfl_xor(gy0, o, WAVE));
-            gx1 = max(gx1, __shfl_xor(gx1, o, WAVE)); gy1 = max(gy1, __shfl_xor(gy1, o, WAVE));
+        if (in_regs) {  // (the round number is uniform: a select per register, no indexed access)
+#pragma unroll
+            for (int r = 0; r < SETUP_REG_ROUNDS; ++r) {
+                const bool here = f0 == r * (int)blockDim.x;
+                rbox[r] = here ? box : rbox[r];
+                rzn[r] = here ? __float_as_uint(znear) : rzn[r];
+            }
         }
-        const int grp = (f0 + (int)threadIdx.x) / WAVE;
-        if ((threadIdx.x & (WAVE - 1)) == 0 && grp < FP / WAVE)
-            q.gbox[(size_t)n * n_groups + grp] = (uint32_t)gx0 | ((uint32_t)gy0 << 8) | ((uint32_t)gx1 << 16) | ((uint32_t)gy1 << 24);
+        if (store) group_box(box, (f0 + (int)threadIdx.x) / WAVE);
+        // (the wave's largest so far ride in scalar registers; non-negative floats order like their bit patterns)
+        wave_px = max(wave_px, wave_max_u32(my_px));
+        wave_zext = max(wave_zext, wave_max_u32(__float_as_uint(my_zext)));
+        my_px = 0u;
+        my_zext = 0.f;
     }
+    my_px = wave_px;
+    my_zext = __uint_as_float(wave_zext);
     __syncthreads();
     TSETUP(2)
     // the faces that cross the plane: cut c owns the new vertices 2c, 2c + 1 and the front-part faces FP + 2c, FP + 2c + 1
@@ -154,7 +189,13 @@ __global__ void __launch_bounds__(SETUP_THREADS, 8) k_raster_setup(SetupArgs q) 
         const int k1 = nb == 1 ? (Z[0] < q.z_clip ? 0 : (Z[1] < q.z_clip ? 1 : 2)) : (!(Z[0] < q.z_clip) ? 0 : (!(Z[1] < q.z_clip) ? 1 : 2));
         const int o1 = k1, o2 = (k1 + 1) % 3, o3 = (k1 + 2) % 3;
         const uint32_t jv = 2u * c;
-        float nx[2], ny[2];
+        float nx[2], ny[2], zn_;
+        {  // the front parts' vertex ids (ahead of the arithmetic: the face's own ids do not live through it)
+            const int v4 = V + (int)jv, v5 = v4 + 1;
+            int *xf = xf_n + 3 * (2 * c);
+            if (nb == 1) { xf[0] = v4; xf[1] = ii[o2]; xf[2] = ii[o3]; xf[3] = v4; xf[4] = ii[o3]; xf[5] = v5; }  // quadrilateral (p4, p2, p3, p5) as (p4, p2, p3) + (p4, p3, p5)
+            else { xf[0] = ii[o1]; xf[1] = v4; xf[2] = v5; }                                                    // triangle (p1, p4, p5)
+        }
         for (int e = 0; e < 2; ++e) {  // where the edges p1-p2 and p1-p3 cross the plane (view-space interpolation)
             const int a = o1, b = e == 0 ? o2 : o3;
             const float wb = (Z[a] - q.z_clip) / (Z[a] - Z[b]);
@@ -165,30 +206,25 @@ __global__ void __launch_bounds__(SETUP_THREADS, 8) k_raster_setup(SetupArgs q) 
             q.clip.xsrc[(size_t)n * CLIP_VX + jv + e] = make_int2(ii[a], ii[b]);
             q.clip.xcoef[(size_t)n * CLIP_VX + jv + e] = make_float2(ca, cb);
         }
-        const int v4 = V + (int)jv, v5 = v4 + 1;
-        int *xf = xf_n + 3 * (2 * c);
         if (nb == 1) {  // quadrilateral (p4, p2, p3, p5) as (p4, p2, p3) + (p4, p3, p5)
-            xf[0] = v4; xf[1] = ii[o2]; xf[2] = ii[o3]; xf[3] = v4; xf[4] = ii[o3]; xf[5] = v5;
-            emit(FP + 2 * (int)c, nx[0], ny[0], q.z_clip, X[o2], Y[o2], Z[o2], X[o3], Y[o3], Z[o3]);
-            emit(FP + 2 * (int)c + 1, nx[0], ny[0], q.z_clip, X[o3], Y[o3], Z[o3], nx[1], ny[1], q.z_clip);
+            emit(FP + 2 * (int)c, nx[0], ny[0], q.z_clip, X[o2], Y[o2], Z[o2], X[o3], Y[o3], Z[o3], zn_);
+            emit(FP + 2 * (int)c + 1, nx[0], ny[0], q.z_clip, X[o3], Y[o3], Z[o3], nx[1], ny[1], q.z_clip, zn_);
         } else {        // triangle (p1, p4, p5)
-            xf[0] = ii[o1]; xf[1] = v4; xf[2] = v5;
-            emit(FP + 2 * (int)c, X[o1], Y[o1], Z[o1], nx[0], ny[0], q.z_clip, nx[1], ny[1], q.z_clip);
+            emit(FP + 2 * (int)c, X[o1], Y[o1], Z[o1], nx[0], ny[0], q.z_clip, nx[1], ny[1], q.z_clip, zn_);
+            q.tbox[(size_t)n * FT + FP + 2 * (int)c + 1] = 0x0000FFFFu;  // (the cut's second slot: empty - nothing else fills the rows from FP on when the tables are not stored)
         }
     }
     __syncthreads();  // the front parts' tile boxes are in place (written by whichever thread cut their face)
     TSETUP(3)
     static_assert(CLIP_FX % WAVE == 0 && SETUP_THREADS % WAVE == 0, "whole waves of front-part faces");
-    for (int i = threadIdx.x; i < CLIP_FX; i += blockDim.x) {  // their group boxes (wave = group of 64; rows behind the last cut are empty)
-        const uint32_t box = i < 2 * (int)n_cut ? q.tbox[(size_t)n * FT + FP + i] : 0x0000FFFFu;
-        int gx0 = box & 0xFF, gy0 = (box >> 8) & 0xFF, gx1 = (box >> 16) & 0xFF, gy1 = box >> 24;
-        for (int o = 32; o > 0; o >>= 1) {
-            gx0 = min(gx0, __shfl_xor(gx0, o, WAVE)); gy0 = min(gy0, __shfl_xor(gy0, o, WAVE));
-            gx1 = max(gx1, __shfl_xor(gx1, o, WAVE)); gy1 = max(gy1, __shfl_xor(gy1, o, WAVE));
+    auto front_group_boxes = [&]() {  // their group boxes (wave = group of 64; rows behind the last cut are empty)
+        for (int i = threadIdx.x; i < CLIP_FX; i += blockDim.x) {
+            const uint32_t box = i < 2 * (int)n_cut ? q.tbox[(size_t)n * FT + FP + i] : 0x0000FFFFu;
+            const uint32_t g = wave_box(box);
+            if ((i & (WAVE - 1)) == 0) q.gbox[(size_t)n * n_groups + FP / WAVE + i / WAVE] = g;
         }
-        if ((i & (WAVE - 1)) == 0)
-            q.gbox[(size_t)n * n_groups + FP / WAVE + i / WAVE] = (uint32_t)gx0 | ((uint32_t)gy0 << 8) | ((uint32_t)gx1 << 16) | ((uint32_t)gy1 << 24);
-    }
+    };
+    if (store) front_group_boxes();
     if (q.clip.xcount) {
         const uint32_t nxv = 2u * n_cut;
         if (threadIdx.x == 0) q.clip.xcount[n] = nxv;
@@ -204,12 +240,10 @@ __global__ void __launch_bounds__(SETUP_THREADS, 8) k_raster_setup(SetupArgs q) 
         for (int o = 32; o > 0; o >>= 1) {
             my_px = max(my_px, (uint32_t)__shfl_xor((int)my_px, o, WAVE));
             zb = max(zb, (uint32_t)__shfl_xor((int)zb, o, WAVE));
-            my_straddle += (uint32_t)__shfl_xor((int)my_straddle, o, WAVE);
         }
         if ((threadIdx.x & (WAVE - 1)) == 0) {
             if (my_px) atomicMax(&s_maxpx, my_px);
             if (zb) atomicMax(&s_zext, zb);
-            if (my_straddle) atomicAdd(&s_straddle, my_straddle);
         }
     }
     __syncthreads();
@@ -288,25 +322,53 @@ __global__ void __launch_bounds__(SETUP_THREADS, 8) k_raster_setup(SetupArgs q) 
         // descriptor were two dependent ones
         q.items[idx] = make_uint4((uint32_t)n * (uint32_t)n_tiles + (uint32_t)t, binned ? first : 0u, binned ? e : 0xFFFFFFFFu, zext_bits);
     }
-    if (!binned) return;  // (block-uniform)
+    if (!binned) {  // (block-uniform)
+        // The tile kernel builds this image's lists itself, from the tables: nobody stored them yet - the boxes come from the registers,
+        // a face's depth range from its vertices again (min / max of the same three floats; this is the rare image, and a third
+        // register a round for the farthest depth would cost every image), the rows behind the last cut face's front parts are empty.
+        if (!store) {
+            for (int i = threadIdx.x + 2 * (int)n_cut; i < CLIP_FX; i += blockDim.x) q.tbox[(size_t)n * FT + FP + i] = 0x0000FFFFu;
+#pragma unroll
+            for (int r = 0; r < SETUP_REG_ROUNDS; ++r) {
+                const int f = r * (int)blockDim.x + (int)threadIdx.x;
+                if (r * (int)blockDim.x < FP) {
+                    if (f < FP) q.tbox[(size_t)n * FT + f] = rbox[r];
+                    if (f < F) {
+                        const float z0 = vn[3 * q.faces[3 * f] + 2], z1 = vn[3 * q.faces[3 * f + 1] + 2], z2 = vn[3 * q.faces[3 * f + 2] + 2];
+                        q.fzr[(size_t)n * FT + f] = make_float2(fminf(fminf(z0, z1), z2), fmaxf(fmaxf(z0, z1), z2));
+                    }
+                    group_box(rbox[r], f / WAVE);
+                }
+            }
+            front_group_boxes();
+        }
+        return;
+    }
     __syncthreads();
     TSETUP(7)
-    // pass 2: every face to the lists of the tiles of its box (its own tile box and depth range come back from L1 / L2)
+    // pass 2: every face to the lists of the tiles of its box (box and nearest depth from this thread's registers; the front parts of
+    // cut faces, and every face of a mesh of more than SETUP_REG_ROUNDS rounds, from the tables: back from L1 / L2)
     uint2 *const lists = q.lists + (size_t)n * q.list_cap;
     // (consecutive faces cover the same tiles: their entries take consecutive slots, so a wave's stores land in few cache lines;
     // spreading the lanes over distant faces to thin out the same-address atomics was measured slower, 601 -> 658 us)
     const int f_end = FP + 2 * (int)n_cut;  // (the rows behind the last cut face's front parts are empty)
-    for (int f = threadIdx.x; f < f_end; f += blockDim.x) {
-        const uint32_t box = q.tbox[(size_t)n * FT + f];
-        const uint2 ent = make_uint2((uint32_t)f, __float_as_uint(q.fzr[(size_t)n * FT + f].x));  // (requested with the box: one round trip)
+    auto bin_face = [&](int f, uint32_t box, uint32_t znear_bits) {
+        const uint2 ent = make_uint2((uint32_t)f, znear_bits);
         const int tx0 = box & 0xFF, ty0 = (box >> 8) & 0xFF, tx1 = (box >> 16) & 0xFF, ty1 = box >> 24;
-        if (tx0 > tx1) continue;
+        if (tx0 > tx1) return;
         uint32_t *const cur = tcur + (f & (KC - 1)) * n_tiles;
         // (a fast path for boxes of at most 2 x 2 tiles - the four returning atomics issued before the four stores - measured no
         // different, profiles/r5_experiments.md)
         for (int ty = ty0; ty <= ty1; ++ty)
             for (int tx = tx0; tx <= tx1; ++tx) at(lists, atomicAdd(&cur[ty * tiles_x + tx], 1u)) = ent;
+    };
+    if (in_regs) {
+#pragma unroll
+        for (int r = 0; r < SETUP_REG_ROUNDS; ++r)
+            if (r * (int)blockDim.x < FP) bin_face(r * (int)blockDim.x + (int)threadIdx.x, rbox[r], rzn[r]);  // (rows from FP on: empty boxes)
     }
+    for (int f = (in_regs ? FP : 0) + (int)threadIdx.x; f < f_end; f += blockDim.x)
+        bin_face(f, q.tbox[(size_t)n * FT + f], __float_as_uint(q.fzr[(size_t)n * FT + f].x));  // (one round trip: both requested together)
     TSETUP(8)
     TSETUP_REPORT
 }

@@ -51,6 +51,10 @@ if args.quick:
     print(f"images {N}  time/launch {dt*1e3:.3f} ms  {dt/N*1e6:.2f} us/image  [SMIL_RESIDENT={os.environ.get('SMIL_RESIDENT')} SMIL_WRAP={os.environ.get('SMIL_WRAP')}]")
     sys.exit(0)
 # the workspace as raster_layout() (raster.hip, host side) lays it out: RasterCounters (656 bytes, padded to 768), then the tile boxes (N, FT)
+# (the default mode stores the tile boxes only for images whose lists do not fit: one more forward call under tie_rule = reference_queue,
+# which reads them and therefore has the setup kernel store them for every image; counters and boxes do not depend on the rule)
+engine.silhouette_forward(dm, ndc, args.S, engine.raster_settings(tie_rule="reference_queue"))
+torch.cuda.synchronize()
 ws = dm._ws
 FT = (dm.F + 63) // 64 * 64 + 2048  # rows of the per-image face tables (raster_common.h: faces_padded(F) + CLIP_FX)
 ctr = ws[:128].view(torch.int32).cpu().numpy().reshape(8, 4).sum(0)  # (partition, cost class) counters
