@@ -53,10 +53,11 @@ int smil_model_create(const SmilModelDesc *desc, SmilModel **out);
 void smil_model_destroy(SmilModel *m);
 int smil_model_dims(const SmilModel *m, int32_t dims[4]); /* V,F,J,nB */
 const char *smil_last_error(void);
-const char *smil_version(void);   /* "smilfit 0.4 (gfx950; 0.3 + SmilCameras.principal)".  0.3 = the layout of rounds 5 - 6: SmilLbsGrads carries clip_depth in front of
+const char *smil_version(void);   /* "smilfit 0.5 (gfx950; 0.3 + SmilCameras.principal (0.4) + fragments, depth visibility)".  0.3 = the layout of rounds 5 - 6: SmilLbsGrads carries clip_depth in front of
                                     * beta_rows (which must hold 2 * B * nB_used + 16 floats), SmilRasterSettings ends in {tie_rule, clip_depth,
                                     * image0}, smil_window_terms exists.  0.4: SmilCameras ends in {principal, nPrincipal} (a zero-initialised
-                                    * struct means what it meant in 0.3).  Callers zero-initialise every struct they pass and rebuild against
+                                    * struct means what it meant in 0.3).  0.5 adds smil_render_fragments and
+                                    * smil_depth_visibility and changes no layout.  Callers zero-initialise every struct they pass and rebuild against
                                     * this header when the number changes: there is no binary compatibility across it. */
 
 /* ------------------------------------------------------------------------------------------
@@ -318,6 +319,37 @@ size_t smil_colour_workspace_bytes(const SmilModel *m, int32_t N, int32_t S);
  * as pytorch3d's clip_faces cuts them and reported as their original face.  A pixel shows the smallest (depth, face, part). */
 int smil_render_colour(const SmilModel *m, const SmilCameras *cam, const float *verts_world, const float *verts_ndc,
                        const float rgb[3], float *image, int32_t *pix_to_face, void *workspace, void *stream);
+/* ------------------------------------------------------------------------------------------
+ * Fragments of the hard rasteriser, and keypoint self-occlusion against a depth buffer.  smil_render_fragments hands out what
+ * pytorch3d's MeshRasterizer (blur_radius 0, faces_per_pixel 1, bin_size 0: p3d_renderer.py:54-70) returns as Fragments and the colour
+ * path uses for one pixel of shading; smil_depth_visibility replaces Unreal2Pytorch3D.py:664-760 (refine_visibility_with_depth, called
+ * per view at :1558-1580) for all images of a batch.  No gradient.
+ * ---------------------------------------------------------------------------------------- */
+/* Caller-owned scratch for N images of side S: the tables of the colour path's setup alone (no vertex normals). */
+size_t smil_fragments_workspace_bytes(const SmilModel *m, int32_t N, int32_t S);
+/* The rasterisation of smil_render_colour (same arguments, same rule: a pixel shows the smallest (depth, face, part)) without the
+ * shading.  Every output may be NULL (at least one is not):
+ *   pix_to_face (N,S,S)    original per-mesh face id, -1 for background
+ *   zbuf        (N,S,S)    view depth of the winner, -1 for background
+ *   bary        (N,S,S,3)  perspective-correct, unclipped barycentrics with respect to the original face, -1 for background
+ *   dist        (N,S,S)    |C - X|: Euclidean distance from the camera centre C = -T R^T to the world point X = sum_c b_c
+ *                          verts_world[P_c], formed as the colour path forms them; +inf for background
+ * There is no K axis and no `dists` (K = 1, blur 0).  verts_world (frames,V,3) and the camera tables R, T are read only for dist and
+ * may be NULL without it.  Two calls give the same bits. */
+int smil_render_fragments(const SmilModel *m, const SmilCameras *cam, const float *verts_world, const float *verts_ndc,
+                          int32_t *pix_to_face, float *zbuf, float *bary, float *dist, void *workspace, void *stream);
+/* Unreal2Pytorch3D.py:733-758 for B images of P keypoints each, every comparison in float64.  depth: with depth_is_u8 a (B,H,W,channels)
+ * uint8 buffer whose channel 0 encodes surface = (r / 255.0) * depth_max (the minimum over the window is taken on the bytes); otherwise
+ * (B,H,W) float32 distances, +inf for background (channels and depth_max are ignored).  kp_norm (B,P,2) float64 = (norm_x, norm_y) with
+ * norm_x along the ROWS (the reference's swapped convention): row = min(max(trunc(norm_x H), 0), H - 1), col likewise from norm_y W.
+ * kp_dist (B,P) float64 the keypoint's distance to the camera (non-finite: no 3-D position).  neighborhood = half-window h in [0, 8]
+ * (otherwise SMIL_E_INVALID): rows [max(0, row - h), min(H, row + h + 1)), columns likewise.
+ * vis_out (B,P) = vis_in, except 0 where vis_in != 0, kp_dist is finite, 0 <= norm_x, norm_y <= 1 (a NaN fails) and
+ * kp_dist > surface + tolerance.  surface (B,P) float64 or NULL: the sampled minimum, NaN where no sample was taken.  vis_out may be
+ * vis_in. */
+int smil_depth_visibility(const void *depth, int32_t depth_is_u8, int32_t channels, double depth_max, int32_t B, int32_t H, int32_t W,
+                          const double *kp_norm, const double *kp_dist, int32_t P, const float *vis_in, double tolerance,
+                          int32_t neighborhood, float *vis_out, double *surface, void *stream);
 /* Measurement hook (bench.py): when enabled, every launch of the tile kernel is bracketed by HIP events on its
  * launch stream; smil_profile_read synchronises those events and returns their summed duration + count. */
 int smil_profile_enable(int32_t on);

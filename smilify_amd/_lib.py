@@ -21,6 +21,7 @@ EXPORTS = [
     "smil_silhouette_l1_fused", "smil_prior_losses", "smil_mask_rows", "smil_joint_loss", "smil_pix_scale",
     "smil_image_abs_sum", "smil_sil_objective", "smil_window_terms", "smil_adam_step", "smil_adam_step_multi", "smil_adam_step_dev", "smil_profile_enable",
     "smil_profile_read", "smil_colour_workspace_bytes", "smil_render_colour",
+    "smil_fragments_workspace_bytes", "smil_render_fragments", "smil_depth_visibility",
     "smil_sample_points", "smil_chamfer_workspace_bytes", "smil_chamfer", "smil_mesh_reg_workspace_bytes", "smil_mesh_regularisers",
     "smil_knn_workspace_bytes", "smil_knn", "smil_sdf_distance_workspace_bytes", "smil_sdf_distance", "smil_sample_vertices",
     "smil_sample_vertices_backward_workspace_bytes", "smil_sample_vertices_backward",
@@ -173,6 +174,11 @@ def load():
     lib.smil_colour_workspace_bytes.restype = c_size_t
     lib.smil_render_colour.argtypes = [c_void_p, POINTER(Cameras), c_void_p, c_void_p, POINTER(c_float), c_void_p, c_void_p, c_void_p,
                                        c_void_p]
+    lib.smil_fragments_workspace_bytes.argtypes = [c_void_p, c_int32, c_int32]
+    lib.smil_fragments_workspace_bytes.restype = c_size_t
+    lib.smil_render_fragments.argtypes = [c_void_p, POINTER(Cameras)] + [c_void_p] * 8
+    lib.smil_depth_visibility.argtypes = [c_void_p, c_int32, c_int32, c_double, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                          c_double, c_int32, c_void_p, c_void_p, c_void_p]
     lib.smil_sample_points.argtypes = [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_void_p, c_void_p,
                                        c_void_p]
     lib.smil_chamfer_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]

@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes
 import os
 from dataclasses import dataclass
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -564,8 +564,8 @@ _COLOUR_WS: Dict = {}  # (device type, index) -> the device's colour workspace (
 MAX_COLOUR_WORKSPACE_BYTES = 8 << 30  # frames per colour launch shrink until the workspace fits this
 
 
-def _colour_workspace(model: DeviceModel, N: int, S: int) -> torch.Tensor:
-    need = int(_lib.load().smil_colour_workspace_bytes(model.handle, N, S))
+def _colour_workspace(model: DeviceModel, N: int, S: int, size_of=None) -> torch.Tensor:
+    need = int((size_of or _lib.load().smil_colour_workspace_bytes)(model.handle, N, S))
     key = model._ws_key()
     ws = _COLOUR_WS.get(key)
     if ws is None or ws.numel() < need:
@@ -608,6 +608,104 @@ def render_colour(model: DeviceModel, cams: CameraSet, verts: torch.Tensor, mesh
                                           _ptr(image[n0:n1]), _ptr(None if p2f is None else p2f[n0:n1]), _ptr(ws), _stream()),
                    "smil_render_colour")
     return (image, p2f) if want_pix_to_face else image
+
+
+class Fragments(NamedTuple):
+    """What ``render_fragments`` returns; an output that was not asked for is None.  Unlike pytorch3d's ``Fragments`` there is no K axis
+    (K = 1), face ids count within the image's own mesh (int32, not packed over the batch) and there is no ``dists`` (blur 0)."""
+
+    pix_to_face: Optional[torch.Tensor]  # (N,S,S) int32, -1: background
+    zbuf: Optional[torch.Tensor]         # (N,S,S) float32 view depth, -1: background
+    bary: Optional[torch.Tensor]         # (N,S,S,3) float32 with respect to the original face, -1: background
+    dist: Optional[torch.Tensor]         # (N,S,S) float32 distance camera centre -> surface, +inf: background
+
+
+FRAGMENT_OUTPUTS = Fragments._fields
+
+
+def _camera_rows(cams: CameraSet, N: int, n0: int, n1: int) -> CameraSet:
+    """The cameras of images [n0, n1) of N: tables with one row per image follow the slice; shared / per-view ones stay."""
+    def rows(t):
+        return t if t is None or t.shape[0] != N or n1 - n0 == N else t[n0:n1].contiguous()
+    return CameraSet(rows(cams.R), rows(cams.T), rows(cams.fov.reshape(-1)), rows(None if cams.aspect is None else cams.aspect.reshape(-1)),
+                     cams.views, cams.S, rows(cams.principal))
+
+
+def render_fragments(model: DeviceModel, cams: CameraSet, verts: torch.Tensor, verts_ndc: Optional[torch.Tensor] = None,
+                     want=FRAGMENT_OUTPUTS) -> Fragments:
+    """The hard rasteriser's result (blur 0, K = 1: the rasterisation of ``render_colour``, p3d_renderer.py:54-70) for ``verts``
+    (frames,V,3) in world space: the outputs named in ``want`` as a ``Fragments`` tuple over N = frames * views images.  ``dist`` is the
+    depth pass's convention, the Euclidean distance from the camera centre to the surface point.  ``verts_ndc``: the projection of
+    ``verts`` through ``cams`` when the caller has it.  No gradient.  Large batches are cut into launches of whole frames of at most
+    ``MAX_IMAGES_PER_LAUNCH`` images."""
+    want = tuple(want)
+    unknown = [w for w in want if w not in FRAGMENT_OUTPUTS]
+    if unknown or not want:
+        raise ValueError(f"want must name some of {FRAGMENT_OUTPUTS}, got {want}")
+    verts = verts.detach().float().contiguous()
+    frames, V = verts.shape[0], verts.shape[1]
+    views, S = cams.views, cams.S
+    N = frames * views
+    dev = verts.device
+    if verts_ndc is None:
+        verts_ndc, _ = project(cams, verts, want_yx=False)
+    verts_ndc = verts_ndc.detach().float().contiguous()
+    shapes = dict(pix_to_face=((N, S, S), torch.int32), zbuf=((N, S, S), torch.float32), bary=((N, S, S, 3), torch.float32),
+                  dist=((N, S, S), torch.float32))
+    out = {k: (torch.empty(*shapes[k][0], dtype=shapes[k][1], device=dev) if k in want else None) for k in FRAGMENT_OUTPUTS}
+    lib = _lib.load()
+    step = max(1, min(frames, MAX_IMAGES_PER_LAUNCH // views))  # frames per launch
+    while step > 1 and int(lib.smil_fragments_workspace_bytes(model.handle, step * views, S)) > MAX_COLOUR_WORKSPACE_BYTES:
+        step = (step + 1) // 2
+    ws = _colour_workspace(model, step * views, S, lib.smil_fragments_workspace_bytes)
+    for f0 in range(0, frames, step):
+        f1 = min(frames, f0 + step)
+        n0, n1 = f0 * views, f1 * views
+        c = _camera_rows(cams, N, n0, n1).struct(n1 - n0)
+        part = [_ptr(None if out[k] is None else out[k][n0:n1]) for k in FRAGMENT_OUTPUTS]
+        _lib.check(lib.smil_render_fragments(model.handle, ctypes.byref(c), _ptr(verts[f0:f1]), _ptr(verts_ndc[n0:n1]), *part, _ptr(ws),
+                                             _stream()), "smil_render_fragments")
+    return Fragments(**out)
+
+
+def depth_visibility(depth: torch.Tensor, kp_norm: torch.Tensor, kp_dist: torch.Tensor, visibility: torch.Tensor, tolerance: float,
+                     neighborhood: int = 1, depth_max: Optional[float] = None, want_surface: bool = False):
+    """Keypoint self-occlusion against a depth buffer (Unreal2Pytorch3D.py:733-758 for B images at once, float64 comparisons).
+    ``depth``: uint8 (B,H,W,C) with the depth in channel 0 and ``depth_max`` (surface = r / 255 * depth_max), or float32 (B,H,W)
+    distances with +inf as background.  ``kp_norm`` (B,P,2) float64 = (row / H, column / W), the reference's swapped convention;
+    ``kp_dist`` (B,P) float64 distance of every keypoint to its camera (non-finite: no 3-D position); ``visibility`` (B,P) float32.
+    Returns the refined (B,P) float32 visibility (it only ever turns non-zero into 0), with ``want_surface`` also the (B,P) float64
+    sampled surface distance (NaN where none was sampled).  ``neighborhood``: half-window in pixels, 0 to 8."""
+    dev = require_gpu(depth.device)
+    if depth.dtype == torch.uint8:
+        if depth.dim() != 4 or depth.shape[3] < 1:
+            raise _lib.SmilError(f"a uint8 depth buffer must be (B,H,W,C), got {tuple(depth.shape)}")
+        if depth_max is None:
+            raise _lib.SmilError("a uint8 depth buffer needs depth_max")
+        channels = int(depth.shape[3])
+    elif depth.dtype == torch.float32:
+        if depth.dim() != 3:
+            raise _lib.SmilError(f"a float32 depth buffer must be (B,H,W), got {tuple(depth.shape)}")
+        channels = 1
+    else:
+        raise _lib.SmilError(f"the depth buffer must be uint8 or float32, got {depth.dtype}")
+    B, H, W = int(depth.shape[0]), int(depth.shape[1]), int(depth.shape[2])
+    if kp_norm.dim() != 3 or kp_norm.shape[0] != B or kp_norm.shape[2] != 2:
+        raise _lib.SmilError(f"kp_norm must be ({B},P,2), got {tuple(kp_norm.shape)}")
+    P = int(kp_norm.shape[1])
+    for name, t, dt in (("kp_norm", kp_norm, torch.float64), ("kp_dist", kp_dist, torch.float64), ("visibility", visibility, torch.float32)):
+        if t.dtype != dt or t.device != dev:
+            raise _lib.SmilError(f"{name} must be {dt} on {dev}, got {t.dtype} on {t.device}")
+    if tuple(kp_dist.shape) != (B, P) or tuple(visibility.shape) != (B, P):
+        raise _lib.SmilError(f"kp_dist and visibility must be ({B},{P}), got {tuple(kp_dist.shape)} and {tuple(visibility.shape)}")
+    depth, kp_norm, kp_dist, visibility = depth.contiguous(), kp_norm.contiguous(), kp_dist.contiguous(), visibility.contiguous()
+    out = torch.empty(B, P, dtype=torch.float32, device=dev)
+    surface = torch.empty(B, P, dtype=torch.float64, device=dev) if want_surface else None
+    _lib.check(_lib.load().smil_depth_visibility(_ptr(depth), int(depth.dtype == torch.uint8), channels,
+                                                 float(0.0 if depth_max is None else depth_max), B, H, W, _ptr(kp_norm), _ptr(kp_dist), P,
+                                                 _ptr(visibility), float(tolerance), int(neighborhood), _ptr(out), _ptr(surface), _stream()),
+               "smil_depth_visibility")
+    return (out, surface) if want_surface else out
 
 
 def image_abs_sum(images: torch.Tensor) -> torch.Tensor:

@@ -343,6 +343,31 @@ class SMALFitter(nn.Module):
         finally:
             self.renderer.cameras = cam_all
 
+    def posed_mesh(self):
+        """``(vertices (frames,V,3), canonical joints (frames,Jc,3))`` of the current parameters, in world space, without gradient:
+        what a fit iteration renders."""
+        with torch.no_grad():
+            n = self.num_images
+            theta = torch.cat([(self.global_rotation.detach() * self.global_mask)[:, None], self.joint_rotations.detach() * self.rotation_mask], 1)
+            verts, joints, _, _ = self.smal_model(self.betas.detach()[None].expand(n, -1), theta, betas_logscale=self.log_beta_scales.detach(),
+                                                  betas_trans=self.betas_trans.detach(), propagate_scaling=self.propagate_scaling)
+            trans = self.trans.detach()[:, None]
+            return (verts + trans).contiguous(), (joints + trans)[:, list(self.config.CANONICAL_MODEL_JOINTS)].contiguous()
+
+    def joint_self_occlusion(self, tolerance: float, neighborhood: int = 1) -> torch.Tensor:
+        """(frames * views, Jc) float32: 1 where the canonical joint of the current parameters is seen by the image's camera, 0 where
+        the posed mesh itself hides it (``Renderer.keypoint_visibility`` through the fitter's own renderer and cameras, with the
+        fitter's ``fov``).  ``tolerance`` (world units) must exceed the depth of the joints under the skin.  Reads only: target
+        visibilities, the cached epoch and captured graphs stay as they are."""
+        verts, canon = self.posed_mesh()
+        cam_all = self.renderer.cameras
+        try:
+            self.renderer.cameras = FoVCameras(cam_all.R, cam_all.T, self.fov.detach().reshape(-1), cam_all.aspect_ratio, cam_all.znear, cam_all.zfar,
+                                               getattr(cam_all, "principal_point", None))
+            return self.renderer.keypoint_visibility(verts, canon, self.smal_model.faces[None].expand(verts.shape[0], -1, -1), tolerance, neighborhood)
+        finally:
+            self.renderer.cameras = cam_all
+
     def export_parameters(self, frame_id: int) -> Dict[str, np.ndarray]:
         """The per-frame dict the reference pickles (optimize_to_joints.py:48-63, fitter.py:241-261,507)."""
         ls = self.log_beta_scales.detach()

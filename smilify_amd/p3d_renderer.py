@@ -181,6 +181,56 @@ class Renderer(torch.nn.Module):
         with torch.no_grad():
             return engine.render_colour(dm, self._camera_set(), vertices.detach().float().contiguous(), self.mesh_color.reshape(3).tolist())
 
+    def render_fragments(self, vertices, faces, want=engine.FRAGMENT_OUTPUTS) -> engine.Fragments:
+        """What the hard rasteriser of the colour branch finds per pixel (p3d_renderer.py:54-70: blur 0, K = 1), as an
+        ``engine.Fragments`` tuple over B * views images, image n = frame * views + view: ``pix_to_face`` (n,S,S) int32 face id of
+        the mesh (-1: background), ``zbuf`` (n,S,S) view depth (-1), ``bary`` (n,S,S,3) perspective-correct barycentrics of the
+        original face (-1) and ``dist`` (n,S,S) the distance from the camera centre to the surface point (+inf).  No gradient."""
+        dm = self._device_model(faces, vertices.shape[1])
+        with torch.no_grad():
+            return engine.render_fragments(dm, self._camera_set(), vertices.detach().float().contiguous(), want=want)
+
+    def render_depth(self, vertices, faces, kind: str = "z") -> torch.Tensor:
+        """Depth map (B * views, S, S) float32 of the mesh: ``kind="z"`` the view depth (background -1, pytorch3d's ``zbuf``),
+        ``kind="distance"`` the Euclidean distance from the camera centre (background +inf), the convention of a depth pass that
+        ``visibility.refine_visibility_with_depth`` tests keypoints against.  No gradient."""
+        if kind not in ("z", "distance"):
+            raise ValueError(f"kind must be 'z' or 'distance', got {kind!r}")
+        name = "zbuf" if kind == "z" else "dist"
+        return getattr(self.render_fragments(vertices, faces, want=(name,)), name)
+
+    def keypoint_visibility(self, vertices, points, faces, tolerance: float, neighborhood: int = 1, visibility=None) -> torch.Tensor:
+        """Which of ``points`` (B,P,3) the mesh ``vertices`` (B,V,3) hides from each camera: (B * views, P) float32, 1 = visible (or
+        whatever ``visibility`` (B * views, P) held coming in), 0 where the point lies more than ``tolerance`` behind the nearest
+        surface seen within ``neighborhood`` pixels of its projection.  The test is the reference's depth refinement
+        (Unreal2Pytorch3D.py:664-760) run against the mesh's own distance map instead of a rendered depth PNG; points that project
+        outside the image, onto background, or that are not finite keep their visibility.
+
+        ``tolerance`` is in world units.  Model joints lie INSIDE the skin, so every one of them is behind the surface it is seen
+        through: the tolerance must exceed the depth of the joints under that surface, or interior joints are declared hidden - the
+        reference's own note at :712-717 (there with one LSB of the 8-bit depth pass on top, which a float map does not have).
+        No gradient."""
+        cams = self._camera_set()
+        S, views = self.image_size, self.views
+        with torch.no_grad():
+            pts = points.detach().float().contiguous()
+            B, P = pts.shape[0], pts.shape[1]
+            N = B * views
+            dist_map = self.render_depth(vertices, faces, kind="distance")
+            _, yx = engine.project(cams, pts, want_ndc=False)
+            kp_norm = yx.double() / float(S)
+            # the points' distances to each image's camera centre C = -T R^T, in float64
+            img = torch.arange(N, device=pts.device)
+            R = cams.R.double()[img % cams.R.shape[0]]
+            T = cams.T.double()[img % cams.T.shape[0]]
+            centre = -torch.einsum("nk,nqk->nq", T, R)
+            kp_dist = (pts.double()[img // views] - centre[:, None]).norm(dim=-1)
+            if visibility is None:
+                vis = torch.ones(N, P, dtype=torch.float32, device=pts.device)
+            else:
+                vis = torch.as_tensor(visibility).to(device=pts.device, dtype=torch.float32).reshape(N, P)
+            return engine.depth_visibility(dist_map, kp_norm.contiguous(), kp_dist.contiguous(), vis, tolerance, neighborhood)
+
     def forward(self, vertices, points, faces, render_texture=False, joints_only=False):
         if render_texture and not self.colour:
             raise NotImplementedError("colour output is opt-in: construct Renderer(image_size, device, colour=True) "
