@@ -687,6 +687,61 @@ int smil_refine_points(const double *P, const double *obs, const uint32_t *view_
                        double f_scale, int32_t max_steps, double *xyz, int32_t *status, int32_t *n_accepted, int32_t *n_trials,
                        double *cost0, double *cost, double *view_err, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Target image preparation (smilify_amd/csrc/imageprep.hip, smilify_amd/imageprep.py).  Replaces the host loops that make the
+ * fitter's silhouette and RGB targets in the reference: cv2.undistort per frame (smal_fitter/sleap_data/
+ * preprocess_sleap_multiview_dataset.py:710-735, :969-1028) and crop_to_silhouette (smal_fitter/utils.py:7-49: bounding box, 1.05 x
+ * square, padding, cv2.resize).  No gradient, no workspace, asynchronous on `stream`; two calls give the same bits.
+ * ---------------------------------------------------------------------------------------- */
+/* sil (N,H,W), uint8 (sil_is_u8) or float32 -> bounds (N,5) int32 = y_min, y_max, x_min, x_max, count over the pixels > 0 (a NaN is
+ * not); an image without one keeps H, -1, W, -1, 0.  Integer minima, maxima and sums only.  Pixels are indexed as int in slabs of 2^16:
+ * H W <= 2^31 - 1 - 2^16 and N ceil(H W / 2^16) <= 2^31 - 1 (the grid) are required. */
+int smil_image_bounds(const void *sil, int32_t sil_is_u8, int64_t N, int32_t H, int32_t W, int32_t *bounds, void *stream);
+
+#define SMIL_WARP_EXACT 0          /* coordinate modes */
+#define SMIL_WARP_RESIZE_LINEAR 1
+#define SMIL_WARP_RESIZE_NEAREST 2
+#define SMIL_WARP_NEAREST 0        /* interpolation */
+#define SMIL_WARP_BILINEAR 1
+/* One resampling of N output images of S_h x S_w pixels from N_src source images; output image n reads source image n % N_src and row
+ * n % k of every table of k rows (k >= 1).  For output column j and row i, in float64 and without contraction:
+ *   SMIL_WARP_EXACT           u = ax j + bx, v = ay i + by.  With a lens (K, K_new, dist all non-NULL; this mode only) these are pixels
+ *                             of the camera K_new: x = (u - K_new[0][2]) / K_new[0][0], y = (v - K_new[1][2]) / K_new[1][1],
+ *                             r2 = x x + y y, radial = 1 + k1 r2 + k2 r2^2 + k3 r2^3, xd = x radial + 2 p1 x y + p2 (r2 + 2 x x),
+ *                             yd = y radial + p1 (r2 + 2 y y) + 2 p2 x y, and (u, v) <- (K[0][0] xd + K[0][2], K[1][1] yd + K[1][2])
+ *                             (cv2.undistort / initUndistortRectifyMap as documented; skew and the other entries of K are not read).
+ *                             nearest: the tap is floor(u + 0.5); bilinear: x0 = floor(u), fraction = float32(u - x0).
+ *   SMIL_WARP_RESIZE_LINEAR   cv2.resize INTER_LINEAR: f = float32((j + 0.5) ax - 0.5), sx = floor(f), fraction = f - sx, and the
+ *                             taps are (int)bx + sx and the next one: bx, by are the integral origin of the resized rectangle.
+ *   SMIL_WARP_RESIZE_NEAREST  cv2.resize INTER_NEAREST: the tap is (int)bx + floor(j ax).
+ * The interpolation of the two resize modes is their own.  A tap index is first clamped into clamp = (x_lo, x_hi, y_lo, y_hi)
+ * (inclusive, source pixels; NULL: no clamp) - cv2.resize's edge replication, with the rectangle's last pixel as its min(.., side - 1)
+ * - and a tap that then lies outside [0, W) x [0, H) reads border[c].  A non-finite u or v reads the border in every tap.
+ * Bilinear: with the four taps a b / c d and the float32 fractions wx, wy: top = a + wx (b - a), bottom = c + wx (d - c),
+ * value = top + wy (bottom - top), each operation rounded to float32 once (two equal taps give that tap exactly).  The value is
+ * multiplied by `scale`.
+ *   src      (N_src,H,W,C) channels-last, uint8 (src_is_u8) or float32; C in 1 .. 4
+ *   out      (N,S_h,S_w,C), or with `planar` (N,C,S_h,S_w); float32, or with out_is_u8 uint8 = rint(min(max(value, 0), 255))
+ *   affine   (n_affine,4) float64 = ax, bx, ay, by
+ *   K, K_new (n_lens,3,3), dist (n_lens,5) = k1, k2, p1, p2, k3, float64; all three or none
+ *   clamp    (n_clamp,4) int32 or NULL;  border (n_border,C) float32
+ * Sizes, modes, table lengths and pointers are checked, and whatever cannot be indexed is refused, before anything is launched:
+ * H, W < 2^30 (tap coordinates are int; the source itself is indexed with size_t, so H W is not bounded), S_h S_w <= 2^31 - 1 - 256
+ * (an output pixel of one image is an int) and N ceil(S_h S_w / 256) <= 2^31 - 1 (the grid). */
+typedef struct {
+    const void *src;
+    int32_t src_is_u8, N_src, H, W, C;
+    void *out;
+    int32_t out_is_u8, planar, N, S_h, S_w;
+    int32_t coord_mode, interp;
+    const double *affine; int32_t n_affine;
+    const double *K, *K_new, *dist; int32_t n_lens;
+    const int32_t *clamp; int32_t n_clamp;
+    const float *border; int32_t n_border;
+    float scale;
+} SmilWarp;
+int smil_warp_images(const SmilWarp *w, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,7 @@ EXPORTS = [
     "smil_triangulate",
     "smil_refine_workspace_bytes", "smil_refine_evaluate", "smil_refine_cameras",
     "smil_refine_points_evaluate", "smil_refine_points",
+    "smil_image_bounds", "smil_warp_images",
 ]
 
 N_OBJS = 10
@@ -95,6 +96,14 @@ class FitConfig(Structure):
                 ("limit", c_float), ("train_global", c_int32), ("train_joints", c_int32), ("train_trans", c_int32)]
 
 
+class Warp(Structure):
+    _fields_ = [("src", c_void_p), ("src_is_u8", c_int32), ("N_src", c_int32), ("H", c_int32), ("W", c_int32), ("C", c_int32),
+                ("out", c_void_p), ("out_is_u8", c_int32), ("planar", c_int32), ("N", c_int32), ("S_h", c_int32), ("S_w", c_int32),
+                ("coord_mode", c_int32), ("interp", c_int32), ("affine", c_void_p), ("n_affine", c_int32),
+                ("K", c_void_p), ("K_new", c_void_p), ("dist", c_void_p), ("n_lens", c_int32), ("clamp", c_void_p), ("n_clamp", c_int32),
+                ("border", c_void_p), ("n_border", c_int32), ("scale", c_float)]
+
+
 class MeshTopology(Structure):
     _fields_ = [("V", c_int32), ("E", c_int32), ("Q", c_int32)] + [
         (n, c_void_p) for n in ("edges", "pairs", "nbr_ptr", "nbr", "inv_deg", "vpair_ptr", "vpair")]
@@ -111,6 +120,8 @@ TRI_RANSAC, TRI_KEEP_ALL_VIEWS = 1, 2  # SMIL_TRI_RANSAC, SMIL_TRI_KEEP_ALL_VIEW
 REFINE_MIN_POINTS = 20  # SMIL_REFINE_MIN_POINTS
 REFINE_CONVERGED, REFINE_STEP_LIMIT, REFINE_SKIPPED, REFINE_NONFINITE = 0, 1, 2, 3  # SMIL_REFINE_*
 REFINE_POINTS_FEW_VIEWS = 2  # SMIL_REFINE_POINTS_FEW_VIEWS
+WARP_EXACT, WARP_RESIZE_LINEAR, WARP_RESIZE_NEAREST = 0, 1, 2  # SMIL_WARP_* coordinate modes
+WARP_NEAREST, WARP_BILINEAR = 0, 1  # SMIL_WARP_* interpolation
 
 _lib = None
 
@@ -216,6 +227,8 @@ def load():
     lib.smil_refine_cameras.argtypes = [c_void_p] * 4 + [c_int32, c_void_p, c_int32, c_double, c_int32] + [c_void_p] * 9
     lib.smil_refine_points_evaluate.argtypes = [c_void_p] * 4 + [c_int64, c_int32, c_int32, c_double] + [c_void_p] * 4
     lib.smil_refine_points.argtypes = [c_void_p] * 4 + [c_int64, c_int32, c_int32, c_double, c_int32] + [c_void_p] * 8
+    lib.smil_image_bounds.argtypes = [c_void_p, c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p]
+    lib.smil_warp_images.argtypes = [POINTER(Warp), c_void_p]
     lib.smil_profile_enable.argtypes = [c_int32]
     lib.smil_profile_read.argtypes = [POINTER(c_float), POINTER(c_int32)]
     for name in EXPORTS:

@@ -1212,3 +1212,112 @@ def refine_points(P: torch.Tensor, obs: torch.Tensor, view_mask: torch.Tensor, x
                                               _ptr(xyz), _ptr(status), _ptr(n_acc), _ptr(n_trial), _ptr(cost0), _ptr(cost), _ptr(view_err),
                                               _stream()), "smil_refine_points")
     return xyz, status, n_acc, n_trial, cost0, cost, view_err
+
+
+# ---- target image preparation (csrc/imageprep.hip) ----
+WARP_COORD_MODES = {"exact": _lib.WARP_EXACT, "resize_linear": _lib.WARP_RESIZE_LINEAR, "resize_nearest": _lib.WARP_RESIZE_NEAREST}
+WARP_INTERPOLATIONS = {"nearest": _lib.WARP_NEAREST, "bilinear": _lib.WARP_BILINEAR}
+
+
+def image_bounds(sil: torch.Tensor) -> torch.Tensor:
+    """sil (N,H,W) uint8 or float32 -> (N,5) int32 ``y_min, y_max, x_min, x_max, count`` over the pixels > 0; an image without one
+    keeps ``H, -1, W, -1, 0`` (smil_image_bounds, include/smilfit.h).  An exact integer reduction: two calls give the same bits."""
+    if not isinstance(sil, torch.Tensor) or sil.dim() != 3 or sil.dtype not in (torch.uint8, torch.float32):
+        raise ValueError("image_bounds: sil must be a uint8 or float32 tensor (N, H, W)")
+    N, H, W = (int(v) for v in sil.shape)
+    if H < 1 or W < 1 or H * W > 2**31 - 2**16 - 1:
+        raise ValueError(f"image_bounds: images of {H} x {W} pixels cannot be indexed")
+    dev = require_gpu(sil.device)
+    sil = sil.contiguous()
+    bounds = torch.empty(N, 5, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().smil_image_bounds(_ptr(sil), int(sil.dtype == torch.uint8), N, H, W, _ptr(bounds), _stream()), "smil_image_bounds")
+    return bounds
+
+
+def _warp_table(name, t, row_shape, dtype, device):
+    """A per-image table: (k, *row_shape) of dtype on device with k >= 1 (a single row may come without the leading axis)."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+        raise ValueError(f"warp_images: {name} must be a {dtype} tensor (k, {', '.join(map(str, row_shape))})")
+    if tuple(t.shape) == tuple(row_shape):
+        t = t[None]
+    if t.dim() != len(row_shape) + 1 or tuple(t.shape[1:]) != tuple(row_shape) or t.shape[0] < 1:
+        raise ValueError(f"warp_images: {name} must be (k, {', '.join(map(str, row_shape))}) with k >= 1, got {tuple(t.shape)}")
+    if t.device != device:
+        raise ValueError(f"warp_images: {name} must be on {device}, got {t.device}")
+    return t.contiguous()
+
+
+def warp_images(src: torch.Tensor, size, affine: torch.Tensor, *, coord_mode: str = "exact", interpolation: str = "bilinear",
+                K: Optional[torch.Tensor] = None, K_new: Optional[torch.Tensor] = None, dist: Optional[torch.Tensor] = None,
+                clamp: Optional[torch.Tensor] = None, border: Optional[torch.Tensor] = None, scale: float = 1.0, planar: bool = False,
+                n_out: Optional[int] = None, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """One resampling of ``n_out`` images of ``size = (S_h, S_w)`` from ``src`` (N_src,H,W,C) channels-last or (N_src,H,W), uint8 or
+    float32, C in 1 .. 4 (smil_warp_images, include/smilfit.h, states the map to the bit).  Output image n reads source image
+    ``n % N_src`` and row ``n % k`` of every table: ``affine`` (k,4) float64 = ``ax, bx, ay, by``; ``K``, ``K_new`` (k,3,3) and
+    ``dist`` (k,5) float64, all three or none (``coord_mode="exact"`` only); ``clamp`` (k,4) int32 = ``x_lo, x_hi, y_lo, y_hi`` or
+    None; ``border`` (k,C) float32, None: zeros.  ``n_out`` defaults to the longest of N_src and the tables.  Returns float32 (or, with
+    ``out_dtype=torch.uint8``, the rounded and clipped bytes) ``(N,S_h,S_w,C)`` - without the channel axis for a 3-D ``src`` - or with
+    ``planar`` ``(N,C,S_h,S_w)``.  Everything is checked before the device is touched."""
+    if not isinstance(src, torch.Tensor) or src.dim() not in (3, 4) or src.dtype not in (torch.uint8, torch.float32):
+        raise ValueError("warp_images: src must be a uint8 or float32 tensor (N_src, H, W, C) or (N_src, H, W)")
+    has_c = src.dim() == 4
+    N_src, H, W = (int(v) for v in src.shape[:3])
+    C = int(src.shape[3]) if has_c else 1
+    if not 1 <= C <= 4:
+        raise ValueError(f"warp_images: C={C} channels, 1 to 4 are supported")
+    if N_src < 1 or H < 1 or W < 1 or H >= 2**30 or W >= 2**30:
+        raise ValueError(f"warp_images: bad source sizes N_src={N_src} H={H} W={W}")
+    try:
+        S_h, S_w = (int(v) for v in size)
+    except TypeError:
+        S_h = S_w = int(size)
+    if S_h < 1 or S_w < 1 or S_h * S_w > 2**31 - 257:
+        raise ValueError(f"warp_images: bad output size {S_h} x {S_w}")
+    if coord_mode not in WARP_COORD_MODES or interpolation not in WARP_INTERPOLATIONS:
+        raise ValueError(f"warp_images: coord_mode is one of {sorted(WARP_COORD_MODES)} and interpolation one of "
+                         f"{sorted(WARP_INTERPOLATIONS)}, got {coord_mode!r} and {interpolation!r}")
+    own = {"resize_linear": "bilinear", "resize_nearest": "nearest"}.get(coord_mode)
+    if own is not None and interpolation != own:
+        raise ValueError(f"warp_images: coord_mode {coord_mode!r} goes with interpolation {own!r}")
+    if out_dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f"warp_images: out_dtype must be float32 or uint8, got {out_dtype}")
+    dev = src.device
+    affine = _warp_table("affine", affine, (4,), torch.float64, dev)
+    if affine is None:
+        raise ValueError("warp_images: affine is required")
+    lens = [K, K_new, dist]
+    if any(t is not None for t in lens) and any(t is None for t in lens):
+        raise ValueError("warp_images: K, K_new and dist come together")
+    K, K_new = _warp_table("K", K, (3, 3), torch.float64, dev), _warp_table("K_new", K_new, (3, 3), torch.float64, dev)
+    dist = _warp_table("dist", dist, (5,), torch.float64, dev)
+    if K is not None:
+        if coord_mode != "exact":
+            raise ValueError("warp_images: a lens needs coord_mode='exact'")
+        if not (K.shape[0] == K_new.shape[0] == dist.shape[0]):
+            raise ValueError(f"warp_images: K, K_new and dist must have the same number of rows, got {K.shape[0]}, {K_new.shape[0]}, {dist.shape[0]}")
+    clamp = _warp_table("clamp", clamp, (4,), torch.int32, dev)
+    if border is None:
+        border = torch.zeros(1, C, dtype=torch.float32, device=dev)
+    border = _warp_table("border", border, (C,), torch.float32, dev)
+    tables = [affine.shape[0], border.shape[0]] + ([K.shape[0]] if K is not None else []) + ([clamp.shape[0]] if clamp is not None else [])
+    N = max([N_src] + tables) if n_out is None else int(n_out)
+    if N < 0 or N * ((S_h * S_w + 255) // 256) > 2**31 - 1:
+        raise ValueError(f"warp_images: {N} output images of {S_h} x {S_w} pixels cannot be launched in one call")
+    dev = require_gpu(dev)
+    src = src.contiguous()
+    shape = (N, C, S_h, S_w) if planar else ((N, S_h, S_w, C) if has_c else (N, S_h, S_w))
+    out = torch.empty(shape, dtype=out_dtype, device=dev)
+    w = _lib.Warp()
+    w.src, w.src_is_u8, w.N_src, w.H, w.W, w.C = src.data_ptr(), int(src.dtype == torch.uint8), N_src, H, W, C
+    w.out, w.out_is_u8, w.planar, w.N, w.S_h, w.S_w = out.data_ptr(), int(out_dtype == torch.uint8), int(bool(planar)), N, S_h, S_w
+    w.coord_mode, w.interp = WARP_COORD_MODES[coord_mode], WARP_INTERPOLATIONS[interpolation]
+    w.affine, w.n_affine = affine.data_ptr(), int(affine.shape[0])
+    if K is not None:
+        w.K, w.K_new, w.dist, w.n_lens = K.data_ptr(), K_new.data_ptr(), dist.data_ptr(), int(K.shape[0])
+    if clamp is not None:
+        w.clamp, w.n_clamp = clamp.data_ptr(), int(clamp.shape[0])
+    w.border, w.n_border, w.scale = border.data_ptr(), int(border.shape[0]), float(scale)
+    _lib.check(_lib.load().smil_warp_images(ctypes.byref(w), _stream()), "smil_warp_images")
+    return out
