@@ -227,6 +227,13 @@ __device__ __forceinline__ const T &at(const T *base, uint32_t i) {
     return *reinterpret_cast<const T *>(reinterpret_cast<const char *>(base) + byte_offset<T>(i));
 }
 
+// The lane index as a value the compiler cannot trace back to threadIdx.x: what is derived from it (an LDS address, a table offset) is
+// recomputed where it is used, an instruction or two, and not kept for the whole kernel in a register that then spills.
+__device__ __forceinline__ int opaque_lane(int lane) {
+    asm volatile("" : "+v"(lane));
+    return lane;
+}
+
 // inclusive wave64 prefix sum in DPP (row_shr within 16-lane rows, then row_bcast across rows)
 __device__ __forceinline__ int wave_scan_add(int x) {
 #define SCAN_STEP(ctrl, rows) { x += __builtin_amdgcn_update_dpp(0, x, ctrl, rows, 0xF, false); }
@@ -234,6 +241,36 @@ __device__ __forceinline__ int wave_scan_add(int x) {
     SCAN_STEP(0x142, 0xA) SCAN_STEP(0x143, 0xC)
 #undef SCAN_STEP
     return x;
+}
+
+// The record sweeps hold a buffer of N rows of 64 records; the buffer that meets the end of its range holds fewer.  A row body asks
+// rows.has(u) before it touches row u, in its gather phase and again in its arithmetic: for a full buffer (RowsAll) that folds away
+// and the body is the straight-line code it always was; for the last buffer (RowsUpto) it is a scalar branch per row and phase - the
+// ranges are scalars, so the count is wave-uniform - and the rows behind the end cost nothing.
+struct RowsAll { __device__ constexpr bool has(int) const { return true; } };
+struct RowsUpto { int n; __device__ bool has(int u) const { return u < n; } };
+static_assert(WAVE == 64, "rows_upto shifts by log2(WAVE)");
+__device__ __forceinline__ int rows_upto(int g0, int end) { return (end - g0 + WAVE - 1) >> 6; }  // rows that the records [g0, end) touch
+// Double-buffered sweep over the records [beg, end), beg < end, N rows per buffer; the caller has requested load(ra, beg).  While a
+// buffer is processed the next one is in flight, as long as there is a next one: a buffer behind `end` is neither loaded nor processed.
+// The loop is the one every sweep had - two full buffers per turn, straight line - and runs while a whole turn is full; the one or
+// two buffers that remain, the last of them up to `end`, follow it.  Rows are processed in stream order.
+template <int N, typename Buf, typename Load, typename Body>
+__device__ __forceinline__ void sweep_rows(int beg, int end, Buf (&ra)[N], Buf (&rb)[N], Load &&load, Body &&body) {
+    int g0 = beg;
+    for (; g0 + 2 * N * WAVE < end; g0 += 2 * N * WAVE) {
+        load(rb, g0 + N * WAVE);
+        body(RowsAll(), ra, g0);
+        load(ra, g0 + 2 * N * WAVE);
+        body(RowsAll(), rb, g0 + N * WAVE);
+    }
+    if (g0 + N * WAVE < end) {
+        load(rb, g0 + N * WAVE);
+        body(RowsAll(), ra, g0);
+        body(RowsUpto{rows_upto(g0 + N * WAVE, end)}, rb, g0 + N * WAVE);
+    } else {
+        body(RowsUpto{rows_upto(g0, end)}, ra, g0);
+    }
 }
 
 #ifndef SETUP_THREADS
@@ -401,6 +438,23 @@ __device__ __forceinline__ int cvt_round(float x) {
 __device__ __forceinline__ unsigned long long pack_fx2(float x, float y) {
     const int qx = cvt_round(x), qy = cvt_round(y);
     return ((unsigned long long)(uint32_t)(qx + (qy >> 31)) << 32) | (unsigned long long)(uint32_t)qy;
+}
+
+// What a record hands to the end points a, b of its closest edge in pass 3: the closest point of the edge is the clamped projection of
+// the pixel c, as eval_pair computed it (t = 0 for a degenerate edge); r = closest point - pixel; the end points share 2 r gd as
+// (1 - t) : t.  Every rounding is spelled out and contraction is off: the row body of pass 3 exists in two instances (sweep_rows) and
+// left to itself the compiler fuses their multiplies and adds differently - a unit in the last place of a fixed-point contribution.
+// The fused operations are the ones the single instance compiled to.
+struct EdgeGrad { float ax, ay, bx, by; };
+__device__ __forceinline__ EdgeGrad edge_gradient(float2 pa, float2 pb, float2 pc, float gd) {
+#pragma clang fp contract(off)
+    const float exx = pb.x - pa.x, eyy = pb.y - pa.y;
+    const float l2 = exx * exx + eyy * eyy;
+    const float dot = fmaf(exx, pc.x - pa.x, eyy * (pc.y - pa.y));
+    const float t = __builtin_amdgcn_fmed3f(dot * (l2 <= K_EPS ? 0.f : __builtin_amdgcn_rcpf(l2)), 0.f, 1.f);
+    const float rx2 = 2.0f * fmaf(t, exx, pa.x - pc.x), ry2 = 2.0f * fmaf(t, eyy, pa.y - pc.y);
+    const float bx = t * (rx2 * gd), by = t * (ry2 * gd);
+    return EdgeGrad{fmaf(rx2, gd, -bx), fmaf(ry2, gd, -by), bx, by};
 }
 
 __device__ __forceinline__ float face_prob(float sd, float inv_sigma_log2e) {

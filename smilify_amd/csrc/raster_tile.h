@@ -132,7 +132,7 @@ __device__ __forceinline__ void sort_list_near_to_far(const uint2 *list, uint32_
     const int c = lane < n_buckets ? lds.start[lane] : 0;
     const int incl = wave_scan_add(c);
     __syncthreads();
-    if (lane < n_buckets) lds.bstart[lane] = (uint16_t)min(incl - c, 65535);
+    if (lane < n_buckets) lds.bstart[opaque_lane(lane)] = (uint16_t)min(incl - c, 65535);
     lds.start[lane] = incl - c;  // running cursor of every bucket
     __syncthreads();
     for (int i0 = 0; i0 < n; i0 += 4 * WAVE) {
@@ -344,12 +344,14 @@ __device__ __forceinline__ int refine_sweep(DenseLds &lds, Rec3 *crec, int n_rec
             r[u].kk = q.a; r[u].mt = q.b; r[u].lf = __uint_as_float(q.c);
         }
     };
-    auto sift_recs = [&](const CRec (&r)[KGROUP], int g0) {
+    auto sift_rows = [&](auto rows, const CRec (&r)[KGROUP], int g0) {  // (rows.has: sweep_rows)
         uint2 ps[KGROUP];  // all LDS gathers first: one latency, not one per row
 #pragma unroll
-        for (int u = 0; u < KGROUP; ++u) ps[u] = lds.psel[r[u].mt & 63u];
+        for (int u = 0; u < KGROUP; ++u)
+            if (rows.has(u)) ps[u] = lds.psel[r[u].mt & 63u];
 #pragma unroll
         for (int u = 0; u < KGROUP; ++u) {
+            if (!rows.has(u)) continue;
             const uint32_t pxl = r[u].mt & 63u;
             const bool live = (g0 + u * WAVE + lane < n_rec) & (ps[u].y > 0u);
             const uint32_t top = r[u].kk >> nbits;
@@ -368,12 +370,7 @@ __device__ __forceinline__ int refine_sweep(DenseLds &lds, Rec3 *crec, int n_rec
     if (n_rec > 0) {  // double-buffered: the next KGROUP rows are in flight while this one is sifted
         CRec ra[KGROUP], rb[KGROUP];
         load_recs(ra, 0);
-        for (int g0 = 0; g0 < n_rec; g0 += 2 * KGROUP * WAVE) {
-            load_recs(rb, g0 + KGROUP * WAVE);
-            sift_recs(ra, g0);
-            load_recs(ra, g0 + 2 * KGROUP * WAVE);
-            sift_recs(rb, g0 + KGROUP * WAVE);
-        }
+        sweep_rows<KGROUP>(0, n_rec, ra, rb, load_recs, sift_rows);
     }
     __syncthreads();
     return n_out;
@@ -570,7 +567,7 @@ __global__ void __launch_bounds__(64, WAVES_PER_SIMD) k_raster_dense(RasterArgs 
                 const int c = lane < n_buckets ? lds.start[lane] : 0;
                 const int incl = wave_scan_add(c);
                 lds_fence();
-                if (lane < n_buckets) lds.bstart[lane] = (uint16_t)min(incl - c, 65535);
+                if (lane < n_buckets) lds.bstart[opaque_lane(lane)] = (uint16_t)min(incl - c, 65535);
                 lds.start[lane] = incl - c;  // running cursor of every bucket
                 lds_fence();
                 for (int i0 = 0; i0 < list_total; i0 += 4 * WAVE) {
@@ -658,8 +655,9 @@ __global__ void __launch_bounds__(64, WAVES_PER_SIMD) k_raster_dense(RasterArgs 
             tv_nx = load_tri(a, vn, xv_n, ja, jb, jc);
             for (int c0 = 0; c0 < list_total; c0 += DCHUNK) {
                 if (may_truncate) {
+                    const int lane_b = opaque_lane(lane);  // (the address of the lane's `bstart` entry is not kept across chunks)
                     // digit of this chunk's first face = number of buckets that start at or before it, minus one
-                    const int d0 = __popcll(__ballot(lane < (1 << b1) && (int)lds.bstart[lane] <= c0)) - 1;
+                    const int d0 = __popcll(__ballot(lane < (1 << b1) && (int)lds.bstart[lane_b] <= c0)) - 1;
                     if (d0 > final_digits) {  // wave-uniform: digits [final_digits, d0) have just become final
                         for (int d = final_digits; d < d0; ++d)
                             final_cnt += (int)((lds.hist[(d >> 2) * WAVE + lane] >> (8 * (d & 3))) & 0xFFu);
@@ -836,17 +834,20 @@ __global__ void __launch_bounds__(64, WAVES_PER_SIMD) k_raster_dense(RasterArgs 
                         r[u].z = q.a; r[u].mt = q.b; r[u].sd = __uint_as_float(q.c);
                     }
                 };
-                auto blend_recs = [&](const Rec (&r)[DGROUP], int g0) {
+                auto blend_rows = [&](auto rows, const Rec (&r)[DGROUP], int g0) {  // (rows.has: sweep_rows)
                     uint2 ps[DGROUP];
 #pragma unroll
-                    for (int u = 0; u < DGROUP; ++u) ps[u] = lds.psel[r[u].mt & 63u];
+                    for (int u = 0; u < DGROUP; ++u)
+                        if (rows.has(u)) ps[u] = lds.psel[r[u].mt & 63u];
 #pragma unroll
                     for (int u = 0; u < DGROUP; ++u) {
+                        if (!rows.has(u)) continue;
+                        STAT(59, 1)
                         const bool valid = g0 + u * WAVE + lane < vbase;
                         const uint32_t key = r[u].z - kmin, d1 = key >> nbits;
                         const bool sure = valid & ((ps[u].y == 0u) | (d1 < ps[u].x));
                         const bool maybe = valid & (ps[u].y > 0u) & (d1 == ps[u].x);
-                        rmax2 = fmaxf(rmax2, fabsf(r[u].sd));  // (the clamped tail repeats a record: harmless)
+                        rmax2 = fmaxf(rmax2, fabsf(r[u].sd));  // (the clamped tail of the last row repeats a record: harmless)
                         const float lf = __log2f(1.0f - face_prob(r[u].sd, a.inv_sigma_log2e));
                         if (sure & (lf != 0.f)) atomicAdd(&lds.plog[r[u].mt & 63u], (double)lf);
                         STAT(45, __popcll(__ballot(sure))) STAT(46, __popcll(__ballot(valid & !sure & !maybe)))
@@ -864,12 +865,8 @@ __global__ void __launch_bounds__(64, WAVES_PER_SIMD) k_raster_dense(RasterArgs 
                 };
                 Rec ra[DGROUP], rb[DGROUP];
                 load_recs(ra, 0);
-                for (int g0 = 0; g0 < vbase; g0 += 2 * DGROUP * WAVE) {
-                    load_recs(rb, g0 + DGROUP * WAVE);
-                    blend_recs(ra, g0);
-                    load_recs(ra, g0 + 2 * DGROUP * WAVE);
-                    blend_recs(rb, g0 + DGROUP * WAVE);
-                }
+                STAT(56, rows_upto(0, vbase)) STAT(57, (vbase + 2 * DGROUP * WAVE - 1) / (2 * DGROUP * WAVE) * (2 * DGROUP))  // rows needed; rows of whole turns
+                sweep_rows<DGROUP>(0, vbase, ra, rb, load_recs, blend_rows);
             }
             __syncthreads();
             TSUB(4)
@@ -1160,9 +1157,10 @@ __global__ void __launch_bounds__(64, WAVES_PER_SIMD) k_raster_dense(RasterArgs 
                     };
                     GRec ra[DGROUP], rb[DGROUP];
                     load_recs(ra, i_beg);
-                    fv[lane * 3 + 0] = tv0;
-                    fv[lane * 3 + 1] = tv1;
-                    fv[lane * 3 + 2] = tv2;
+                    const int lane_g = opaque_lane(lane);  // (the row's LDS address is recomputed per group, not reloaded from scratch)
+                    fv[lane_g * 3 + 0] = tv0;
+                    fv[lane_g * 3 + 1] = tv1;
+                    fv[lane_g * 3 + 2] = tv2;
                     TP3(1)
                     for (int i_ = lane; i_ < GCOPIES * GCHUNK * 3; i_ += WAVE) (&lds.gacc[0][0])[i_] = 0ull;
                     lds_fence();
@@ -1171,12 +1169,16 @@ __global__ void __launch_bounds__(64, WAVES_PER_SIMD) k_raster_dense(RasterArgs 
                     // contribution whether it is kept or not and only the two accumulator adds are predicated, so that the LDS gathers of
                     // all rows of a buffer are in flight together (a branch per record kept each row's gathers behind the previous row's
                     // conflicting atomics: one exposed LDS round trip per row).
-                    auto grad_recs = [&](const GRec (&r)[DGROUP], int g0) {
+                    // The buffer that meets the group's end is processed for the rows that hold a record of the group only (sweep_rows,
+                    // rows.has), and a buffer behind the end is neither loaded nor processed: a group of 10 rows ran 16 before, with every
+                    // gather and every instruction of the body.
+                    auto grad_rows = [&](auto rows, const GRec (&r)[DGROUP], int g0) {
                         float4 pg[DGROUP];
                         float2 pa[DGROUP], pb[DGROUP], pc[DGROUP];
                         uint32_t oa[DGROUP], ob[DGROUP];
 #pragma unroll
                         for (int u = 0; u < DGROUP; ++u) {
+                            if (!rows.has(u)) continue;
                             const uint32_t mt = r[u].mt;
                             const uint32_t f3 = ((mt >> 6) & (uint32_t)(GCHUNK - 1)) * 3u;  // (list position % GCHUNK) * 3
                             const uint32_t edge = mt >> 23;
@@ -1186,6 +1188,8 @@ __global__ void __launch_bounds__(64, WAVES_PER_SIMD) k_raster_dense(RasterArgs 
                         }
 #pragma unroll
                         for (int u = 0; u < DGROUP; ++u) {
+                            if (!rows.has(u)) continue;
+                            STAT(63, 1)
                             const bool valid = g0 + u * WAVE + lane < i_end;
                             const uint32_t mt = r[u].mt;
                             const uint32_t zt_ = __float_as_uint(pg[u].y);
@@ -1202,13 +1206,8 @@ __global__ void __launch_bounds__(64, WAVES_PER_SIMD) k_raster_dense(RasterArgs 
                             const bool keep = valid & (gd != 0.f) & ((r[u].z < zt_) | ((r[u].z == zt_) & tie_ok));
                             // closest point of that edge: clamped projection of the pixel, as eval_pair computed it (t = 0 for a
                             // degenerate edge); r = closest point - pixel
-                            const float exx = pb[u].x - pa[u].x, eyy = pb[u].y - pa[u].y;
-                            const float l2 = exx * exx + eyy * eyy;
-                            const float t = __builtin_amdgcn_fmed3f((exx * (pc[u].x - pa[u].x) + eyy * (pc[u].y - pa[u].y)) * (l2 <= K_EPS ? 0.f : __builtin_amdgcn_rcpf(l2)), 0.f, 1.f);
-                            const float rx = fmaf(t, exx, pa[u].x - pc[u].x), ry = fmaf(t, eyy, pa[u].y - pc[u].y);
-                            const float ex = 2.0f * rx * gd, ey = 2.0f * ry * gd;
-                            const float bx = t * ex, by = t * ey;
-                            const unsigned long long ga = pack_fx2(ex - bx, ey - by), gb = pack_fx2(bx, by);
+                            const EdgeGrad eg = edge_gradient(pa[u], pb[u], pc[u], gd);
+                            const unsigned long long ga = pack_fx2(eg.ax, eg.ay), gb = pack_fx2(eg.bx, eg.by);
                             if (keep) {
                                 unsigned long long *acc = &lds.gacc[0][0] + copy_off;
                                 atomicAdd(acc + oa[u], ga);
@@ -1216,12 +1215,8 @@ __global__ void __launch_bounds__(64, WAVES_PER_SIMD) k_raster_dense(RasterArgs 
                             }
                         }
                     };
-                    for (int g0 = i_beg; g0 < i_end; g0 += 2 * DGROUP * WAVE) {
-                        load_recs(rb, g0 + DGROUP * WAVE);
-                        grad_recs(ra, g0);
-                        load_recs(ra, g0 + 2 * DGROUP * WAVE);
-                        grad_recs(rb, g0 + DGROUP * WAVE);
-                    }
+                    STAT(60, 1) STAT(61, rows_upto(i_beg, i_end)) STAT(62, (i_end - i_beg + 2 * DGROUP * WAVE - 1) / (2 * DGROUP * WAVE) * (2 * DGROUP))  // groups; rows needed; rows of whole turns
+                    sweep_rows<DGROUP>(i_beg, i_end, ra, rb, load_recs, grad_rows);
                     TP3(3)
                     lds_fence();
                     TP3(4)

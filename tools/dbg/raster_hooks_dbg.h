@@ -100,6 +100,8 @@ static inline void raster_dbg_report(unsigned long long *&dbg_out) {
         fprintf(stderr, "[dbg stats] (sub-)tiles with a truncated pixel %.4e (their records %.4e), that may truncate %.4e (records %.4e); pixels with a split tie group %.4e\n",
                 (double)h[40], (double)h[42], (double)h[41], (double)h[43], (double)h[44]);
         fprintf(stderr, "[dbg stats] blend sweep: records kept for certain %.4e, above their pixel's chosen first digit (dropped) %.4e\n", (double)h[45], (double)h[46]);
+        fprintf(stderr, "[dbg stats] rows of 64 records: blend sweep holds %.4e, whole double-buffer turns %.4e, executed %.4e; pass 3: groups with records %.4e, rows held %.4e, whole turns %.4e, executed %.4e\n",
+                (double)h[56], (double)h[57], (double)h[59], (double)h[60], (double)h[61], (double)h[62], (double)h[63]);
         (void)hipMemset(dbg_dev, 0, 512);
         { const unsigned long long big[3] = {~0ull, ~0ull, 0ull}; (void)hipMemcpy(dbg_dev + 5, big, 24, hipMemcpyHostToDevice); }
         dbg_out = dbg_dev;
