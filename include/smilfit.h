@@ -742,6 +742,44 @@ typedef struct {
 } SmilWarp;
 int smil_warp_images(const SmilWarp *w, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Rotation conversions (smilify_amd/csrc/rotations.hip, rot.h; smilify_amd/rotations.py).  Replaces the four pytorch3d.transforms
+ * functions of the reference's neural callers (smal_fitter/neuralSMIL/smil_image_regressor.py:26-96) and the matrices of its rotation
+ * losses (:2123-2163, :3117-3266).  Arrays hold n rotations, contiguous, as 6 (6-D), 3 (axis-angle), 9 (matrix, row-major) or 1
+ * (distance) values of the storage type `dtype`; all arithmetic is float64.  n == 0 succeeds without a launch; n < 0, a NULL required
+ * pointer or an unknown dtype is SMIL_E_INVALID.  No workspace, asynchronous on `stream`.  A backward call takes the forward's INPUTS
+ * and the upstream gradient and recomputes; it equals the first derivative of the formulas below with these conventions: the norm of
+ * a zero vector has derivative 0, max(x, e) passes the gradient where x >= e, sqrt+ has derivative 0 where its argument is <= 0.
+ *
+ *   6-D -> matrix     a1 = d[0:3], a2 = d[3:6]; b1 = a1 / max(|a1|, 1e-12); u = a2 - (b1 . a2) b1; b2 = u / max(|u|, 1e-12); the rows
+ *                     of R are b1, b2, b1 x b2.  Degenerate rows follow the formulas: zeros give the zero matrix.
+ *   axis-angle -> matrix   theta = |a|; q = (cos(theta / 2), a s) with s = sin(theta / 2) / theta, continued to 1/2 at 0; with
+ *                     q = (r, i, j, k) and t = 2 / (q . q):
+ *                     R = [[1 - t (jj + kk), t (ij - kr), t (ik + jr)], [t (ij + kr), 1 - t (ii + kk), t (jk - ir)],
+ *                          [t (ik - jr), t (jk + ir), 1 - t (ii + jj)]].
+ *   matrix -> axis-angle   for any 3 x 3 m: qa = sqrt+ of (1 + m00 + m11 + m22, 1 + m00 - m11 - m22, 1 - m00 + m11 - m22,
+ *                     1 - m00 - m11 + m22), sqrt+ x = sqrt(x) for x > 0, else 0.  Candidates (qa0^2, m21 - m12, m02 - m20, m10 - m01),
+ *                     (m21 - m12, qa1^2, m10 + m01, m02 + m20), (m02 - m20, m10 + m01, qa2^2, m12 + m21),
+ *                     (m10 - m01, m20 + m02, m21 + m12, qa3^2): the one of the largest qa (a tie: the lowest index), divided by
+ *                     2 max(qa_c, 0.1), negated as a whole where its first entry is negative.  Then n = |q[1:]|, h = atan2(n, q0),
+ *                     aa = q[1:] / (sin(h) / (2 h)), the divisor continued to 1/2 at h = 0.
+ *   distance          dist = the Frobenius norm of R(p) - R(t) of two 6-D rotations; its gradient is 0 where dist == 0. */
+#define SMIL_ROT_F32 0  /* dtype codes */
+#define SMIL_ROT_F64 1
+int smil_rot6d_to_matrix(const void *d6, void *R, int64_t n, int32_t dtype, void *stream);
+int smil_rot6d_to_matrix_backward(const void *d6, const void *dR, void *dd6, int64_t n, int32_t dtype, void *stream);
+int smil_axis_angle_to_matrix(const void *aa, void *R, int64_t n, int32_t dtype, void *stream);
+int smil_axis_angle_to_matrix_backward(const void *aa, const void *dR, void *daa, int64_t n, int32_t dtype, void *stream);
+int smil_matrix_to_axis_angle(const void *R, void *aa, int64_t n, int32_t dtype, void *stream);
+int smil_matrix_to_axis_angle_backward(const void *R, const void *daa, void *dR, int64_t n, int32_t dtype, void *stream);
+/* 6-D -> matrix -> axis-angle in one kernel, no matrix in memory.  Its backward is smil_matrix_to_axis_angle_backward at the matrix of
+ * d6 followed by smil_rot6d_to_matrix_backward. */
+int smil_rot6d_to_axis_angle(const void *d6, void *aa, int64_t n, int32_t dtype, void *stream);
+/* dist (n).  The backward writes dp6 and / or dt6 (n,6); either may be NULL. */
+int smil_rot6d_distance(const void *p6, const void *t6, void *dist, int64_t n, int32_t dtype, void *stream);
+int smil_rot6d_distance_backward(const void *p6, const void *t6, const void *ddist, void *dp6, void *dt6, int64_t n, int32_t dtype,
+                                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif

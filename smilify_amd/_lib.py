@@ -31,6 +31,9 @@ EXPORTS = [
     "smil_refine_workspace_bytes", "smil_refine_evaluate", "smil_refine_cameras",
     "smil_refine_points_evaluate", "smil_refine_points",
     "smil_image_bounds", "smil_warp_images",
+    "smil_rot6d_to_matrix", "smil_rot6d_to_matrix_backward", "smil_axis_angle_to_matrix", "smil_axis_angle_to_matrix_backward",
+    "smil_matrix_to_axis_angle", "smil_matrix_to_axis_angle_backward", "smil_rot6d_to_axis_angle",
+    "smil_rot6d_distance", "smil_rot6d_distance_backward",
 ]
 
 N_OBJS = 10
@@ -122,6 +125,7 @@ REFINE_CONVERGED, REFINE_STEP_LIMIT, REFINE_SKIPPED, REFINE_NONFINITE = 0, 1, 2,
 REFINE_POINTS_FEW_VIEWS = 2  # SMIL_REFINE_POINTS_FEW_VIEWS
 WARP_EXACT, WARP_RESIZE_LINEAR, WARP_RESIZE_NEAREST = 0, 1, 2  # SMIL_WARP_* coordinate modes
 WARP_NEAREST, WARP_BILINEAR = 0, 1  # SMIL_WARP_* interpolation
+ROT_F32, ROT_F64 = 0, 1  # SMIL_ROT_* dtype codes
 
 _lib = None
 
@@ -229,6 +233,12 @@ def load():
     lib.smil_refine_points.argtypes = [c_void_p] * 4 + [c_int64, c_int32, c_int32, c_double, c_int32] + [c_void_p] * 8
     lib.smil_image_bounds.argtypes = [c_void_p, c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p]
     lib.smil_warp_images.argtypes = [POINTER(Warp), c_void_p]
+    for name in ("smil_rot6d_to_matrix", "smil_axis_angle_to_matrix", "smil_matrix_to_axis_angle", "smil_rot6d_to_axis_angle"):
+        getattr(lib, name).argtypes = [c_void_p, c_void_p, c_int64, c_int32, c_void_p]
+    for name in ("smil_rot6d_to_matrix_backward", "smil_axis_angle_to_matrix_backward", "smil_matrix_to_axis_angle_backward",
+                 "smil_rot6d_distance"):
+        getattr(lib, name).argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]
+    lib.smil_rot6d_distance_backward.argtypes = [c_void_p] * 5 + [c_int64, c_int32, c_void_p]
     lib.smil_profile_enable.argtypes = [c_int32]
     lib.smil_profile_read.argtypes = [POINTER(c_float), POINTER(c_int32)]
     for name in EXPORTS:

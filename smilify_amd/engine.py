@@ -1321,3 +1321,42 @@ def warp_images(src: torch.Tensor, size, affine: torch.Tensor, *, coord_mode: st
     w.border, w.n_border, w.scale = border.data_ptr(), int(border.shape[0]), float(scale)
     _lib.check(_lib.load().smil_warp_images(ctypes.byref(w), _stream()), "smil_warp_images")
     return out
+
+
+# ---- rotation conversions (csrc/rotations.hip) ----
+ROT_DTYPES = {torch.float32: _lib.ROT_F32, torch.float64: _lib.ROT_F64}
+
+
+def rot_call(name: str, n: int, dtype: torch.dtype, *tensors: Optional[torch.Tensor]) -> None:
+    """One ``smil_*`` rotation entry point over ``n`` rotations: the tensors in the order of its pointer arguments (None: NULL)."""
+    _lib.check(getattr(_lib.load(), name)(*(_ptr(t) for t in tensors), int(n), ROT_DTYPES[dtype], _stream()), name)
+
+
+def rot_forward(name: str, x: torch.Tensor, width: int) -> torch.Tensor:
+    """``x`` (n,k) contiguous float32 / float64 on the GPU -> (n,width) through the forward entry point ``name``."""
+    out = torch.empty(x.shape[0], width, dtype=x.dtype, device=x.device)
+    rot_call(name, x.shape[0], x.dtype, x, out)
+    return out
+
+
+def rot_backward(name: str, x: torch.Tensor, grad: torch.Tensor) -> torch.Tensor:
+    """The gradient on ``x`` (n,k) from the upstream ``grad`` (n,width) through the backward entry point ``name``."""
+    dx = torch.empty_like(x)
+    rot_call(name, x.shape[0], x.dtype, x, grad, dx)
+    return dx
+
+
+def rot6d_distance(p6: torch.Tensor, t6: torch.Tensor) -> torch.Tensor:
+    """(n,6), (n,6) -> (n,) Frobenius distances of the two rotations' matrices."""
+    dist = torch.empty(p6.shape[0], dtype=p6.dtype, device=p6.device)
+    rot_call("smil_rot6d_distance", p6.shape[0], p6.dtype, p6, t6, dist)
+    return dist
+
+
+def rot6d_distance_backward(p6: torch.Tensor, t6: torch.Tensor, ddist: torch.Tensor, need_p: bool = True, need_t: bool = True):
+    """``(dp6, dt6)``, each (n,6) or None where it is not needed."""
+    dp = torch.empty_like(p6) if need_p else None
+    dt = torch.empty_like(t6) if need_t else None
+    if need_p or need_t:
+        rot_call("smil_rot6d_distance_backward", p6.shape[0], p6.dtype, p6, t6, ddist, dp, dt)
+    return dp, dt
