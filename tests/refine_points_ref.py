@@ -51,8 +51,9 @@ def evaluate(P, obs, mask, X, f_scale=5.0):
     return cost, g, H + np.triu(H, 1).T
 
 
-def evaluate_mp(P, obs, mask, X, f_scale=5.0, digits=40):
-    """The same accumulation in `digits`-digit arithmetic, rounded to float64."""
+def evaluate_mp(P, obs, mask, X, f_scale=5.0, digits=40, rounded=True):
+    """The same accumulation in `digits`-digit arithmetic, rounded to float64.  rounded=False: the unrounded mpf values, cost, g as a
+    list and H as a list of rows (for lm_ref.lm_exact)."""
     import mpmath as mp
 
     with mp.workprec(int(digits * 3.33) + 8):
@@ -73,6 +74,8 @@ def evaluate_mp(P, obs, mask, X, f_scale=5.0, digits=40):
                     g[i] += J[i] * w * f
                     for j in range(3):
                         H[i][j] += w * J[i] * J[j]
+        if not rounded:
+            return fs * fs * cost / 2, g, H
         return float(fs * fs * cost / 2), np.array([float(x) for x in g]), np.array([[float(x) for x in row] for row in H])
 
 
@@ -85,9 +88,15 @@ def lm(P, obs, mask, xyz0, f_scale=5.0, max_steps=50):
     n_trials, cost0, cost, and margin: the smallest |cost_new - cost_cur| / cost_cur over its accept / reject decisions (how far the
     closest decision is from going the other way)."""
     if len(views_of(mask, len(P))) < 2:
-        return dict(xyz=np.asarray(xyz0, np.float64).copy(), status=FEW_VIEWS, n_accepted=0, n_trials=0, cost0=np.nan, cost=np.nan, margin=np.inf)
+        return dict(xyz=np.asarray(xyz0, np.float64).copy(), status=FEW_VIEWS, n_accepted=0, n_trials=0, cost0=np.nan, cost=np.nan, margin=np.inf, trace=[])
     out = lm_ref.lm(lambda x: evaluate(P, obs, mask, x, f_scale), xyz0, 3, max_steps)
-    return dict(xyz=out["x"], **{k: out[k] for k in ("status", "n_accepted", "n_trials", "cost0", "cost", "margin")})
+    return dict(xyz=out["x"], **{k: out[k] for k in ("x", "g", "status", "n_accepted", "n_trials", "cost0", "cost", "margin", "trace")})
+
+
+def lm_exact(P, obs, mask, xyz0, f_scale=5.0, max_steps=50):
+    """The exact-step iteration (lm_ref.lm_exact) of a problem with at least two views: the dict of lm()."""
+    out = lm_ref.lm_exact(lambda x: evaluate_mp(P, obs, mask, x, f_scale, lm_ref.DIGITS, rounded=False), lm_ref.solve_mp, xyz0, 3, max_steps)
+    return dict(xyz=out["x"], **{k: out[k] for k in ("x", "g", "status", "n_accepted", "n_trials", "cost0", "cost", "margin", "trace")})
 
 
 def distance(a, b):

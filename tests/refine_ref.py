@@ -94,9 +94,10 @@ def evaluate(params10, p3, p2, n_params=10, f_scale=5.0):
     return cost, g, H
 
 
-def evaluate_mp(params10, p3, p2, f_scale=5.0, digits=40):
+def evaluate_mp(params10, p3, p2, f_scale=5.0, digits=40, rounded=True):
     """The same accumulation (10 parameters) in `digits`-digit arithmetic, with the closed-form Rodrigues coefficients (their limits
-    at th = 0), rounded to float64.  The 6-parameter values are its leading blocks."""
+    at th = 0), rounded to float64.  The 6-parameter values are its leading blocks.  rounded=False: the unrounded mpf values, cost, g as
+    a list and the symmetric H as a list of rows (for lm_ref.lm_exact)."""
     import mpmath as mp
 
     with mp.workprec(int(digits * 3.33) + 8):
@@ -138,6 +139,8 @@ def evaluate_mp(params10, p3, p2, f_scale=5.0, digits=40):
                         if j >= i:
                             H[i][j] += wi * J[j]
         cost = fs * fs * cost / 2
+        if not rounded:
+            return cost, g, [[H[min(i, j)][max(i, j)] for j in range(10)] for i in range(10)]
         Hf = np.array([[float(H[min(i, j)][max(i, j)]) for j in range(10)] for i in range(10)])
         return float(cost), np.array([float(v) for v in g]), Hf
 
@@ -153,9 +156,16 @@ def lm(params10, p3, p2, n_params=10, f_scale=5.0, max_steps=100):
     """The kernel's Levenberg-Marquardt (lm_ref.lm; include/smilfit.h, smil_refine_cameras).  Returns a dict: params (10), status,
     n_accepted, n_trials, cost0, cost, g (10), lam, margin."""
     if len(p3) < MIN_POINTS:
-        return dict(params=np.asarray(params10, np.float64).copy(), status=SKIPPED, n_accepted=0, n_trials=0, cost0=np.nan, cost=np.nan, g=np.zeros(10), lam=1e-3, margin=np.inf)
+        return dict(params=np.asarray(params10, np.float64).copy(), status=SKIPPED, n_accepted=0, n_trials=0, cost0=np.nan, cost=np.nan, g=np.zeros(10), lam=1e-3, margin=np.inf, trace=[])
     out = lm_ref.lm(lambda x: evaluate(x, p3, p2, n_params, f_scale), params10, n_params, max_steps)
-    out["params"] = out.pop("x")
+    out["params"] = out["x"]
+    return out
+
+
+def lm_exact(params10, p3, p2, n_params=10, f_scale=5.0, max_steps=100):
+    """The exact-step iteration (lm_ref.lm_exact) of a camera with at least MIN_POINTS correspondences: the dict of lm()."""
+    out = lm_ref.lm_exact(lambda x: evaluate_mp(x, p3, p2, f_scale, lm_ref.DIGITS, rounded=False), lm_ref.solve_mp, params10, n_params, max_steps)
+    out["params"] = out["x"]
     return out
 
 
