@@ -780,6 +780,74 @@ int smil_rot6d_distance(const void *p6, const void *t6, void *dist, int64_t n, i
 int smil_rot6d_distance_backward(const void *p6, const void *t6, const void *ddist, void *dp6, void *dt6, int64_t n, int32_t dtype,
                                  void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Keypoint and triangulation losses of a multi-view regressor (smilify_amd/csrc/keypoint_losses.hip; smilify_amd/keypoint_losses.py).
+ * Replaces the reference's smal_fitter/neuralSMIL/multiview_smil_regressor.py:1623-1838 (projection to views, damped DLT), :2250-2388
+ * and :1050-1110 (the 2-D losses and the consistency term) and the per-sample loops of smil_image_regressor.py:3032-3115, :3334-3407.
+ * Arrays are contiguous and hold the storage type `dtype` (SMIL_ROT_F32 / SMIL_ROT_F64); visibility and masks are bytes (non-zero:
+ * true), joint weights and the work arrays are float64; all arithmetic is float64.  Empty sizes succeed; a negative size, a NULL
+ * required pointer, an unknown dtype, flag or reduction is SMIL_E_INVALID.  Asynchronous on `stream`, no host synchronisation, no
+ * atomics: every sum has a fixed order (lane-strided partials over the joints, a fixed butterfly over the wave, one workgroup over
+ * the per-sample partials), so the same inputs give the same bits on every call.  A backward call takes the forward's INPUTS, what
+ * the forward left in `factor`, and the upstream gradient as a DEVICE scalar or array; it recomputes the rest.
+ *
+ * (a) Squared error over pred, target (N,J,D), D = 2 or 3, eps = 1e-8.  Joint (n,j) is valid when mask[n] != 0 (mask (N) or NULL),
+ *     vis[n,j] != 0 (vis (N,J) or NULL: visibility, or any explicit mask) and, by flag: SMIL_KP_TARGET_IN_UNIT every target
+ *     coordinate lies in [0,1]; SMIL_KP_FINITE_NONZERO every prediction and target coordinate is finite and sum_d |t_d| > 0.
+ *     With SMIL_KP_PRED_NAN_TO_ZERO a non-finite prediction coordinate counts as 0 and receives no gradient.  With weights w (J) or
+ *     w = 1:  num_n = sum_j w_j valid_nj sum_d (p - t)^2,  count_n = sum_j w_j valid_nj.  Reductions:
+ *       SMIL_KP_POOLED         sum_n num_n / (D sum_n count_n + eps) + eps;  with SMIL_KP_NO_TRAILING_EPS the same without the last
+ *                              + eps, and exactly eps when no joint is valid
+ *       SMIL_KP_VALID_SAMPLES  the mean of num_n / (D count_n + eps) over the samples with mask[n] != 0 that hold a valid joint, + eps
+ *       SMIL_KP_SAMPLES        the same mean over all samples with mask[n] != 0, + eps
+ *     (a mean over no sample is 0: with nothing valid every reduction is exactly eps.)  `partials` (N,4) is scratch, `factor` (N)
+ *     receives d loss / d num_n, `loss` one value.  Backward: dpred = upstream factor_n 2 w_j valid_nj (p - t).
+ * (b) Projection of joints (B,J,3) through cameras R (B,V,3,3), T (B,V,3), fov (B,V) in degrees, aspect (B,V) or NULL (1), image size
+ *     S, to out (B,V,J,2): v = X R + T (row vectors); k11 = 1 / tan(fov pi / 360), k00 = k11 / aspect; x_ndc = k00 vx / vz,
+ *     y_ndc = k11 vy / vz; (y, x) = (S/2 - S/2 y_ndc, S/2 - S/2 x_ndc) / (S + 1e-8), clamped to [0,1] - the camera of
+ *     smilify_amd/csrc/camera.h in float64.  Backward: djoints, dR (all nine entries), dT, dfov, any of them NULL; a clamped
+ *     coordinate passes its gradient where the unclamped value lies in [0,1], bounds included; none on aspect.
+ * (c) (b) followed by (a) with D = 2, flags SMIL_KP_TARGET_IN_UNIT | SMIL_KP_PRED_NAN_TO_ZERO, reduction SMIL_KP_POOLED over the
+ *     N = B V (sample, view) pairs with mask = view_mask (B,V); the projected array is never written.
+ * (d) Damped DLT.  kp (B,V,J,2) normalised (y, x); for every (v,j) with vis[b,v,j] != 0 and view_mask[b,v] != 0 (either NULL: all):
+ *     u = 1 - (x S) / (S / 2), v likewise from y; a1 = u [R[:,2]; T2] - k00 [R[:,0]; T0], a2 = v [R[:,2]; T2] - k11 [R[:,1]; T1];
+ *     M = sum a_xyz a_xyz^T + damping I, c = -sum a_xyz a_w, points = M^-1 c (Cholesky).  valid (B,J): seen by >= 2 views; sane
+ *     (B,J) or NULL: valid and |point| < max_norm.  Backward: lambda = M^-1 dpoints, dM = -lambda p^T, dc = lambda, through the rows
+ *     to dR, dT, dfov (any NULL); lam_p (B,J,6) float64 is scratch.  The keypoints carry no gradient.  damping must be positive and
+ *     finite (SMIL_E_INVALID otherwise): a joint seen by fewer than two views has a singular sum, and the damping is what keeps its
+ *     factorisation, its point and its lambda finite. */
+#define SMIL_KP_TARGET_IN_UNIT 1   /* flags of (a) */
+#define SMIL_KP_PRED_NAN_TO_ZERO 2
+#define SMIL_KP_FINITE_NONZERO 4
+#define SMIL_KP_NO_TRAILING_EPS 8
+#define SMIL_KP_POOLED 0           /* reductions of (a) */
+#define SMIL_KP_VALID_SAMPLES 1
+#define SMIL_KP_SAMPLES 2
+int smil_kp_se_forward(const void *pred, const void *target, const uint8_t *vis, const uint8_t *mask, const double *weights, int64_t N,
+                       int32_t J, int32_t D, int32_t flags, int32_t rule, int32_t dtype, double *partials, double *factor, void *loss,
+                       void *stream);
+int smil_kp_se_backward(const void *pred, const void *target, const uint8_t *vis, const uint8_t *mask, const double *weights,
+                        const double *factor, const void *upstream, void *dpred, int64_t N, int32_t J, int32_t D, int32_t flags,
+                        int32_t dtype, void *stream);
+int smil_kp_project(const void *joints, const void *R, const void *T, const void *fov, const void *aspect, int64_t B, int32_t V, int32_t J,
+                    double S, int32_t dtype, void *out, void *stream);
+int smil_kp_project_backward(const void *joints, const void *R, const void *T, const void *fov, const void *aspect, const void *dout,
+                             int64_t B, int32_t V, int32_t J, double S, int32_t dtype, void *djoints, void *dR, void *dT, void *dfov,
+                             void *stream);
+int smil_kp_project_loss(const void *joints, const void *R, const void *T, const void *fov, const void *aspect, const void *target,
+                         const uint8_t *vis, const uint8_t *view_mask, const double *weights, int64_t B, int32_t V, int32_t J, double S,
+                         int32_t dtype, double *partials, double *factor, void *loss, void *stream);
+int smil_kp_project_loss_backward(const void *joints, const void *R, const void *T, const void *fov, const void *aspect, const void *target,
+                                  const uint8_t *vis, const uint8_t *view_mask, const double *weights, const double *factor,
+                                  const void *upstream, int64_t B, int32_t V, int32_t J, double S, int32_t dtype, void *djoints, void *dR,
+                                  void *dT, void *dfov, void *stream);
+int smil_kp_triangulate(const void *kp, const uint8_t *vis, const uint8_t *view_mask, const void *R, const void *T, const void *fov,
+                        const void *aspect, int64_t B, int32_t V, int32_t J, double S, double damping, double max_norm, int32_t dtype,
+                        void *points, uint8_t *valid, uint8_t *sane, void *stream);
+int smil_kp_triangulate_backward(const void *kp, const uint8_t *vis, const uint8_t *view_mask, const void *R, const void *T, const void *fov,
+                                 const void *aspect, const void *dpoints, int64_t B, int32_t V, int32_t J, double S, double damping,
+                                 int32_t dtype, double *lam_p, void *dR, void *dT, void *dfov, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

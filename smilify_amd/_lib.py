@@ -34,6 +34,8 @@ EXPORTS = [
     "smil_rot6d_to_matrix", "smil_rot6d_to_matrix_backward", "smil_axis_angle_to_matrix", "smil_axis_angle_to_matrix_backward",
     "smil_matrix_to_axis_angle", "smil_matrix_to_axis_angle_backward", "smil_rot6d_to_axis_angle",
     "smil_rot6d_distance", "smil_rot6d_distance_backward",
+    "smil_kp_se_forward", "smil_kp_se_backward", "smil_kp_project", "smil_kp_project_backward", "smil_kp_project_loss",
+    "smil_kp_project_loss_backward", "smil_kp_triangulate", "smil_kp_triangulate_backward",
 ]
 
 N_OBJS = 10
@@ -126,6 +128,8 @@ REFINE_POINTS_FEW_VIEWS = 2  # SMIL_REFINE_POINTS_FEW_VIEWS
 WARP_EXACT, WARP_RESIZE_LINEAR, WARP_RESIZE_NEAREST = 0, 1, 2  # SMIL_WARP_* coordinate modes
 WARP_NEAREST, WARP_BILINEAR = 0, 1  # SMIL_WARP_* interpolation
 ROT_F32, ROT_F64 = 0, 1  # SMIL_ROT_* dtype codes
+KP_TARGET_IN_UNIT, KP_PRED_NAN_TO_ZERO, KP_FINITE_NONZERO, KP_NO_TRAILING_EPS = 1, 2, 4, 8  # SMIL_KP_* flags
+KP_POOLED, KP_VALID_SAMPLES, KP_SAMPLES = 0, 1, 2  # SMIL_KP_* reductions
 
 _lib = None
 
@@ -239,6 +243,14 @@ def load():
                  "smil_rot6d_distance"):
         getattr(lib, name).argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]
     lib.smil_rot6d_distance_backward.argtypes = [c_void_p] * 5 + [c_int64, c_int32, c_void_p]
+    lib.smil_kp_se_forward.argtypes = [c_void_p] * 5 + [c_int64] + [c_int32] * 5 + [c_void_p] * 4
+    lib.smil_kp_se_backward.argtypes = [c_void_p] * 8 + [c_int64] + [c_int32] * 4 + [c_void_p]
+    lib.smil_kp_project.argtypes = [c_void_p] * 5 + [c_int64, c_int32, c_int32, c_double, c_int32, c_void_p, c_void_p]
+    lib.smil_kp_project_backward.argtypes = [c_void_p] * 6 + [c_int64, c_int32, c_int32, c_double, c_int32] + [c_void_p] * 5
+    lib.smil_kp_project_loss.argtypes = [c_void_p] * 9 + [c_int64, c_int32, c_int32, c_double, c_int32] + [c_void_p] * 4
+    lib.smil_kp_project_loss_backward.argtypes = [c_void_p] * 11 + [c_int64, c_int32, c_int32, c_double, c_int32] + [c_void_p] * 5
+    lib.smil_kp_triangulate.argtypes = [c_void_p] * 7 + [c_int64, c_int32, c_int32, c_double, c_double, c_double, c_int32] + [c_void_p] * 4
+    lib.smil_kp_triangulate_backward.argtypes = [c_void_p] * 8 + [c_int64, c_int32, c_int32, c_double, c_double, c_int32] + [c_void_p] * 5
     lib.smil_profile_enable.argtypes = [c_int32]
     lib.smil_profile_read.argtypes = [POINTER(c_float), POINTER(c_int32)]
     for name in EXPORTS:

@@ -1360,3 +1360,111 @@ def rot6d_distance_backward(p6: torch.Tensor, t6: torch.Tensor, ddist: torch.Ten
     if need_p or need_t:
         rot_call("smil_rot6d_distance_backward", p6.shape[0], p6.dtype, p6, t6, ddist, dp, dt)
     return dp, dt
+
+
+# ---- keypoint and triangulation losses (csrc/keypoint_losses.hip) ----
+# Every tensor below is contiguous on one GPU: floats in one storage type of ROT_DTYPES, visibility and masks uint8 (or None), joint
+# weights float64 (or None).  Scalars (losses, their upstream gradients) are 0-dim device tensors: nothing here synchronises.
+KP_REDUCTIONS = {"pooled": _lib.KP_POOLED, "valid_samples": _lib.KP_VALID_SAMPLES, "samples": _lib.KP_SAMPLES}
+KP_FLAGS_2D = _lib.KP_TARGET_IN_UNIT | _lib.KP_PRED_NAN_TO_ZERO
+KP_FLAGS_3D = _lib.KP_FINITE_NONZERO
+
+
+def _kp_f64(*shape, device) -> torch.Tensor:
+    return torch.empty(*shape, dtype=torch.float64, device=device)
+
+
+def kp_se_forward(pred: torch.Tensor, target: torch.Tensor, vis, mask, weights, flags: int, rule: int):
+    """``pred``, ``target`` (N,J,D) -> ``(loss (), factor (N) float64)``: smil_kp_se_forward."""
+    N, J, D = pred.shape
+    loss = torch.empty((), dtype=pred.dtype, device=pred.device)
+    factor = _kp_f64(N, device=pred.device)
+    _lib.check(_lib.load().smil_kp_se_forward(_ptr(pred), _ptr(target), _ptr(vis), _ptr(mask), _ptr(weights), N, J, D, flags, rule,
+                                              ROT_DTYPES[pred.dtype], _ptr(_kp_f64(N, 4, device=pred.device)), _ptr(factor), _ptr(loss),
+                                              _stream()), "smil_kp_se_forward")
+    return loss, factor
+
+
+def kp_se_backward(pred, target, vis, mask, weights, factor, upstream: torch.Tensor, flags: int) -> torch.Tensor:
+    """The gradient on ``pred`` from the 0-dim device tensor ``upstream``."""
+    N, J, D = pred.shape
+    dpred = torch.empty_like(pred)
+    _lib.check(_lib.load().smil_kp_se_backward(_ptr(pred), _ptr(target), _ptr(vis), _ptr(mask), _ptr(weights), _ptr(factor), _ptr(upstream),
+                                               _ptr(dpred), N, J, D, flags, ROT_DTYPES[pred.dtype], _stream()), "smil_kp_se_backward")
+    return dpred
+
+
+def _kp_sizes(R: torch.Tensor, J: int):
+    return int(R.shape[0]), int(R.shape[1]), int(J)
+
+
+def kp_project(joints, R, T, fov, aspect, S: float) -> torch.Tensor:
+    """joints (B,J,3), R (B,V,3,3), T (B,V,3), fov (B,V), aspect (B,V) or None -> (B,V,J,2) normalised, clamped (y, x)."""
+    B, V, J = _kp_sizes(R, joints.shape[1])
+    out = torch.empty(B, V, J, 2, dtype=joints.dtype, device=joints.device)
+    _lib.check(_lib.load().smil_kp_project(_ptr(joints), _ptr(R), _ptr(T), _ptr(fov), _ptr(aspect), B, V, J, float(S),
+                                           ROT_DTYPES[joints.dtype], _ptr(out), _stream()), "smil_kp_project")
+    return out
+
+
+def _kp_camera_grads(joints, R, T, fov, need):
+    """Output buffers (d joints, d R, d T, d fov), None where ``need`` says nobody wants it."""
+    return tuple(torch.empty_like(t) if n else None for t, n in zip((joints, R, T, fov), need))
+
+
+def kp_project_backward(joints, R, T, fov, aspect, dout, S: float, need=(True, True, True, True)):
+    B, V, J = _kp_sizes(R, joints.shape[1])
+    grads = _kp_camera_grads(joints, R, T, fov, need)
+    if any(need):
+        _lib.check(_lib.load().smil_kp_project_backward(_ptr(joints), _ptr(R), _ptr(T), _ptr(fov), _ptr(aspect), _ptr(dout), B, V, J, float(S),
+                                                        ROT_DTYPES[joints.dtype], *(_ptr(g) for g in grads), _stream()),
+                   "smil_kp_project_backward")
+    return grads
+
+
+def kp_project_loss(joints, R, T, fov, aspect, target, vis, view_mask, weights, S: float):
+    """The pooled 2-D loss of the projections against target (B,V,J,2) -> ``(loss (), factor (B V) float64)``."""
+    B, V, J = _kp_sizes(R, joints.shape[1])
+    loss = torch.empty((), dtype=joints.dtype, device=joints.device)
+    factor = _kp_f64(B * V, device=joints.device)
+    _lib.check(_lib.load().smil_kp_project_loss(_ptr(joints), _ptr(R), _ptr(T), _ptr(fov), _ptr(aspect), _ptr(target), _ptr(vis),
+                                                _ptr(view_mask), _ptr(weights), B, V, J, float(S), ROT_DTYPES[joints.dtype],
+                                                _ptr(_kp_f64(B * V, 4, device=joints.device)), _ptr(factor), _ptr(loss), _stream()),
+               "smil_kp_project_loss")
+    return loss, factor
+
+
+def kp_project_loss_backward(joints, R, T, fov, aspect, target, vis, view_mask, weights, factor, upstream, S: float,
+                             need=(True, True, True, True)):
+    B, V, J = _kp_sizes(R, joints.shape[1])
+    grads = _kp_camera_grads(joints, R, T, fov, need)
+    if any(need):
+        _lib.check(_lib.load().smil_kp_project_loss_backward(_ptr(joints), _ptr(R), _ptr(T), _ptr(fov), _ptr(aspect), _ptr(target), _ptr(vis),
+                                                             _ptr(view_mask), _ptr(weights), _ptr(factor), _ptr(upstream), B, V, J, float(S),
+                                                             ROT_DTYPES[joints.dtype], *(_ptr(g) for g in grads), _stream()),
+                   "smil_kp_project_loss_backward")
+    return grads
+
+
+def kp_triangulate(kp, vis, view_mask, R, T, fov, aspect, S: float, damping: float, max_norm: Optional[float] = None):
+    """kp (B,V,J,2) -> ``(points (B,J,3), valid (B,J) uint8, sane (B,J) uint8 or None)``; ``sane`` = valid and |point| < max_norm."""
+    B, V, J = _kp_sizes(R, kp.shape[2])
+    points = torch.empty(B, J, 3, dtype=kp.dtype, device=kp.device)
+    valid = torch.empty(B, J, dtype=torch.uint8, device=kp.device)
+    sane = torch.empty_like(valid) if max_norm is not None else None
+    _lib.check(_lib.load().smil_kp_triangulate(_ptr(kp), _ptr(vis), _ptr(view_mask), _ptr(R), _ptr(T), _ptr(fov), _ptr(aspect), B, V, J, float(S),
+                                               float(damping), float(max_norm or 0.0), ROT_DTYPES[kp.dtype], _ptr(points), _ptr(valid),
+                                               _ptr(sane), _stream()), "smil_kp_triangulate")
+    return points, valid, sane
+
+
+def kp_triangulate_backward(kp, vis, view_mask, R, T, fov, aspect, dpoints, S: float, damping: float, need=(True, True, True)):
+    """``(d R, d T, d fov)`` from the gradient on the points (B,J,3)."""
+    B, V, J = _kp_sizes(R, kp.shape[2])
+    grads = tuple(torch.empty_like(t) if n else None for t, n in zip((R, T, fov), need))
+    if any(need):
+        _lib.check(_lib.load().smil_kp_triangulate_backward(_ptr(kp), _ptr(vis), _ptr(view_mask), _ptr(R), _ptr(T), _ptr(fov), _ptr(aspect),
+                                                            _ptr(dpoints), B, V, J, float(S), float(damping), ROT_DTYPES[kp.dtype],
+                                                            _ptr(_kp_f64(B, J, 6, device=kp.device)), *(_ptr(g) for g in grads), _stream()),
+                   "smil_kp_triangulate_backward")
+    return grads
