@@ -848,6 +848,64 @@ int smil_kp_triangulate_backward(const void *kp, const uint8_t *vis, const uint8
                                  const void *aspect, const void *dpoints, int64_t B, int32_t V, int32_t J, double S, double damping,
                                  int32_t dtype, double *lam_p, void *dR, void *dT, void *dfov, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Rigid and similarity alignment of 3-D keypoint sets (smilify_amd/csrc/align.hip, align.h; smilify_amd/align.py): the rotation R,
+ * translation t and scale s that carry src (B,J,3) onto dst (B,J,3), dst_i ~ s R src_i + t, in the weighted least-squares sense, by
+ * Horn's quaternion method.  An extension: the reference has no alignment; only the masking rule of its MPJPE is mirrored
+ * (smal_fitter/neuralSMIL/benchmark_model.py:287-297).  Arrays are contiguous and hold the storage type `dtype` (SMIL_ROT_F32 /
+ * SMIL_ROT_F64); weights, the saved records and the final weights are float64, masks are bytes (non-zero: true), the status is int32;
+ * all arithmetic is float64 and every output is rounded once.  B == 0 succeeds without a launch; a negative size, a NULL required
+ * pointer, an unknown dtype or mode, a min_gap that is negative or not finite, or (robust_iters > 0) a robust_scale that is not
+ * positive and finite is SMIL_E_INVALID.  Asynchronous on `stream`, no host synchronisation, no atomics: one wave holds one problem
+ * and sums its joints in a fixed order, so the same inputs give the same bits on every call.  No cap on B or J.
+ *
+ * Weights.  w_i = weights[i] (weights (J) with weight_rows == 0, (B,J) with 1, NULL: 1) where mask[b,i] != 0 (mask (B,J) or NULL), and
+ *     0 where a coordinate of either point is not finite or the weight is not a positive finite number.  A joint of weight 0 is not
+ *     read into any sum.
+ * Moments, in two passes.  W = sum w, mx = sum w src / W, my = sum w dst / W; on x = src - mx, y = dst - my:
+ *     M[a][b] = sum w x_a y_b, vx = sum w |x|^2.
+ * Solve.  N (4 x 4, symmetric) from S = M: row 0 (Sxx+Syy+Szz, Syz-Szy, Szx-Sxz, Sxy-Syx), row 1 from the diagonal (Sxx-Syy-Szz,
+ *     Sxy+Syx, Szx+Sxz), row 2 (-Sxx+Syy-Szz, Syz+Szy), row 3 (-Sxx-Syy+Szz).  Cyclic Jacobi, at most 12 sweeps, ended when the
+ *     off-diagonal sum of squares is <= (2^-52 |N|_F)^2, gives lam_1 >= ... >= lam_4 and v_k; q = v_1 = (a,b,c,d) and
+ *     R = [[aa+bb-cc-dd, 2(bc-ad), 2(bd+ac)], [2(bc+ad), aa-bb+cc-dd, 2(cd-ab)], [2(bd-ac), 2(cd+ab), aa-bb-cc+dd]]: even in q and
+ *     always a proper rotation, a mirrored dst included.  s = sum_ab R[a][b] M[b][a] / vx with with_scale, else 1;  t = my - s R mx;
+ *     gap = (lam_1 - lam_2) / max(lam_1, -lam_4);  rms = sqrt(sum w |s R x - y|^2 / W), summed over the joints.
+ * Status.  SMIL_ALIGN_EMPTY where W == 0 (J == 0 included): R = I, s = 1, t = 0, gap = rms = 0.  SMIL_ALIGN_DEGENERATE where W > 0 and
+ *     (vx == 0, or max |lam| == 0, or gap <= min_gap) - one point, two points, collinear or coincident points do not determine a
+ *     rotation: R = I, s = 1, t = my - mx, gap as computed (0 for max |lam| == 0), rms of that transform.  Else SMIL_ALIGN_OK.  The
+ *     gradients of a problem that is not SMIL_ALIGN_OK are exactly 0.
+ * Robust variant.  robust_iters > 0 re-solves that many times, each with w_i = w0_i / sqrt(1 + r_i^2 / robust_scale^2),
+ *     r_i = |s R src_i + t - dst_i| under the transform of the solve before (soft-L1, the cost of the refinement kernels).  The
+ *     outputs are those of the last solve; w_final (B,J) or NULL receives its weights.
+ * Backward, of an SMIL_ALIGN_OK problem, from gR (B,9), gt (B,3), gs (B) (any NULL: zero; gs is ignored without with_scale), with the
+ *     weights of the last solve as constants; gap and rms carry no gradient.
+ *       g_my = gt;  gs += -gt . (R mx);  gR += -s gt mx^T;  g_mx = -s R^T gt
+ *       with_scale:  gR += gs M^T / vx;  gM = gs R^T / vx;  g_vx = -gs s / vx
+ *       gq = 2 N(gR^T) q   (sum gR R(q) is the quadratic form q^T N(gR^T) q)
+ *       u = sum_{k=2..4} v_k (v_k . gq) / (lam_1 - lam_k);  G = u q^T;  gM[a][b] += sum_ij G[i][j] dN[i][j] / dM[a][b]
+ *       d src_i = w_i (gM y_i + 2 g_vx x_i) + (w_i / W) g_mx;   d dst_i = w_i gM^T x_i + (w_i / W) g_my
+ *     (the centring terms cancel: sum w x = sum w y = 0).  `saved` (B, SMIL_ALIGN_SAVED) float64 is written by the forward (NULL: not
+ *     kept) and read, with `status` and `w_final`, by the backward; dsrc and ddst may each be NULL.
+ * Errors.  smil_align_errors: valid[b,i] = mask != 0, both points finite and, with `sentinel`, |target_i| > 1e-6; the alignment
+ *     `mode` (SMIL_ALIGN_NONE: the identity) carries pred onto target with `valid` as weights; dist[b,i] = scale |s R pred_i + t -
+ *     target_i|, 0 where the joint is not valid.  A sample that is not SMIL_ALIGN_OK uses the transform stated above and reports its
+ *     status; with SMIL_ALIGN_NONE the status is SMIL_ALIGN_OK where a joint is valid, else SMIL_ALIGN_EMPTY.  Forward only. */
+#define SMIL_ALIGN_OK 0          /* status */
+#define SMIL_ALIGN_DEGENERATE 1
+#define SMIL_ALIGN_EMPTY 2
+#define SMIL_ALIGN_NONE 0        /* modes of smil_align_errors */
+#define SMIL_ALIGN_RIGID 1
+#define SMIL_ALIGN_SIMILARITY 2
+#define SMIL_ALIGN_SAVED 40      /* float64 values the forward keeps per problem */
+int smil_align_forward(const void *src, const void *dst, const double *weights, int32_t weight_rows, const uint8_t *mask, int64_t B,
+                       int32_t J, int32_t with_scale, double min_gap, int32_t robust_iters, double robust_scale, int32_t dtype, void *R,
+                       void *t, void *s, int32_t *status, void *gap, void *rms, double *w_final, double *saved, void *stream);
+int smil_align_backward(const void *src, const void *dst, const double *w_final, const double *saved, const int32_t *status, const void *gR,
+                        const void *gt, const void *gs, int64_t B, int32_t J, int32_t with_scale, int32_t dtype, void *dsrc, void *ddst,
+                        void *stream);
+int smil_align_errors(const void *pred, const void *target, const uint8_t *mask, int64_t B, int32_t J, int32_t mode, int32_t sentinel,
+                      double scale, double min_gap, int32_t dtype, void *dist, uint8_t *valid, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

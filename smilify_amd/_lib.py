@@ -36,6 +36,7 @@ EXPORTS = [
     "smil_rot6d_distance", "smil_rot6d_distance_backward",
     "smil_kp_se_forward", "smil_kp_se_backward", "smil_kp_project", "smil_kp_project_backward", "smil_kp_project_loss",
     "smil_kp_project_loss_backward", "smil_kp_triangulate", "smil_kp_triangulate_backward",
+    "smil_align_forward", "smil_align_backward", "smil_align_errors",
 ]
 
 N_OBJS = 10
@@ -130,6 +131,9 @@ WARP_NEAREST, WARP_BILINEAR = 0, 1  # SMIL_WARP_* interpolation
 ROT_F32, ROT_F64 = 0, 1  # SMIL_ROT_* dtype codes
 KP_TARGET_IN_UNIT, KP_PRED_NAN_TO_ZERO, KP_FINITE_NONZERO, KP_NO_TRAILING_EPS = 1, 2, 4, 8  # SMIL_KP_* flags
 KP_POOLED, KP_VALID_SAMPLES, KP_SAMPLES = 0, 1, 2  # SMIL_KP_* reductions
+ALIGN_OK, ALIGN_DEGENERATE, ALIGN_EMPTY = 0, 1, 2  # SMIL_ALIGN_* status
+ALIGN_NONE, ALIGN_RIGID, ALIGN_SIMILARITY = 0, 1, 2  # SMIL_ALIGN_* modes of smil_align_errors
+ALIGN_SAVED = 40  # SMIL_ALIGN_SAVED
 
 _lib = None
 
@@ -251,6 +255,10 @@ def load():
     lib.smil_kp_project_loss_backward.argtypes = [c_void_p] * 11 + [c_int64, c_int32, c_int32, c_double, c_int32] + [c_void_p] * 5
     lib.smil_kp_triangulate.argtypes = [c_void_p] * 7 + [c_int64, c_int32, c_int32, c_double, c_double, c_double, c_int32] + [c_void_p] * 4
     lib.smil_kp_triangulate_backward.argtypes = [c_void_p] * 8 + [c_int64, c_int32, c_int32, c_double, c_double, c_int32] + [c_void_p] * 5
+    lib.smil_align_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_int32, c_double, c_int32, c_double,
+                                       c_int32] + [c_void_p] * 9
+    lib.smil_align_backward.argtypes = [c_void_p] * 8 + [c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
+    lib.smil_align_errors.argtypes = [c_void_p] * 3 + [c_int64, c_int32, c_int32, c_int32, c_double, c_double, c_int32] + [c_void_p] * 4
     lib.smil_profile_enable.argtypes = [c_int32]
     lib.smil_profile_read.argtypes = [POINTER(c_float), POINTER(c_int32)]
     for name in EXPORTS:

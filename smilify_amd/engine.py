@@ -1468,3 +1468,49 @@ def kp_triangulate_backward(kp, vis, view_mask, R, T, fov, aspect, dpoints, S: f
                                                             _ptr(_kp_f64(B, J, 6, device=kp.device)), *(_ptr(g) for g in grads), _stream()),
                    "smil_kp_triangulate_backward")
     return grads
+
+
+# ---- rigid and similarity alignment of 3-D keypoint sets (csrc/align.hip) ----
+# Conventions as above: contiguous tensors on one GPU, floats in one storage type of ROT_DTYPES, masks uint8 (or None), weights
+# float64 (or None).  The status is an int32 device tensor: nothing here synchronises.
+ALIGN_MODES = {"none": _lib.ALIGN_NONE, "rigid": _lib.ALIGN_RIGID, "similarity": _lib.ALIGN_SIMILARITY}
+
+
+def align_forward(src: torch.Tensor, dst: torch.Tensor, weights, mask, with_scale: bool, min_gap: float, robust_iters: int,
+                  robust_scale: float):
+    """src, dst (B,J,3), weights (J) / (B,J) float64 or None, mask (B,J) uint8 or None -> ``(R (B,3,3), t (B,3), s (B), status (B) int32,
+    gap (B), rms (B), w_final (B,J) float64, saved (B, ALIGN_SAVED) float64)``: smil_align_forward."""
+    B, J = int(src.shape[0]), int(src.shape[1])
+    new = lambda *shape, dtype=src.dtype: torch.empty(*shape, dtype=dtype, device=src.device)  # noqa: E731
+    R, t, s, gap, rms = new(B, 3, 3), new(B, 3), new(B), new(B), new(B)
+    status = new(B, dtype=torch.int32)
+    w_final, saved = new(B, J, dtype=torch.float64), new(B, _lib.ALIGN_SAVED, dtype=torch.float64)
+    _lib.check(_lib.load().smil_align_forward(_ptr(src), _ptr(dst), _ptr(weights), int(weights is not None and weights.dim() == 2), _ptr(mask),
+                                              B, J, int(bool(with_scale)), float(min_gap), int(robust_iters), float(robust_scale),
+                                              ROT_DTYPES[src.dtype], _ptr(R), _ptr(t), _ptr(s), _ptr(status), _ptr(gap), _ptr(rms),
+                                              _ptr(w_final), _ptr(saved), _stream()), "smil_align_forward")
+    return R, t, s, status, gap, rms, w_final, saved
+
+
+def align_backward(src, dst, w_final, saved, status, gR, gt, gs, with_scale: bool, need=(True, True)):
+    """``(d src, d dst)``, each (B,J,3) or None where it is not needed, from the upstream gR, gt, gs (any None: zero)."""
+    B, J = int(src.shape[0]), int(src.shape[1])
+    dsrc = torch.empty_like(src) if need[0] else None
+    ddst = torch.empty_like(dst) if need[1] else None
+    if any(need):
+        _lib.check(_lib.load().smil_align_backward(_ptr(src), _ptr(dst), _ptr(w_final), _ptr(saved), _ptr(status), _ptr(gR), _ptr(gt), _ptr(gs),
+                                                   B, J, int(bool(with_scale)), ROT_DTYPES[src.dtype], _ptr(dsrc), _ptr(ddst), _stream()),
+                   "smil_align_backward")
+    return dsrc, ddst
+
+
+def align_errors(pred, target, mask, mode: int, sentinel: bool, scale: float, min_gap: float):
+    """pred, target (B,J,3) -> ``(dist (B,J), valid (B,J) uint8, status (B) int32)``: smil_align_errors."""
+    B, J = int(pred.shape[0]), int(pred.shape[1])
+    dist = torch.empty(B, J, dtype=pred.dtype, device=pred.device)
+    valid = torch.empty(B, J, dtype=torch.uint8, device=pred.device)
+    status = torch.empty(B, dtype=torch.int32, device=pred.device)
+    _lib.check(_lib.load().smil_align_errors(_ptr(pred), _ptr(target), _ptr(mask), B, J, int(mode), int(bool(sentinel)), float(scale),
+                                             float(min_gap), ROT_DTYPES[pred.dtype], _ptr(dist), _ptr(valid), _ptr(status), _stream()),
+               "smil_align_errors")
+    return dist, valid, status
