@@ -53,7 +53,9 @@ int smil_model_create(const SmilModelDesc *desc, SmilModel **out);
 void smil_model_destroy(SmilModel *m);
 int smil_model_dims(const SmilModel *m, int32_t dims[4]); /* V,F,J,nB */
 const char *smil_last_error(void);
-const char *smil_version(void);   /* "smilfit 0.5 (gfx950; 0.3 + SmilCameras.principal (0.4) + fragments, depth visibility)".  0.3 = the layout of rounds 5 - 6: SmilLbsGrads carries clip_depth in front of
+const char *smil_version(void);   /* "smilfit 0.6 (gfx950; 0.3 + SmilCameras.principal (0.4) + fragments, depth visibility (0.5) + mesh-free joints, kp3d fit)".  0.6 adds
+                                    * smil_joints_forward / smil_joints_backward / smil_kp3d_fit_eval / smil_adam_step_multi_bc64 with their own structs and changes no layout.
+                                    * 0.3 = the layout of rounds 5 - 6: SmilLbsGrads carries clip_depth in front of
                                     * beta_rows (which must hold 2 * B * nB_used + 16 floats), SmilRasterSettings ends in {tie_rule, clip_depth,
                                     * image0}, smil_window_terms exists.  0.4: SmilCameras ends in {principal, nPrincipal} (a zero-initialised
                                     * struct means what it meant in 0.3).  0.5 adds smil_render_fragments and
@@ -905,6 +907,105 @@ int smil_align_backward(const void *src, const void *dst, const double *w_final,
                         void *stream);
 int smil_align_errors(const void *pred, const void *target, const uint8_t *mask, int64_t B, int32_t J, int32_t mode, int32_t sentinel,
                       double scale, double min_gap, int32_t dtype, void *dist, uint8_t *valid, int32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Mesh-free joint kinematics (smilify_amd/csrc/joints.hip; tables: smilify_amd/joints.py).  The posed joints SMAL.__call__ returns
+ * (smal_torch.py:340-351) without forming a vertex, for models WITHOUT pose blend shapes: a static-joint model's joints are the
+ * translation column of the kinematic chain (J_transformed); a regressor model's are sum_k A_k m[j,k] over the (joint, bone) pairs
+ * with a non-zero weight product, with the moments m = M0 + sum_b beta_b MB_b and the rest joints J_rest = J0 + sum_b beta_b JB_b
+ * affine in the shape.  One wavefront per frame; all arithmetic is float64 on float32 parameters and every output is rounded once.
+ * The semantics of the chain are those of smil_lbs_forward (Rodrigues with |theta + 1e-8|, the root's rotation-only rule, the y flip of
+ * betas_trans, propagate_scaling, allow_limb_scaling, theta_mask).  No float atomics: two calls on the same inputs return the same
+ * bits, the sums over frames of the shared tables' gradients included.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {                /* DEVICE pointers; built on the host in float64 once per model */
+    int32_t J, nB, P;           /* joints, shape directions, (joint, bone) pairs (0 for a static-joint model) */
+    int32_t max_depth;          /* deepest level of the chain */
+    int32_t static_joints;
+    const int32_t *parents;     /* (J) parents[0] = -1, parents[i] < i */
+    const int32_t *depth;       /* (J) */
+    const int32_t *child_ptr;   /* (J+1) children of every joint, ascending ... */
+    const int32_t *child;       /* (J-1) ... gathered by the reverse walk in this order */
+    const double *J0;           /* (J,3) rest joints of the template (J_static for a static-joint model) */
+    const double *JB;           /* (nB,J,3) their shape directions */
+    const int32_t *pair_ptr;    /* (J+1) pairs by joint */
+    const int32_t *pair_bone;   /* (P) */
+    const double *M0;           /* (P,4) moment of the template; [3] = sum_v Jreg[j,v] w[v,k] */
+    const double *MB;           /* (P,nB,3) */
+    const int32_t *bpair_ptr;   /* (J+1) the same pairs by bone */
+    const int32_t *bpair_joint; /* (P) */
+    const int32_t *bpair_index; /* (P) the entry's pair in the by-joint order (index into M0 / MB) */
+    const double *rowsum;       /* (J) sum_v Jreg[j,v]: factor of a translation added before the regression */
+} SmilJointTables;
+
+typedef struct {                /* SmilLbsInputs without del_v, v_template and Rs_in; same conventions */
+    int32_t B;
+    int32_t shared_beta;
+    int32_t nB_used;            /* 0 .. nB */
+    const float *beta;          /* (B,nB_used) or (nB_used,); may be NULL when nB_used == 0 */
+    const float *theta;         /* (B,J,3) axis-angle */
+    const float *logscale;      /* (B,J,3) / (J,3) / NULL */
+    int32_t logscale_shared;
+    const float *btrans;        /* same conventions */
+    int32_t btrans_shared;
+    const float *trans;         /* (B,3) or NULL */
+    int32_t trans_after_joints; /* 1: trans is added to the joints (fitter convention, static-joint models included); 0: SMAL.__call__ -
+                                   trans is added to the vertices before the regression (times rowsum[j]) and a static-joint model's
+                                   joints carry no trans at all (smal_torch.py:343-346) */
+    int32_t propagate_scaling;
+    int32_t allow_limb_scaling;
+    const float *theta_mask;    /* (J,3) or NULL; d_theta is the gradient with respect to the MASKED pose */
+} SmilJointsInputs;
+
+/* joints (B,J,3) out; new_J (B,J,3) = SMAL.J_transformed, or NULL. */
+int smil_joints_forward(const SmilJointTables *t, const SmilJointsInputs *in, float *joints, float *new_J, void *stream);
+
+typedef struct {
+    const float *d_joints;  /* (B,J,3) upstream gradient */
+    float *d_beta;          /* (B,nB_used) or (nB_used,) when shared; NULL to skip (ignored when nB_used == 0) */
+    float *d_theta;         /* (B,J,3); NULL to skip */
+    float *d_trans;         /* (B,3); NULL to skip; zeros when `trans` has no effect on the joints */
+    float *d_logscale;      /* (B,J,3) or (J,3) when shared; NULL to skip; zeros without logscale / allow_limb_scaling */
+    float *d_btrans;        /* same; zeros without btrans */
+    void *workspace;        /* smil_joints_backward_workspace_bytes: required iff a SHARED table's gradient is asked for.  Its first 256
+                               bytes (the counter of finished blocks) must be zero before the first use; every call leaves them zero.
+                               One workspace serves the calls of one stream */
+} SmilJointsGrads;
+/* Every output is overwritten.  The forward is recomputed in LDS: nothing is saved between the calls.  Gradients of shared tables
+ * (shared beta, logscale, btrans) are sums over frames: every frame leaves its float64 row in the workspace and the rows are added in a
+ * fixed order (runs of 256 frames, then runs of 256 partial sums, ...), rounded to float32 once. */
+size_t smil_joints_backward_workspace_bytes(const SmilJointTables *t, const SmilJointsInputs *in, const SmilJointsGrads *g);
+int smil_joints_backward(const SmilJointTables *t, const SmilJointsInputs *in, const SmilJointsGrads *g, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * 3-D keypoint term on the mesh-free joints, fused: forward, term and backward of a frame in one launch (no (N,J,3) round trip).
+ * With windows as everywhere in fit.hip (b_w frames in window w, from cfg->window, frame0, N_total; cfg->N frames, cfg->J joints;
+ * cfg is not changed):
+ *   objs[9] += w_k3d sum_w 1/(3 Jc b_w) sum_{n in w} sum_c vis[n,c] wj[c] rho(|joints[n,canon[c]] - target[n,c]|^2)
+ * rho(s) = s when robust_scale == 0 (the 3-D twin of fitter.py:292-296), rho(s) = 2 sigma^2 (sqrt(1 + s / sigma^2) - 1) with
+ * robust_scale = sigma > 0 (the soft-L1 of the refinement kernels).  A target row that is exactly (0,0,0) or holds a non-finite entry is
+ * invisible; a frame with nothing visible contributes exactly 0 and gets exactly zero gradients.  The joints follow the fitter
+ * convention (in->trans_after_joints must be 1); in->B must equal cfg->N.
+ * canon (Jc) int32 joint ids (NULL: the first Jc joints), target (N,Jc,3) float32, visibility (N,Jc) uint8 or NULL, joint_weights (Jc)
+ * float64 or NULL.  The RAW gradients are written (overwritten): d_pose (N,J,3) with respect to the masked pose, d_trans (N,3),
+ * d_betas / d_logscale / d_btrans with the shapes of SmilJointsGrads (each may be NULL), so that smil_prior_losses(..., accumulate = 1)
+ * run after it finishes them.  joints_out (N,J,3) or NULL.  workspace: smil_kp3d_fit_eval_workspace_bytes (the counter and the
+ * per-block rows of the shared tables' gradients and of the term, zeroed like SmilJointsGrads.workspace; all sums over frames are
+ * taken in a fixed order). */
+size_t smil_kp3d_fit_eval_workspace_bytes(const SmilJointTables *t, const SmilJointsInputs *in, int32_t want_betas, int32_t want_logscale,
+                                          int32_t want_btrans);
+int smil_kp3d_fit_eval(const SmilFitConfig *cfg, double w_k3d, double robust_scale, const SmilJointTables *t, const SmilJointsInputs *in,
+                       int32_t Jc, const int32_t *canon, const float *target, const uint8_t *visibility, const double *joint_weights,
+                       float *objs, float *d_pose, float *d_trans, float *d_betas, float *d_logscale, float *d_btrans, float *joints_out,
+                       void *workspace, void *stream);
+
+/* smil_adam_step_multi with the bias corrections formed in double, as torch.optim.Adam forms them: 1 - beta1^step and
+ * sqrt(1 - beta2^step) are computed in double from the betas the caller wrote and rounded to float32 once, and the step size
+ * lr / (1 - beta1^step) likewise.  smil_adam_step_multi forms 1 - beta2^step in float32, which is up to 1e-5 off in its square root
+ * for small step counts: every update is then that fraction of lr off, whatever the parameter's magnitude (2e-7 after five steps at
+ * lr = 5e-3) - more than the rounding of parameters well below 1, which KeypointFitter3D's are.  Everything else is the float32
+ * arithmetic of smil_adam_step_multi (csrc/joints.hip). */
+int smil_adam_step_multi_bc64(const SmilAdamTensor *tensors, int32_t count, double beta1, double beta2, float eps, void *stream);
 
 #ifdef __cplusplus
 }

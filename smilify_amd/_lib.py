@@ -37,6 +37,8 @@ EXPORTS = [
     "smil_kp_se_forward", "smil_kp_se_backward", "smil_kp_project", "smil_kp_project_backward", "smil_kp_project_loss",
     "smil_kp_project_loss_backward", "smil_kp_triangulate", "smil_kp_triangulate_backward",
     "smil_align_forward", "smil_align_backward", "smil_align_errors",
+    "smil_joints_forward", "smil_joints_backward_workspace_bytes", "smil_joints_backward",
+    "smil_kp3d_fit_eval_workspace_bytes", "smil_kp3d_fit_eval", "smil_adam_step_multi_bc64",
 ]
 
 N_OBJS = 10
@@ -108,6 +110,23 @@ class Warp(Structure):
                 ("coord_mode", c_int32), ("interp", c_int32), ("affine", c_void_p), ("n_affine", c_int32),
                 ("K", c_void_p), ("K_new", c_void_p), ("dist", c_void_p), ("n_lens", c_int32), ("clamp", c_void_p), ("n_clamp", c_int32),
                 ("border", c_void_p), ("n_border", c_int32), ("scale", c_float)]
+
+
+class JointTables(Structure):
+    _fields_ = [(n, c_int32) for n in ("J", "nB", "P", "max_depth", "static_joints")] + [
+        (n, c_void_p) for n in ("parents", "depth", "child_ptr", "child", "J0", "JB", "pair_ptr", "pair_bone", "M0", "MB", "bpair_ptr",
+                                "bpair_joint", "bpair_index", "rowsum")]
+
+
+class JointsInputs(Structure):
+    _fields_ = [("B", c_int32), ("shared_beta", c_int32), ("nB_used", c_int32), ("beta", c_void_p), ("theta", c_void_p),
+                ("logscale", c_void_p), ("logscale_shared", c_int32), ("btrans", c_void_p), ("btrans_shared", c_int32),
+                ("trans", c_void_p), ("trans_after_joints", c_int32), ("propagate_scaling", c_int32), ("allow_limb_scaling", c_int32),
+                ("theta_mask", c_void_p)]
+
+
+class JointsGrads(Structure):
+    _fields_ = [(n, c_void_p) for n in ("d_joints", "d_beta", "d_theta", "d_trans", "d_logscale", "d_btrans", "workspace")]
 
 
 class MeshTopology(Structure):
@@ -259,6 +278,15 @@ def load():
                                        c_int32] + [c_void_p] * 9
     lib.smil_align_backward.argtypes = [c_void_p] * 8 + [c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
     lib.smil_align_errors.argtypes = [c_void_p] * 3 + [c_int64, c_int32, c_int32, c_int32, c_double, c_double, c_int32] + [c_void_p] * 4
+    lib.smil_joints_forward.argtypes = [POINTER(JointTables), POINTER(JointsInputs), c_void_p, c_void_p, c_void_p]
+    lib.smil_joints_backward_workspace_bytes.argtypes = [POINTER(JointTables), POINTER(JointsInputs), POINTER(JointsGrads)]
+    lib.smil_joints_backward_workspace_bytes.restype = c_size_t
+    lib.smil_joints_backward.argtypes = [POINTER(JointTables), POINTER(JointsInputs), POINTER(JointsGrads), c_void_p]
+    lib.smil_kp3d_fit_eval_workspace_bytes.argtypes = [POINTER(JointTables), POINTER(JointsInputs), c_int32, c_int32, c_int32]
+    lib.smil_kp3d_fit_eval_workspace_bytes.restype = c_size_t
+    lib.smil_kp3d_fit_eval.argtypes = [POINTER(FitConfig), c_double, c_double, POINTER(JointTables), POINTER(JointsInputs), c_int32] + \
+        [c_void_p] * 13
+    lib.smil_adam_step_multi_bc64.argtypes = [POINTER(AdamTensor), c_int32, c_double, c_double, c_float, c_void_p]
     lib.smil_profile_enable.argtypes = [c_int32]
     lib.smil_profile_read.argtypes = [POINTER(c_float), POINTER(c_int32)]
     for name in EXPORTS:

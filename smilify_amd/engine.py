@@ -1514,3 +1514,138 @@ def align_errors(pred, target, mask, mode: int, sentinel: bool, scale: float, mi
                                              float(min_gap), ROT_DTYPES[pred.dtype], _ptr(dist), _ptr(valid), _ptr(status), _stream()),
                "smil_align_errors")
     return dist, valid, status
+
+
+# ---- mesh-free joint kinematics and the fused 3-D keypoint evaluation (csrc/joints.hip; tables: joints.py) ----
+class DeviceJointTables:
+    """``joints.JointTables`` resident on one GPU (``SmilJointTables``), with the workspace the sums over frames use: ONE zeroed
+    buffer, grown when a call needs more, used by the calls on these tables in stream order (every call leaves its counter at zero)."""
+
+    def __init__(self, jt, device):
+        self.device = require_gpu(device)
+        self.host = jt
+        self.J, self.nB, self.P, self.static_joints = jt.J, jt.nB, jt.P, bool(jt.static_joints)
+        s = _lib.JointTables()
+        s.J, s.nB, s.P, s.max_depth, s.static_joints = jt.J, jt.nB, jt.P, jt.max_depth, int(jt.static_joints)
+        self._keep = {}
+        for name, dtype in (("parents", np.int32), ("depth", np.int32), ("child_ptr", np.int32), ("child", np.int32), ("J0", np.float64),
+                            ("JB", np.float64), ("pair_ptr", np.int32), ("pair_bone", np.int32), ("M0", np.float64), ("MB", np.float64),
+                            ("bpair_ptr", np.int32), ("bpair_joint", np.int32), ("bpair_index", np.int32), ("rowsum", np.float64)):
+            a = np.ascontiguousarray(getattr(jt, name), dtype)
+            if a.size:
+                self._keep[name] = torch.from_numpy(a.copy()).to(self.device)
+                setattr(s, name, self._keep[name].data_ptr())
+        self.struct = s
+        self._ws: Optional[torch.Tensor] = None
+
+    def workspace(self, nbytes: int) -> Optional[torch.Tensor]:
+        if nbytes == 0:
+            return None
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+
+def _joints_inputs(jt: DeviceJointTables, beta, theta, trans, logscale, btrans, theta_mask, fl: Dict) -> _lib.JointsInputs:
+    """beta (B,nB_used) or (nB_used,) [shared]; theta (B,J,3); logscale / btrans (B,J,3) or (J,3) [shared] or None; trans (B,3) or None;
+    ``fl``: trans_after_joints, propagate_scaling, allow_limb_scaling.  Shapes are checked here: a kernel never reads past a buffer."""
+    B, J = int(theta.shape[0]), jt.J
+    if tuple(theta.shape) != (B, J, 3):
+        raise ValueError(f"theta must be (B,{J},3), got {tuple(theta.shape)}")
+    if beta.dim() not in (1, 2) or (beta.dim() == 2 and beta.shape[0] != B) or beta.shape[-1] > jt.nB:
+        raise ValueError(f"beta must be (B,nB_used) or (nB_used,) with B={B}, nB_used <= {jt.nB}; got {tuple(beta.shape)}")
+    i = _lib.JointsInputs()
+    i.B, i.shared_beta, i.nB_used = B, int(beta.dim() == 1), int(beta.shape[-1])
+    i.beta, i.theta = _ptr(beta) if beta.numel() else None, _ptr(theta)
+    for name, t in (("logscale", logscale), ("btrans", btrans)):
+        if t is not None and tuple(t.shape) not in ((B, J, 3), (J, 3)):
+            raise ValueError(f"{name} must be (B,{J},3) or ({J},3) with B={B}, got {tuple(t.shape)}")
+        setattr(i, name, _ptr(t))
+        setattr(i, name + "_shared", int(t is not None and t.dim() == 2))
+    if trans is not None and tuple(trans.shape) != (B, 3):
+        raise ValueError(f"trans must be (B,3) with B={B}, got {tuple(trans.shape)}")
+    if theta_mask is not None and tuple(theta_mask.shape) != (J, 3):
+        raise ValueError(f"theta_mask must be ({J},3), got {tuple(theta_mask.shape)}")
+    i.trans, i.theta_mask = _ptr(trans), _ptr(theta_mask)
+    i.trans_after_joints, i.propagate_scaling = int(fl.get("trans_after_joints", True)), int(fl.get("propagate_scaling", False))
+    i.allow_limb_scaling = int(fl.get("allow_limb_scaling", True))
+    for t in (beta, theta, trans, logscale, btrans, theta_mask):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != jt.device):
+            raise ValueError("the joints kernels take contiguous float32 tensors on the tables' device")
+    return i
+
+
+def joints_forward(jt: DeviceJointTables, beta, theta, trans=None, logscale=None, btrans=None, theta_mask=None, want_new_J=True, **fl):
+    """``(joints (B,J,3), new_J (B,J,3) or None)``: smil_joints_forward."""
+    i = _joints_inputs(jt, beta, theta, trans, logscale, btrans, theta_mask, fl)
+    joints = torch.empty(i.B, jt.J, 3, dtype=torch.float32, device=jt.device)
+    new_J = torch.empty_like(joints) if want_new_J else None
+    _lib.check(_lib.load().smil_joints_forward(ctypes.byref(jt.struct), ctypes.byref(i), _ptr(joints), _ptr(new_J), _stream()),
+               "smil_joints_forward")
+    return joints, new_J
+
+
+def joints_backward(jt: DeviceJointTables, d_joints, beta, theta, trans=None, logscale=None, btrans=None, theta_mask=None,
+                    need=("d_beta", "d_theta", "d_trans", "d_logscale", "d_btrans"), **fl) -> Dict[str, torch.Tensor]:
+    """The gradients named in ``need`` (shapes of the inputs; a shared table's gradient is the sum over frames): smil_joints_backward."""
+    i = _joints_inputs(jt, beta, theta, trans, logscale, btrans, theta_mask, fl)
+    B, J = i.B, jt.J
+    if tuple(d_joints.shape) != (B, J, 3) or d_joints.dtype != torch.float32 or not d_joints.is_contiguous():
+        raise ValueError(f"d_joints must be a contiguous float32 ({B},{J},3) tensor")
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=jt.device)  # noqa: E731
+    out = {}
+    if "d_beta" in need and i.nB_used > 0:
+        out["d_beta"] = new(*beta.shape)
+    if "d_theta" in need:
+        out["d_theta"] = new(B, J, 3)
+    if "d_trans" in need:
+        out["d_trans"] = new(B, 3)
+    if "d_logscale" in need:
+        out["d_logscale"] = new(*(logscale.shape if logscale is not None else (B, J, 3)))
+    if "d_btrans" in need:
+        out["d_btrans"] = new(*(btrans.shape if btrans is not None else (B, J, 3)))
+    g = _lib.JointsGrads()
+    g.d_joints = _ptr(d_joints)
+    for k, v in out.items():
+        setattr(g, k, _ptr(v))
+    lib = _lib.load()
+    ws = jt.workspace(int(lib.smil_joints_backward_workspace_bytes(ctypes.byref(jt.struct), ctypes.byref(i), ctypes.byref(g))))
+    g.workspace = _ptr(ws)
+    _lib.check(lib.smil_joints_backward(ctypes.byref(jt.struct), ctypes.byref(i), ctypes.byref(g), _stream()), "smil_joints_backward")
+    return out
+
+
+def kp3d_fit_eval(cfg: _lib.FitConfig, jt: DeviceJointTables, w_k3d: float, robust_scale: float, canon, target, visibility, joint_weights,
+                  beta, theta, trans, logscale, btrans, theta_mask, objs, d_pose, d_trans, d_betas=None, d_logscale=None, d_btrans=None,
+                  joints_out=None, **fl) -> None:
+    """smil_kp3d_fit_eval: canon (Jc) int32 or None, target (N,Jc,3) float32, visibility (N,Jc) uint8 or None, joint_weights (Jc)
+    float64 or None; objs[9] is added to, the gradient tensors are overwritten with the RAW gradients."""
+    fl = dict(fl, trans_after_joints=True)
+    i = _joints_inputs(jt, beta, theta, trans, logscale, btrans, theta_mask, fl)
+    N, Jc = i.B, int(target.shape[1])
+    if tuple(target.shape) != (N, Jc, 3) or target.dtype != torch.float32 or not target.is_contiguous():
+        raise ValueError(f"target must be a contiguous float32 ({N},Jc,3) tensor, got {tuple(target.shape)} {target.dtype}")
+    if canon is not None and (canon.dtype != torch.int32 or tuple(canon.shape) != (Jc,)):
+        raise ValueError(f"canon must be int32 ({Jc},)")
+    if visibility is not None and (visibility.dtype != torch.uint8 or tuple(visibility.shape) != (N, Jc) or not visibility.is_contiguous()):
+        raise ValueError(f"visibility must be a contiguous uint8 ({N},{Jc}) tensor")
+    if joint_weights is not None and (joint_weights.dtype != torch.float64 or tuple(joint_weights.shape) != (Jc,)):
+        raise ValueError(f"joint_weights must be float64 ({Jc},)")
+    lib = _lib.load()
+    ws = jt.workspace(int(lib.smil_kp3d_fit_eval_workspace_bytes(ctypes.byref(jt.struct), ctypes.byref(i), int(d_betas is not None),
+                                                                 int(d_logscale is not None), int(d_btrans is not None))))
+    _lib.check(lib.smil_kp3d_fit_eval(ctypes.byref(cfg), float(w_k3d), float(robust_scale), ctypes.byref(jt.struct), ctypes.byref(i), Jc,
+                                      _ptr(canon), _ptr(target), _ptr(visibility), _ptr(joint_weights), _ptr(objs), _ptr(d_pose),
+                                      _ptr(d_trans), _ptr(d_betas), _ptr(d_logscale), _ptr(d_btrans), _ptr(joints_out), _ptr(ws),
+                                      _stream()), "smil_kp3d_fit_eval")
+
+
+def adam_step_multi_bc64(items, beta1=0.5, beta2=0.999, eps=1e-8):
+    """``adam_step_multi`` through smil_adam_step_multi_bc64: the bias corrections formed in double, as torch.optim.Adam forms them."""
+    for k0 in range(0, len(items), _lib.ADAM_MAX_TENSORS):
+        chunk = items[k0:k0 + _lib.ADAM_MAX_TENSORS]
+        arr = (_lib.AdamTensor * len(chunk))()
+        for a, (p, g, m, v, lr, step) in zip(arr, chunk):
+            a.param, a.grad, a.exp_avg, a.exp_avg_sq = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
+            a.n, a.lr, a.step = p.numel(), float(lr), int(step)
+        _lib.check(_lib.load().smil_adam_step_multi_bc64(arr, len(chunk), beta1, beta2, eps, _stream()), "smil_adam_step_multi_bc64")

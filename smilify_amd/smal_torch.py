@@ -75,6 +75,34 @@ class _LbsFunction(torch.autograd.Function):
         return None, None, g["d_beta"], d_theta, g["d_trans"], d_ls, d_bt, d_delv, d_vt
 
 
+class _JointsFunction(torch.autograd.Function):
+    """Posed joints without vertices (csrc/joints.hip).  Nothing is saved but the inputs: the backward recomputes the chain."""
+
+    @staticmethod
+    def forward(ctx, jt, flags, beta, theta, trans, logscale, btrans):
+        c = lambda t: None if t is None else t.detach().to(device=jt.device, dtype=torch.float32).contiguous()  # noqa: E731
+        args = (c(beta), c(theta), c(trans), c(logscale), c(btrans))
+        joints, new_J = engine.joints_forward(jt, *args, **flags)
+        ctx.jt, ctx.flags = jt, flags
+        ctx.save_for_backward(*(a for a in args if a is not None))
+        ctx.present = tuple(a is not None for a in args)
+        ctx.mark_non_differentiable(new_J)
+        return joints, new_J
+
+    @staticmethod
+    def backward(ctx, d_joints, _dnj):
+        if d_joints is None:
+            return (None,) * 7
+        saved = iter(ctx.saved_tensors)
+        beta, theta, trans, logscale, btrans = (next(saved) if p else None for p in ctx.present)
+        n = ctx.needs_input_grad  # (jt, flags, beta, theta, trans, logscale, btrans)
+        need = [k for k, on in (("d_beta", n[2] and beta.shape[-1] > 0), ("d_theta", n[3]), ("d_trans", n[4] and trans is not None),
+                                ("d_logscale", n[5] and logscale is not None), ("d_btrans", n[6] and btrans is not None)) if on]
+        g = engine.joints_backward(ctx.jt, d_joints.to(torch.float32).contiguous(), beta, theta, trans, logscale, btrans, need=need,
+                                   **ctx.flags)
+        return None, None, g.get("d_beta"), g.get("d_theta"), g.get("d_trans"), g.get("d_logscale"), g.get("d_btrans")
+
+
 _HARDCODED_BODY_VERTS = (1863, 26, 2124, 150, 3055, 1097)  # end of nose, chin, right / left ear tip, left / right eye
 
 
@@ -185,4 +213,56 @@ class SMAL(nn.Module):
             joints = torch.cat([joints, verts[:, list(_HARDCODED_BODY_VERTS)]], dim=1)
         if get_skin:
             return verts, joints, Rs, v_shaped
+        return joints
+
+    @property
+    def joint_tables(self) -> engine.DeviceJointTables:
+        """The mesh-free joint tables of this model on its device, built on first use (``joints.JointTables``: raises
+        NotImplementedError for a model with pose blend shapes)."""
+        if getattr(self, "_jt", None) is None:
+            from .joints import JointTables
+
+            self._jt = engine.DeviceJointTables(JointTables.from_tables(self.tables), self.device)
+        return self._jt
+
+    def joints(self, beta, theta, trans=None, betas_logscale=None, betas_trans=None, propagate_scaling=False):
+        """The posed joints ``__call__(...)[1]`` returns, (B,J,3) and differentiable, computed from the kinematic chain and the
+        model's joint moments without forming a vertex (csrc/joints.hip; float64 arithmetic, equal to ``__call__``'s up to rounding).
+        Same argument checks and broadcasting as ``__call__``; sets ``J_transformed``.  Axis-angle ``theta`` only; models with pose
+        blend shapes, ``del_v`` and ``v_template`` overrides stay with ``__call__``."""
+        J = self.tables.J
+        if J == 35 and not self.config.ignore_hardcoded_body:
+            raise NotImplementedError("SMAL.joints: the legacy body's six extra joints are vertices of the posed mesh; use SMAL.__call__")
+        if theta.dim() == 4:
+            raise ValueError("SMAL.joints takes axis-angle theta (B,J,3); rotation matrices go through SMAL.__call__")
+        if theta.shape[1] != J:  # reference :282-287: wrong joint count -> zero pose
+            theta = torch.zeros(beta.shape[0] if beta.shape[1] > 0 else 1, J, 3, device=self.device)
+        if tuple(theta.shape[1:]) != (J, 3):
+            raise ValueError(f"theta must be (B,{J},3) axis-angle, got {tuple(theta.shape)}")
+        B = theta.shape[0]
+        if beta.dim() != 2 or beta.shape[0] not in (1, B):
+            raise ValueError(f"beta must be (B,nB) or (1,nB) with B={B}, got {tuple(beta.shape)}")
+        if beta.shape[1] > self.tables.nB:
+            raise ValueError(f"beta has {beta.shape[1]} columns but the model has {self.tables.nB} shape directions")
+
+        def rows(name, t, tail):  # (as in __call__; one row shared by the batch goes to the kernel as one row)
+            if t is None:
+                return None
+            if tuple(t.shape) == tail:
+                t = t[None]
+            if t.dim() != len(tail) + 1 or tuple(t.shape[1:]) != tail or t.shape[0] not in (1, B):
+                raise ValueError(f"{name} must be (B,{','.join(map(str, tail))}) or broadcast from one row, with B={B}; got {tuple(t.shape)}")
+            return t[0] if (t.shape[0] == 1 and B > 1) else t
+
+        trans = rows("trans", trans, (3,))
+        if trans is not None and trans.dim() == 1:
+            trans = trans[None].expand(B, 3)
+        betas_logscale = rows("betas_logscale", betas_logscale, (J, 3))
+        betas_trans = rows("betas_trans", betas_trans, (J, 3))
+        if beta.shape[0] == 1 and B > 1:
+            beta = beta[0]
+        flags = dict(trans_after_joints=False, propagate_scaling=bool(propagate_scaling),
+                     allow_limb_scaling=bool(self.config.ALLOW_LIMB_SCALING))
+        joints, new_J = _JointsFunction.apply(self.joint_tables, flags, beta, theta, trans, betas_logscale, betas_trans)
+        self.J_transformed = new_J
         return joints
