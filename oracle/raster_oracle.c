@@ -15,8 +15,10 @@
  *                                               BarycentricClipForward, PointLineDistance*,
  *                                               PointTriangleDistance*
  *   renderer/blending.py                        sigmoid_alpha_blend
- * PARITY UNPINNED for this file: the reference holds no golden silhouette; it is pinned
- * only by analytic known-answer cases in tests/test_oracle_raster.py.
+ * PARITY UNPINNED by reference-owned vectors: pytorch3d itself is absent and the reference holds no golden silhouette.  What
+ * checks this file: analytic known-answer cases (tests/test_oracle_raster.py) and an independent float64 restatement of the same
+ * published algorithm with an autograd gradient (tests/raster_ref64.py), against which forward and backward of this file are
+ * measured per pixel and per vertex component on the scenes of tests/raster_cases.py (tests/test_raster_ref64_cpu.py).
  *
  * Layout: verts_ndc (N,V,3) fp32 = (x_ndc, y_ndc, z_view) per image; faces (F,3) int32
  * shared by all images; output sil (N,S,S) fp32, row = image y (top row first).

@@ -5,8 +5,9 @@ CPU restatement of the camera/projection/silhouette arithmetic behind the refere
 un-vendored third-party ``pytorch3d`` (pinned 0.7.8, environment.yml:35) - this restates the
 published algorithm of ``FoVPerspectiveCameras`` / ``look_at_view_transform`` /
 ``transform_points_screen`` / ``MeshRasterizer.transform`` and binds the C restatement of the
-naive rasteriser (oracle/raster_oracle.c).  PARITY UNPINNED by reference-owned vectors; pinned
-by analytic known-answer tests only (tests/test_oracle_raster.py).
+naive rasteriser (oracle/raster_oracle.c).  PARITY UNPINNED by reference-owned vectors (pytorch3d is absent); checked by analytic
+known-answer tests (tests/test_oracle_raster.py) and, silhouette and gradient, by an independent float64 restatement with an autograd
+gradient (tests/raster_ref64.py, tests/test_raster_ref64_cpu.py; ``clip_depth_gradient`` against autograd through the crossing points).
 """
 from __future__ import annotations
 

@@ -1,6 +1,6 @@
 """Known-answer tests for the oracle's restatement of the naive soft-silhouette rasteriser.
 PARITY UNPINNED by reference-owned vectors (pytorch3d is un-vendored and absent): these analytic
-cases are what pins oracle/raster_oracle.c."""
+cases and the float64 restatement of tests/raster_ref64.py (tests/test_raster_ref64_cpu.py) are what checks oracle/raster_oracle.c."""
 import math
 
 import numpy as np
