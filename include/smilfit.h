@@ -53,7 +53,8 @@ int smil_model_create(const SmilModelDesc *desc, SmilModel **out);
 void smil_model_destroy(SmilModel *m);
 int smil_model_dims(const SmilModel *m, int32_t dims[4]); /* V,F,J,nB */
 const char *smil_last_error(void);
-const char *smil_version(void);   /* "smilfit 0.6 (gfx950; 0.3 + SmilCameras.principal (0.4) + fragments, depth visibility (0.5) + mesh-free joints, kp3d fit)".  0.6 adds
+const char *smil_version(void);   /* "smilfit 0.7 (gfx950; 0.3 + SmilCameras.principal (0.4) + fragments, depth visibility (0.5) + mesh-free joints, kp3d fit (0.6) + kp2d fit)".  0.7 adds
+                                    * smil_kp2d_fit_eval and its workspace query and changes no layout.  0.6 adds
                                     * smil_joints_forward / smil_joints_backward / smil_kp3d_fit_eval / smil_adam_step_multi_bc64 with their own structs and changes no layout.
                                     * 0.3 = the layout of rounds 5 - 6: SmilLbsGrads carries clip_depth in front of
                                     * beta_rows (which must hold 2 * B * nB_used + 16 floats), SmilRasterSettings ends in {tie_rule, clip_depth,
@@ -998,6 +999,43 @@ int smil_kp3d_fit_eval(const SmilFitConfig *cfg, double w_k3d, double robust_sca
                        int32_t Jc, const int32_t *canon, const float *target, const uint8_t *visibility, const double *joint_weights,
                        float *objs, float *d_pose, float *d_trans, float *d_betas, float *d_logscale, float *d_btrans, float *joints_out,
                        void *workspace, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Multi-view 2-D keypoint term on the mesh-free joints, fused like smil_kp3d_fit_eval: chain, joints, projection into every view, the
+ * term and the whole backward of a frame in one launch.  Images are numbered frame * views + view; cam->N = cfg->N * cam->views,
+ * cam->views <= 64, cam->S the side of the square image the pixels are measured in.  With yx(X; cam) the (y, x) pixel position of a
+ * world point and b_w the window sizes of smil_kp3d_fit_eval:
+ *   objs[0] += w_k2d sum_w 1/(2 Jc Nv b_w) sum_{n in w} sum_{v < Nv} sum_{c < Jc}
+ *              seen[n,v,c] conf[n,v,c] wj[c] rho(|yx(joints[n,canon[c]]; cam(n,v)) - target2d[n,v,c]|^2)
+ * rho(s) = s when robust_scale_px == 0: with no confidences and no joint weights the value of smil_joint_loss on the same
+ * projections, element for element (an unseen entry counts in the denominator: fitter.py:292-296); with robust_scale_px = sigma > 0
+ * the soft-L1 2 sigma^2 (sqrt(1 + s / sigma^2) - 1), evaluated as 2 s / (1 + u), u = sqrt(1 + s / sigma^2), gradient factor 1 / u.
+ * Camera arithmetic: that of csrc/camera.h in float64 on the float32 tables - X_view = X R + T; k11 = 1 / tan(fov / 2) (fov in
+ * degrees), k00 = k11 / aspect; x_ndc = k00 x_view / z_view + px, y_ndc = k11 y_view / z_view + py (the principal point added after
+ * the division); y_s = S/2 - (S/2) y_ndc, x_s = S/2 - (S/2) x_ndc.  R, T, fov, aspect and principal may each hold 1, views or
+ * N * views rows, indexed image % rows.  The cameras are constants: no gradient on them is returned.
+ * seen[n,v,c] holds iff visibility2d (if given) is non-zero, both target coordinates are finite, the confidence (if given) is finite
+ * and > 0, and z_view of the joint in that camera (float64) is > SMIL_ZNEAR = 0.001.  An entry that is not seen contributes exactly 0
+ * and no gradient.
+ * The 3-D term of smil_kp3d_fit_eval (objs[9], its own visibility rule, the same joint_weights) is evaluated in the same launch when
+ * target3d is not NULL and w_k3d > 0; the 2-D term when target2d is not NULL and w_k2d > 0; both add into the gradient on the joints
+ * before the chain backward; a call that asks for neither is an error, and the slot of a term not asked for is not written.  A
+ * frame with no seen entry in any view and no visible 3-D target contributes exactly 0 and writes +0 in every gradient.
+ * target2d (N,Nv,Jc,2) float32 (y,x); visibility2d (N,Nv,Jc) uint8 or NULL; confidence (N,Nv,Jc) float32 or NULL; joint_weights
+ * (Jc) float64 or NULL; target3d (N,Jc,3) / visibility3d (N,Jc) as in smil_kp3d_fit_eval, or NULL.  The gradient outputs, joints_out
+ * and the workspace are those of smil_kp3d_fit_eval (RAW gradients, finished by smil_prior_losses(accumulate = 1)).  yx_out
+ * (N,Nv,Jc,2) float32 or NULL: the projections of the canonical joints, rounded once, NaN where the depth rule fails (whatever the
+ * targets hold).  Each lane adds its joint's contributions in a fixed order (the 3-D entries of the joint, then the 2-D ones: canon
+ * entries ascending, views ascending within each); all sums over frames are taken in a fixed order: two calls return the same bits.
+ * Errors (smil_last_error): a NaN, infinite or negative weight or scale; views outside 1..64; cam->N != cfg->N * views;
+ * in->B != cfg->N; trans_after_joints != 1; a camera table whose row count is not 1, views or N * views. */
+size_t smil_kp2d_fit_eval_workspace_bytes(const SmilJointTables *t, const SmilJointsInputs *in, const SmilCameras *cam, int32_t want_betas,
+                                          int32_t want_logscale, int32_t want_btrans);
+int smil_kp2d_fit_eval(const SmilFitConfig *cfg, double w_k2d, double robust_scale_px, const SmilJointTables *t, const SmilJointsInputs *in,
+                       const SmilCameras *cam, int32_t Jc, const int32_t *canon, const float *target2d, const uint8_t *visibility2d,
+                       const float *confidence, const double *joint_weights, double w_k3d, double robust_scale, const float *target3d,
+                       const uint8_t *visibility3d, float *objs, float *d_pose, float *d_trans, float *d_betas, float *d_logscale,
+                       float *d_btrans, float *joints_out, float *yx_out, void *workspace, void *stream);
 
 /* smil_adam_step_multi with the bias corrections formed in double, as torch.optim.Adam forms them: 1 - beta1^step and
  * sqrt(1 - beta2^step) are computed in double from the betas the caller wrote and rounded to float32 once, and the step size

@@ -39,6 +39,7 @@ EXPORTS = [
     "smil_align_forward", "smil_align_backward", "smil_align_errors",
     "smil_joints_forward", "smil_joints_backward_workspace_bytes", "smil_joints_backward",
     "smil_kp3d_fit_eval_workspace_bytes", "smil_kp3d_fit_eval", "smil_adam_step_multi_bc64",
+    "smil_kp2d_fit_eval_workspace_bytes", "smil_kp2d_fit_eval",
 ]
 
 N_OBJS = 10
@@ -286,6 +287,10 @@ def load():
     lib.smil_kp3d_fit_eval_workspace_bytes.restype = c_size_t
     lib.smil_kp3d_fit_eval.argtypes = [POINTER(FitConfig), c_double, c_double, POINTER(JointTables), POINTER(JointsInputs), c_int32] + \
         [c_void_p] * 13
+    lib.smil_kp2d_fit_eval_workspace_bytes.argtypes = [POINTER(JointTables), POINTER(JointsInputs), POINTER(Cameras), c_int32, c_int32, c_int32]
+    lib.smil_kp2d_fit_eval_workspace_bytes.restype = c_size_t
+    lib.smil_kp2d_fit_eval.argtypes = [POINTER(FitConfig), c_double, c_double, POINTER(JointTables), POINTER(JointsInputs), POINTER(Cameras),
+                                       c_int32] + [c_void_p] * 5 + [c_double, c_double] + [c_void_p] * 12
     lib.smil_adam_step_multi_bc64.argtypes = [POINTER(AdamTensor), c_int32, c_double, c_double, c_float, c_void_p]
     lib.smil_profile_enable.argtypes = [c_int32]
     lib.smil_profile_read.argtypes = [POINTER(c_float), POINTER(c_int32)]

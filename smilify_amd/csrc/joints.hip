@@ -1,5 +1,6 @@
 // Mesh-free joint kinematics for gfx950: the posed joints of SMAL.__call__ (reference smal_model/smal_torch.py:340-351) without a
-// vertex, their backward, and the 3-D keypoint term of a sequence fit fused onto both.
+// vertex, their backward, and the keypoint terms of a sequence fit fused onto both: the 3-D term (smil_kp3d_fit_eval) and the multi-view
+// 2-D reprojection term with the 3-D one optionally beside it (smil_kp2d_fit_eval; specification: include/smilfit.h).
 //
 // A static-joint model's joints are the translation column of the kinematic chain.  A regressor model's joints are linear in the
 // bone transforms: joints[j] = sum_k A_k m[j,k] over the (joint, bone) pairs of smilify_amd/joints.py, m = M0 + sum_b beta_b MB_b,
@@ -32,8 +33,17 @@ struct JArgs {
     const uint8_t *vis;
     const double *wj;
     float *objs;
+    // fused multi-view 2-D keypoint term (K2D instantiations only; `target` / `vis` above are then the optional 3-D targets)
+    double w_k2d, sigma_px;
+    SmilCameras cam;
+    int cam_wave;            // doubles of a wave's LDS that hold its frame's cameras; 0: one set per block, staged once, ...
+    int cam_block;           // ... this many doubles behind the waves' LDS
+    const float *target2d;   // (N,Nv,Jc,2) (y,x) px
+    const uint8_t *vis2d;    // (N,Nv,Jc) or NULL
+    const float *conf;       // (N,Nv,Jc) or NULL
+    float *yx_out;           // (N,Nv,Jc,2) or NULL
     // sums over frames: columns of a block's row (-1: not kept), the rows and the counter of finished blocks
-    int C, c_obj, c_beta, c_ls, c_bt;
+    int C, c_obj, c_obj2, c_beta, c_ls, c_bt;
     unsigned int *counter;
     double *part;
 };
@@ -231,15 +241,33 @@ __device__ __forceinline__ int window_size_of(const SmilFitConfig &c, int local_
 // doubles of LDS a wave of the backward kernels needs
 __host__ __device__ static inline size_t bwd_wave_doubles(int J, int C) { return (size_t)J * 39 + (size_t)C; }
 
-// Backward of k_joints_fwd (FUSED false: d_joints from memory) and the fused 3-D keypoint evaluation (FUSED true: d_joints is the
-// gradient of the term, formed here).  The forward is recomputed in LDS.
-template <int NJ, bool FUSED>
+// A camera staged for the 2-D term: sixteen doubles, float64 arithmetic on the float32 tables (camera.h: X_view = X R + T,
+// k11 = 1 / tan(fov / 2), k00 = k11 / aspect, the principal point added after the division)
+#define K2D_CAM 16
+#define K2D_MAX_VIEWS 64
+__device__ __forceinline__ void stage_camera64(double *row, const SmilCameras &c, int n) {
+    const float *R = c.R + (size_t)(n % c.nR) * 9, *T = c.T + (size_t)(n % c.nT) * 3;
+    for (int i = 0; i < 9; ++i) row[i] = (double)R[i];
+    for (int i = 0; i < 3; ++i) row[9 + i] = (double)T[i];
+    const double k11 = 1.0 / tan((double)c.fov[n % c.nFov] * 0.017453292519943295 / 2.0);
+    row[12] = c.aspect ? k11 / (double)c.aspect[n % c.nAspect] : k11;
+    row[13] = k11;
+    row[14] = c.principal ? (double)c.principal[2 * (size_t)(n % c.nPrincipal)] : 0.0;
+    row[15] = c.principal ? (double)c.principal[2 * (size_t)(n % c.nPrincipal) + 1] : 0.0;
+}
+
+// Backward of k_joints_fwd (FUSED false: d_joints from memory) and the fused keypoint evaluations (FUSED true: d_joints is the
+// gradient of the term, formed here): the 3-D term alone (K2D false, smil_kp3d_fit_eval) or the multi-view 2-D term with the 3-D
+// term optionally beside it (K2D true, smil_kp2d_fit_eval).  The forward is recomputed in LDS.  Everything the 2-D term adds
+// stands under `if (K2D)`: the other instantiations hold the operations they held before it existed, in their order.
+template <int NJ, bool FUSED, bool K2D = false>
 __global__ void __launch_bounds__(64 * JT_MAX_FPB) k_joints_bwd(JArgs a) {
+    static_assert(FUSED || !K2D, "the 2-D term is a fused term");
     extern __shared__ double smem64[];
     __shared__ unsigned int s_last;
     const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63, fpb = blockDim.x >> 6;
     const int J = a.t.J, B = a.in.B, C = a.C;
-    const size_t per_wave = bwd_wave_doubles(J, C);
+    const size_t per_wave = bwd_wave_doubles(J, C) + (K2D ? (size_t)a.cam_wave : 0);
     double *sG = smem64 + (size_t)wid * per_wave;  // (J,12) world transforms
     double *sdG = sG + J * 12;                      // (J,12) their gradients; after a joint's turn: what it owes its parent
     double *sJ = sdG + J * 12;                      // (J,3) rest joints
@@ -251,6 +279,10 @@ __global__ void __launch_bounds__(64 * JT_MAX_FPB) k_joints_bwd(JArgs a) {
     int *sChild = (int *)(smem64 + (size_t)fpb * per_wave);  // (J) the child lists, one copy per block
     for (int i = lane; i < C; i += WAVE) acc[i] = 0.0;
     for (int i = threadIdx.x; i < J - 1; i += blockDim.x) sChild[i] = a.t.child[i];
+    // (K2D) the cameras of a frame, (views,16) float64: behind the wave's sums when they differ by frame, else behind the child lists
+    double *sCam = K2D ? (a.cam_wave ? acc + C : smem64 + (size_t)fpb * per_wave + a.cam_block) : nullptr;
+    if (K2D && !a.cam_wave)
+        for (int v = threadIdx.x; v < a.cam.views; v += blockDim.x) stage_camera64(sCam + K2D_CAM * v, a.cam, v);
     __syncthreads();
 
     for (int b0 = blockIdx.x * fpb; b0 < B; b0 += gridDim.x * fpb) {
@@ -259,14 +291,18 @@ __global__ void __launch_bounds__(64 * JT_MAX_FPB) k_joints_bwd(JArgs a) {
         const size_t fb = live ? b : 0;
         const float *beta = a.in.beta + (size_t)(a.in.shared_beta ? 0 : fb) * a.in.nB_used;
         LaneState<NJ> L;
+        if (K2D && a.cam_wave && live && lane < a.cam.views)  // (visible after chain_forward's barriers)
+            stage_camera64(sCam + K2D_CAM * lane, a.cam, (int)fb * a.cam.views + lane);
         chain_forward<NJ>(a, b, live, lane, beta, sG, sJ, L);
 
         // ---- upstream gradient on the posed joints ----
         bool dead = false;  // (wave-uniform) fused: nothing visible in this frame - every gradient is +0
         if (FUSED) {
             double loss = 0.0, nvis = 0.0;
+            double loss2 = 0.0;  // (K2D) the 2-D term of this frame
             const double scale = live ? a.w_k3d / (3.0 * (double)a.Jc * (double)window_size_of(a.cfg, b)) : 0.0;
-#pragma unroll
+            constexpr int TERM_UNROLL = K2D ? 1 : NJ;  // (nothing below indexes the lane state: the 2-D term's longer body stays rolled, for the registers' sake)
+#pragma unroll TERM_UNROLL
             for (int q = 0; q < NJ; ++q) {
                 const int j = lane + WAVE * q;
                 if (!live || j >= J) continue;
@@ -276,7 +312,7 @@ __global__ void __launch_bounds__(64 * JT_MAX_FPB) k_joints_bwd(JArgs a) {
                     for (int k = 0; k < 3; ++k) pos[k] += (double)a.in.trans[3 * fb + k];
                 if (a.joints)
                     for (int k = 0; k < 3; ++k) a.joints[(fb * J + j) * 3 + k] = (float)pos[k];
-                for (int c = 0; c < a.Jc; ++c) {  // (every lane scans the list for its own joints: fixed order, duplicates allowed)
+                for (int c = 0; c < (K2D && !a.target ? 0 : a.Jc); ++c) {  // (every lane scans the list for its own joints: fixed order, duplicates allowed)
                     if ((a.canon ? a.canon[c] : c) != j) continue;
                     const float *tg = a.target + (fb * a.Jc + c) * 3;
                     const float t0 = tg[0], t1 = tg[1], t2 = tg[2];
@@ -297,11 +333,62 @@ __global__ void __launch_bounds__(64 * JT_MAX_FPB) k_joints_bwd(JArgs a) {
                     dj[0] += 2.0 * g * r0; dj[1] += 2.0 * g * r1; dj[2] += 2.0 * g * r2;
                     nvis += 1.0;
                 }
+                if (K2D) {  // the 2-D term after the 3-D one: canon entries ascending, views ascending within each
+                    const int Nv = a.cam.views;
+                    const double hS = 0.5 * (double)a.cam.S;
+                    const double scale2 = a.w_k2d / (2.0 * (double)a.Jc * (double)Nv * (double)window_size_of(a.cfg, b));
+                    for (int c = 0; c < a.Jc; ++c) {
+                        if ((a.canon ? a.canon[c] : c) != j) continue;
+                        const double wc = (a.wj ? a.wj[c] : 1.0) * scale2;
+                        for (int v = 0; v < Nv; ++v) {
+                            const double *cm = sCam + K2D_CAM * v;
+                            const size_t e = (fb * Nv + v) * a.Jc + c;
+                            const double vx = pos[0] * cm[0] + pos[1] * cm[3] + pos[2] * cm[6] + cm[9];
+                            const double vy = pos[0] * cm[1] + pos[1] * cm[4] + pos[2] * cm[7] + cm[10];
+                            const double vz = pos[0] * cm[2] + pos[1] * cm[5] + pos[2] * cm[8] + cm[11];
+                            const bool front = vz > (double)SMIL_ZNEAR;
+                            const double iz = 1.0 / vz;
+                            const double xn = vx * cm[12] * iz, yn = vy * cm[13] * iz;  // (unshifted)
+                            const double ys = hS - hS * (yn + cm[15]), xs = hS - hS * (xn + cm[14]);
+                            if (a.yx_out) {
+                                a.yx_out[2 * e] = front ? (float)ys : __builtin_nanf("");
+                                a.yx_out[2 * e + 1] = front ? (float)xs : __builtin_nanf("");
+                            }
+                            if (!a.target2d) continue;
+                            const float ty = a.target2d[2 * e], tx = a.target2d[2 * e + 1];
+                            const float cf = a.conf ? a.conf[e] : 1.f;
+                            const bool seen = front && (!a.vis2d || a.vis2d[e] != 0) && isfinite(ty) && isfinite(tx) && isfinite(cf) && cf > 0.f;
+                            if (!seen) continue;
+                            const double w = wc * (double)cf;
+                            const double ry = ys - (double)ty, rx = xs - (double)tx;
+                            const double s = ry * ry + rx * rx;
+                            double g = w;
+                            if (a.sigma_px > 0.0) {
+                                const double u = sqrt(1.0 + s / (a.sigma_px * a.sigma_px));
+                                loss2 += w * 2.0 * s / (u + 1.0);
+                                g = w / u;
+                            } else {
+                                loss2 += w * s;
+                            }
+                            // d y_s = 2 g ry, d x_s = 2 g rx ; y_s = hS - hS y_ndc ; then camera_project_bwd's chain in float64
+                            const double dyn = -hS * 2.0 * g * ry, dxn = -hS * 2.0 * g * rx;
+                            const double dvx = dxn * cm[12] * iz, dvy = dyn * cm[13] * iz, dvz = -(xn * dxn + yn * dyn) * iz;
+                            dj[0] += cm[0] * dvx + cm[1] * dvy + cm[2] * dvz;
+                            dj[1] += cm[3] * dvx + cm[4] * dvy + cm[5] * dvz;
+                            dj[2] += cm[6] * dvx + cm[7] * dvy + cm[8] * dvz;
+                            nvis += 1.0;
+                        }
+                    }
+                }
                 for (int k = 0; k < 3; ++k) sDJ[3 * j + k] = dj[k];
             }
             loss = wave_sum(loss);
             nvis = wave_sum(nvis);
             dead = !(nvis > 0.0);
+            if (K2D) {
+                loss2 = wave_sum(loss2);
+                if (lane == 0 && live && !dead) acc[a.c_obj2] += loss2;
+            }
             if (lane == 0 && live && !dead) acc[a.c_obj] += loss;
         } else {
 #pragma unroll
@@ -478,7 +565,9 @@ __global__ void __launch_bounds__(64 * JT_MAX_FPB) k_joints_bwd(JArgs a) {
         double s = 0.0;
         for (unsigned int blk = 0; blk < gridDim.x; ++blk)
             s += __hip_atomic_load(&a.part[(size_t)blk * C + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (c == a.c_obj) a.objs[9] += (float)s;
+        if (K2D && c == a.c_obj2) { if (a.target2d) a.objs[0] += (float)s; }
+        else if (K2D && c == a.c_obj) { if (a.target) a.objs[9] += (float)s; }
+        else if (c == a.c_obj) a.objs[9] += (float)s;
         else if (a.c_beta >= 0 && c >= a.c_beta && c < a.c_beta + a.in.nB_used) a.d_beta[c - a.c_beta] = (float)s;
         else if (a.c_ls >= 0 && c >= a.c_ls && c < a.c_ls + 3 * J) a.d_logscale[c - a.c_ls] = (float)s;
         else if (a.c_bt >= 0 && c >= a.c_bt && c < a.c_bt + 3 * J) a.d_btrans[c - a.c_bt] = (float)s;
@@ -523,24 +612,27 @@ static int launch_joints(K kern, const JArgs &a, size_t wave_bytes, size_t block
     return SMIL_OK;
 }
 
-static int joints_grid(const SmilJointTables *t, const SmilJointsInputs *in, int C) {
-    const size_t wave = bwd_wave_doubles(t->J, C) * sizeof(double), block = align256((size_t)t->J * sizeof(int));
+// extra LDS of the 2-D term's cameras (bytes): per wave when a table has a row per image, else once per block
+struct CamLds { size_t wave = 0, block = 0; };
+static int joints_grid(const SmilJointTables *t, const SmilJointsInputs *in, int C, const CamLds &cl = CamLds()) {
+    const size_t wave = bwd_wave_doubles(t->J, C) * sizeof(double) + cl.wave, block = align256((size_t)t->J * sizeof(int)) + cl.block;
     return std::min(ceil_div(in->B, frames_per_block(wave, block)), JT_MAX_BLOCKS);
 }
 
 // columns of the rows that hold the sums over frames
-struct SumColumns { int C = 0, c_obj = -1, c_beta = -1, c_ls = -1, c_bt = -1; };
-static SumColumns sum_columns(const SmilJointTables *t, const SmilJointsInputs *in, bool obj, bool beta, bool ls, bool bt) {
+struct SumColumns { int C = 0, c_obj = -1, c_obj2 = -1, c_beta = -1, c_ls = -1, c_bt = -1; };
+static SumColumns sum_columns(const SmilJointTables *t, const SmilJointsInputs *in, bool obj, bool beta, bool ls, bool bt, bool obj2 = false) {
     SumColumns s;
     if (obj) { s.c_obj = s.C; s.C += 1; }
+    if (obj2) { s.c_obj2 = s.C; s.C += 1; }
     if (beta && in->shared_beta && in->nB_used > 0) { s.c_beta = s.C; s.C += in->nB_used; }
     if (ls && in->logscale_shared) { s.c_ls = s.C; s.C += 3 * t->J; }
     if (bt && in->btrans_shared) { s.c_bt = s.C; s.C += 3 * t->J; }
     return s;
 }
-static size_t sums_workspace(const SmilJointTables *t, const SmilJointsInputs *in, const SumColumns &s) {
+static size_t sums_workspace(const SmilJointTables *t, const SmilJointsInputs *in, const SumColumns &s, const CamLds &cl = CamLds()) {
     if (s.C == 0) return 0;
-    return 256 + align256((size_t)joints_grid(t, in, s.C) * s.C * sizeof(double));  // [counter | rows]
+    return 256 + align256((size_t)joints_grid(t, in, s.C, cl) * s.C * sizeof(double));  // [counter | rows]
 }
 
 extern "C" int smil_joints_forward(const SmilJointTables *t, const SmilJointsInputs *in, float *joints, float *new_J, void *stream_) {
@@ -559,19 +651,20 @@ extern "C" int smil_joints_forward(const SmilJointTables *t, const SmilJointsInp
     return launch_joints(k_joints_fwd<4>, a, wave, 0, s);
 }
 
-template <bool FUSED>
-static int launch_bwd(JArgs &a, const SumColumns &sc, void *workspace, hipStream_t s) {
-    a.C = sc.C; a.c_obj = sc.c_obj; a.c_beta = sc.c_beta; a.c_ls = sc.c_ls; a.c_bt = sc.c_bt;
+template <bool FUSED, bool K2D = false>
+static int launch_bwd(JArgs &a, const SumColumns &sc, void *workspace, hipStream_t s, const CamLds &cl = CamLds()) {
+    a.C = sc.C; a.c_obj = sc.c_obj; a.c_obj2 = sc.c_obj2; a.c_beta = sc.c_beta; a.c_ls = sc.c_ls; a.c_bt = sc.c_bt;
     if (sc.C) {
         a.counter = (unsigned int *)workspace;
         a.part = (double *)((char *)workspace + 256);
     }
     const int J = a.t.J;
-    const size_t wave = bwd_wave_doubles(J, sc.C) * sizeof(double), block = align256((size_t)J * sizeof(int));
-    if (J <= WAVE) return launch_joints(k_joints_bwd<1, FUSED>, a, wave, block, s);
-    if (J <= 2 * WAVE) return launch_joints(k_joints_bwd<2, FUSED>, a, wave, block, s);
-    if (J <= 3 * WAVE) return launch_joints(k_joints_bwd<3, FUSED>, a, wave, block, s);
-    return launch_joints(k_joints_bwd<4, FUSED>, a, wave, block, s);
+    const size_t wave = bwd_wave_doubles(J, sc.C) * sizeof(double) + cl.wave, block = align256((size_t)J * sizeof(int)) + cl.block;
+    a.cam_wave = (int)(cl.wave / sizeof(double)); a.cam_block = (int)(align256((size_t)J * sizeof(int)) / sizeof(double));
+    if (J <= WAVE) return launch_joints(k_joints_bwd<1, FUSED, K2D>, a, wave, block, s);
+    if (J <= 2 * WAVE) return launch_joints(k_joints_bwd<2, FUSED, K2D>, a, wave, block, s);
+    if (J <= 3 * WAVE) return launch_joints(k_joints_bwd<3, FUSED, K2D>, a, wave, block, s);
+    return launch_joints(k_joints_bwd<4, FUSED, K2D>, a, wave, block, s);
 }
 
 extern "C" size_t smil_joints_backward_workspace_bytes(const SmilJointTables *t, const SmilJointsInputs *in, const SmilJointsGrads *g) {
@@ -622,6 +715,72 @@ extern "C" int smil_kp3d_fit_eval(const SmilFitConfig *cfg, double w_k3d, double
     a.cfg = *cfg; a.w_k3d = w_k3d; a.sigma = robust_scale;
     a.Jc = Jc; a.canon = canon; a.target = target; a.vis = visibility; a.wj = joint_weights; a.objs = objs;
     return launch_bwd<true>(a, sc, workspace, (hipStream_t)stream_);
+}
+
+// ---- the multi-view 2-D keypoint term (with the 3-D term optionally beside it) ----
+static int check_kp2d_cameras(const SmilCameras *cam, int N, CamLds *cl) {
+    SMIL_REQUIRE(cam && cam->R && cam->T && cam->fov, "smil_kp2d_fit_eval: a camera table is missing");
+    SMIL_REQUIRE(cam->views >= 1 && cam->views <= K2D_MAX_VIEWS, "smil_kp2d_fit_eval: views=%d outside 1..%d", cam->views, K2D_MAX_VIEWS);
+    SMIL_REQUIRE((long long)cam->N == (long long)N * cam->views, "smil_kp2d_fit_eval: cameras hold N=%d images, expected %d frames x %d views",
+                 cam->N, N, cam->views);
+    SMIL_REQUIRE(cam->S >= 1, "smil_kp2d_fit_eval: S=%d", cam->S);
+    const int rows[5] = {cam->nR, cam->nT, cam->nFov, cam->aspect ? cam->nAspect : 1, cam->principal ? cam->nPrincipal : 1};
+    const char *names[5] = {"R", "T", "fov", "aspect", "principal"};
+    bool per_frame = false;
+    for (int k = 0; k < 5; ++k) {
+        SMIL_REQUIRE(rows[k] == 1 || rows[k] == cam->views || rows[k] == cam->N,
+                     "smil_kp2d_fit_eval: camera table %s has %d rows; expected 1, views=%d or N*views=%d", names[k], rows[k], cam->views, cam->N);
+        per_frame = per_frame || rows[k] > cam->views;
+    }
+    const size_t bytes = (size_t)cam->views * K2D_CAM * sizeof(double);
+    *cl = CamLds();
+    if (per_frame) cl->wave = bytes; else cl->block = bytes;
+    return SMIL_OK;
+}
+
+extern "C" size_t smil_kp2d_fit_eval_workspace_bytes(const SmilJointTables *t, const SmilJointsInputs *in, const SmilCameras *cam,
+                                                     int32_t want_betas, int32_t want_logscale, int32_t want_btrans) {
+    if (!t || !in || !cam || t->J < 1 || in->B < 1) return 0;
+    CamLds cl;
+    if (check_kp2d_cameras(cam, in->B, &cl)) return 0;
+    return sums_workspace(t, in, sum_columns(t, in, true, want_betas != 0, want_logscale != 0, want_btrans != 0, true), cl);
+}
+
+extern "C" int smil_kp2d_fit_eval(const SmilFitConfig *cfg, double w_k2d, double robust_scale_px, const SmilJointTables *t,
+                                  const SmilJointsInputs *in, const SmilCameras *cam, int32_t Jc, const int32_t *canon,
+                                  const float *target2d, const uint8_t *visibility2d, const float *confidence, const double *joint_weights,
+                                  double w_k3d, double robust_scale, const float *target3d, const uint8_t *visibility3d, float *objs,
+                                  float *d_pose, float *d_trans, float *d_betas, float *d_logscale, float *d_btrans, float *joints_out,
+                                  float *yx_out, void *workspace, void *stream_) {
+    if (int rc = check_joint_args("smil_kp2d_fit_eval", t, in)) return rc;
+    SMIL_REQUIRE(cfg && objs && workspace, "smil_kp2d_fit_eval: null argument");
+    SMIL_REQUIRE(cfg->N == in->B && cfg->J == t->J, "smil_kp2d_fit_eval: cfg holds N=%d J=%d, the inputs B=%d J=%d", cfg->N, cfg->J, in->B, t->J);
+    SMIL_REQUIRE(cfg->frame0 >= 0 && cfg->N_total >= cfg->frame0 + cfg->N, "smil_kp2d_fit_eval: bad frame range");
+    SMIL_REQUIRE(Jc >= 1, "smil_kp2d_fit_eval: Jc=%d", Jc);
+    SMIL_REQUIRE(canon || Jc <= t->J, "smil_kp2d_fit_eval: Jc=%d above J=%d without a canon list", Jc, t->J);
+    SMIL_REQUIRE(in->trans_after_joints == 1, "smil_kp2d_fit_eval: the term is defined on the fitter convention (trans_after_joints = 1)");
+    SMIL_REQUIRE(std::isfinite(w_k2d) && w_k2d >= 0.0 && std::isfinite(robust_scale_px) && robust_scale_px >= 0.0 && std::isfinite(w_k3d) &&
+                 w_k3d >= 0.0 && std::isfinite(robust_scale) && robust_scale >= 0.0,
+                 "smil_kp2d_fit_eval: w_k2d=%g robust_scale_px=%g w_k3d=%g robust_scale=%g must be finite and not negative", w_k2d,
+                 robust_scale_px, w_k3d, robust_scale);
+    CamLds cl;
+    if (int rc = check_kp2d_cameras(cam, cfg->N, &cl)) return rc;
+    const bool has2d = target2d && w_k2d > 0.0, has3d = target3d && w_k3d > 0.0;
+    SMIL_REQUIRE(has2d || has3d, "smil_kp2d_fit_eval: neither term is asked for (w_k2d=%g with%s 2-D targets, w_k3d=%g with%s 3-D targets)",
+                 w_k2d, target2d ? "" : "out", w_k3d, target3d ? "" : "out");
+    const SumColumns sc = sum_columns(t, in, true, d_betas != nullptr, d_logscale != nullptr, d_btrans != nullptr, true);
+    JArgs a = {};
+    a.t = *t; a.in = *in;
+    a.use_scale = in->logscale && in->allow_limb_scaling;
+    a.joints = joints_out;
+    a.d_beta = in->nB_used > 0 ? d_betas : nullptr;
+    a.d_theta = d_pose; a.d_trans = d_trans; a.d_logscale = d_logscale; a.d_btrans = d_btrans;
+    a.cfg = *cfg; a.w_k3d = w_k3d; a.sigma = robust_scale;
+    a.Jc = Jc; a.canon = canon; a.wj = joint_weights; a.objs = objs;
+    a.target = has3d ? target3d : nullptr; a.vis = visibility3d;
+    a.w_k2d = w_k2d; a.sigma_px = robust_scale_px; a.cam = *cam;
+    a.target2d = has2d ? target2d : nullptr; a.vis2d = visibility2d; a.conf = confidence; a.yx_out = yx_out;
+    return launch_bwd<true, true>(a, sc, workspace, (hipStream_t)stream_, cl);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1640,6 +1640,49 @@ def kp3d_fit_eval(cfg: _lib.FitConfig, jt: DeviceJointTables, w_k3d: float, robu
                                       _stream()), "smil_kp3d_fit_eval")
 
 
+def kp2d_fit_eval(cfg: _lib.FitConfig, jt: DeviceJointTables, cams: CameraSet, w_k2d: float, robust_scale_px: float, canon, target2d,
+                  visibility2d, confidence, joint_weights, beta, theta, trans, logscale, btrans, theta_mask, objs, d_pose=None, d_trans=None,
+                  d_betas=None, d_logscale=None, d_btrans=None, joints_out=None, yx_out=None, w_k3d: float = 0.0, robust_scale: float = 0.0,
+                  target3d=None, visibility3d=None, **fl) -> None:
+    """smil_kp2d_fit_eval: ``cams`` a ``CameraSet`` of ``views`` views on S x S images (tables of 1, views or N*views rows); target2d
+    (N,Nv,Jc,2) float32 in (y,x), visibility2d (N,Nv,Jc) uint8 or None, confidence (N,Nv,Jc) float32 or None, joint_weights (Jc)
+    float64 or None, the optional 3-D term's target3d (N,Jc,3) / visibility3d (N,Jc) as in ``kp3d_fit_eval``.  objs[0] (and objs[9]) are
+    added to, the gradient tensors are overwritten with the RAW gradients, yx_out (N,Nv,Jc,2) with the projections."""
+    fl = dict(fl, trans_after_joints=True)
+    i = _joints_inputs(jt, beta, theta, trans, logscale, btrans, theta_mask, fl)
+    N, Nv = i.B, int(cams.views)
+    if target2d.dim() != 4:
+        raise ValueError(f"target2d must be (N,Nv,Jc,2), got {tuple(target2d.shape)}")
+    Jc = int(target2d.shape[2])
+    dev = jt.device
+
+    def want(name, t, shape, dtype):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev):
+            raise ValueError(f"{name} must be a contiguous {dtype} {shape} tensor on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+
+    want("target2d", target2d, (N, Nv, Jc, 2), torch.float32)
+    want("visibility2d", visibility2d, (N, Nv, Jc), torch.uint8)
+    want("confidence", confidence, (N, Nv, Jc), torch.float32)
+    want("canon", canon, (Jc,), torch.int32)
+    want("joint_weights", joint_weights, (Jc,), torch.float64)
+    want("target3d", target3d, (N, Jc, 3), torch.float32)
+    want("visibility3d", visibility3d, (N, Jc), torch.uint8)
+    want("yx_out", yx_out, (N, Nv, Jc, 2), torch.float32)
+    want("joints_out", joints_out, (N, jt.J, 3), torch.float32)
+    if canon is None and Jc > jt.J:
+        raise ValueError(f"Jc={Jc} above J={jt.J} without a canon list")
+    cam = cams.struct(N * Nv)
+    lib = _lib.load()
+    ws = jt.workspace(int(lib.smil_kp2d_fit_eval_workspace_bytes(ctypes.byref(jt.struct), ctypes.byref(i), ctypes.byref(cam),
+                                                                 int(d_betas is not None), int(d_logscale is not None),
+                                                                 int(d_btrans is not None))))
+    _lib.check(lib.smil_kp2d_fit_eval(ctypes.byref(cfg), float(w_k2d), float(robust_scale_px), ctypes.byref(jt.struct), ctypes.byref(i),
+                                      ctypes.byref(cam), Jc, _ptr(canon), _ptr(target2d), _ptr(visibility2d), _ptr(confidence),
+                                      _ptr(joint_weights), float(w_k3d), float(robust_scale), _ptr(target3d), _ptr(visibility3d), _ptr(objs),
+                                      _ptr(d_pose), _ptr(d_trans), _ptr(d_betas), _ptr(d_logscale), _ptr(d_btrans), _ptr(joints_out),
+                                      _ptr(yx_out), _ptr(ws), _stream()), "smil_kp2d_fit_eval")
+
+
 def adam_step_multi_bc64(items, beta1=0.5, beta2=0.999, eps=1e-8):
     """``adam_step_multi`` through smil_adam_step_multi_bc64: the bias corrections formed in double, as torch.optim.Adam forms them."""
     for k0 in range(0, len(items), _lib.ADAM_MAX_TENSORS):

@@ -1,0 +1,145 @@
+"""Times of one iteration of a multi-view 2-D keypoint fit, three ways, on the same cameras and targets:
+
+(a) ``KeypointFitter2D.fit_step`` (smil_kp2d_fit_eval + smil_prior_losses + smil_adam_step_multi_bc64, csrc/joints.hip);
+(b) the unfused composition the library offered before it: ``SMAL.joints`` + a float64 torch projection and term + autograd +
+    ``torch.optim.Adam`` (per-frame pose and translation, shared shape);
+(c) ``SMALFitter.fit_step`` with the stage-0 weights of the reference's schedule (joint 25 and temporal 500, everything else 0), which
+    skins every vertex of every frame to regress the joints.
+
+Rows: STICK at 1 and 4 views, the mouse at 18 views, at every ``--sizes`` frame count (a path that runs out of memory at a size is
+recorded as such).  Needs a GPU; writes profiles/kp2d_probe.json (``--out``).  Method (tools/joints_probe.py): every path is warmed up at
+every size; a window is as many back-to-back calls as fill ``--window-ms`` (2 to 500, sized from a first window of 2) between two
+device events, ended by a synchronise; the paths' windows ALTERNATE, ``--windows`` of each; median, min and max of the per-call time
+are recorded, and the peak memory one call of (a) and of (c) allocates beyond what is resident (``resident_mb``: both fitters).  The times are those of the whole Python call.
+
+    python3 tools/kp2d_probe.py
+"""
+import argparse
+import json
+import math
+import os
+import statistics
+import sys
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+from smilify_amd import _lib, model_io  # noqa: E402
+from smilify_amd.cameras import look_at_view_transform  # noqa: E402
+from smilify_amd.config import FitterConfig  # noqa: E402
+from smilify_amd.fit_keypoints2d import KeypointFitter2D  # noqa: E402
+from smilify_amd.fitter import SMALFitter  # noqa: E402
+from smilify_amd.smal_torch import SMAL  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--out", default=os.path.join(REPO, "profiles", "kp2d_probe.json"))
+ap.add_argument("--window-ms", type=float, default=300.0)
+ap.add_argument("--windows", type=int, default=5)
+ap.add_argument("--warmup", type=int, default=3)
+ap.add_argument("--sizes", type=int, nargs="*", default=[4096, 32768])
+ap.add_argument("--image-size", type=int, default=64)
+args = ap.parse_args()
+dev = torch.device("cuda:0")
+SHAPES = [("stick", "SMILy_STICK.npz", 1), ("stick", "SMILy_STICK.npz", 4), ("mouse", "SMILy_Mouse_static_joints.npz", 18)]
+W_JOINT, W_TEMP, WINDOW, LR = 25.0, 500.0, 10, 5e-3
+
+
+def window(fn, calls):
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ev[0].record()
+    for _ in range(calls):
+        fn()
+    ev[1].record()
+    torch.cuda.synchronize()
+    return ev[0].elapsed_time(ev[1]) / calls
+
+
+def compare(row, paths):
+    for fn in paths.values():
+        for _ in range(args.warmup):
+            fn()
+    torch.cuda.synchronize()
+    calls = {who: int(min(500, max(2, args.window_ms / max(window(fn, 2), 1e-6)))) for who, fn in paths.items()}
+    times = {who: [] for who in paths}
+    for _ in range(args.windows):
+        for who, fn in paths.items():
+            times[who].append(window(fn, calls[who]))
+    for who, t in times.items():
+        row[f"{who}_ms"], row[f"{who}_ms_min"], row[f"{who}_ms_max"], row[f"{who}_calls"] = statistics.median(t), min(t), max(t), calls[who]
+    return row
+
+
+def peak_mb(fn):
+    """Peak allocated memory of one call beyond what is resident before it (both fitters, their targets and Adam states)."""
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    fn()
+    torch.cuda.synchronize()
+    return (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+
+
+rows = []
+for name, file, views in SHAPES:
+    t = model_io.load_model(os.path.join(REPO, "data", "models", file))
+    J, S = t.J, args.image_size
+    for N in args.sizes:
+        row = dict(model=name, J=J, V=t.V, views=views, N=N, S=S)
+        try:
+            g = torch.Generator().manual_seed(1)
+            R, T = look_at_view_transform([4.0] * views, [12.0] * views, [360.0 * v / views for v in range(views)])
+            fov = torch.full((views,), 40.0)
+            target = S / 2 + 0.2 * S * torch.randn(N, views, J, 2, generator=g)
+            canon = list(range(J))
+            a = KeypointFitter2D(dev, target, cameras=dict(R=R, T=T, fov=fov), image_size=S, tables=t, canonical_joints=canon)
+            a.begin_stage(LR)
+            n_img = N * views
+            data = (torch.zeros(n_img, 3, 1, 1), torch.zeros(n_img, 1, S, S, dtype=torch.uint8), target.reshape(n_img, J, 2),
+                    torch.ones(n_img, J, dtype=torch.long))
+            c = SMALFitter(dev, data, N, -1, False, tables=t, config=FitterConfig.from_tables(t, WINDOW_SIZE=WINDOW), views=views)
+            c.set_cameras(R, T, fov=fov)
+            c.fov.requires_grad = False
+            c.begin_stage(LR)
+            smal = SMAL(dev, tables=t)
+            p_beta = torch.zeros(1, t.nB, device=dev, requires_grad=True)
+            p_theta, p_trans = a._pose.clone().requires_grad_(), torch.zeros(N, 3, device=dev, requires_grad=True)
+            opt = torch.optim.Adam([p_beta, p_theta, p_trans], lr=LR, betas=(0.5, 0.999))
+            R64, T64, tgt64 = R.double().to(dev), T.double().to(dev), target.double().to(dev)
+            k11 = 1.0 / math.tan(math.radians(40.0) / 2)
+            bw = torch.full((N, 1, 1), float(WINDOW), dtype=torch.float64, device=dev)
+            bw[(N // WINDOW) * WINDOW:] = max(N % WINDOW, 1)
+
+            def step_a():
+                return a.fit_step(W_JOINT, w_temp=W_TEMP, window=WINDOW)
+
+            def step_b():
+                opt.zero_grad(set_to_none=False)
+                j = smal.joints(p_beta, p_theta, None).double() + p_trans.double()[:, None]
+                view = torch.einsum("njk,vkl->nvjl", j, R64) + T64[None, :, None]
+                ndc = view[..., :2] * k11 / view[..., 2:]
+                yx = S / 2 - (S / 2) * ndc.flip(-1)
+                (W_JOINT * (((yx - tgt64) ** 2).sum(-1) / (2.0 * J * views * bw)).sum()).backward()
+                opt.step()
+
+            def step_c():
+                return c.fit_step((W_JOINT, 0.0, 0.0, 0.0, 0.0, 0.0), W_TEMP, window=WINDOW)
+
+            compare(row, {"fitter2d": step_a, "unfused": step_b, "smalfitter": step_c})
+            row["fitter2d_peak_mb"], row["smalfitter_peak_mb"] = peak_mb(step_a), peak_mb(step_c)
+            row["resident_mb"] = torch.cuda.memory_allocated() / 2 ** 20
+            row["smalfitter_over_fitter2d"] = row["smalfitter_ms"] / row["fitter2d_ms"]
+            row["unfused_over_fitter2d"] = row["unfused_ms"] / row["fitter2d_ms"]
+        except torch.cuda.OutOfMemoryError as e:
+            row["out_of_memory"] = str(e).splitlines()[0]
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+        a = c = smal = opt = p_theta = p_trans = data = target = tgt64 = None
+        torch.cuda.empty_cache()
+
+result = dict(device=torch.cuda.get_device_name(0), library=_lib.load().smil_version().decode(), window_ms=args.window_ms, windows=args.windows,
+              warmup=args.warmup, rows=rows)
+os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+with open(args.out, "w") as f:
+    json.dump(result, f, indent=1)
+print(f"wrote {args.out}")
