@@ -915,7 +915,7 @@ int smil_align_errors(const void *pred, const void *target, const uint8_t *mask,
  * translation column of the kinematic chain (J_transformed); a regressor model's are sum_k A_k m[j,k] over the (joint, bone) pairs
  * with a non-zero weight product, with the moments m = M0 + sum_b beta_b MB_b and the rest joints J_rest = J0 + sum_b beta_b JB_b
  * affine in the shape.  One wavefront per frame; all arithmetic is float64 on float32 parameters and every output is rounded once.
- * The semantics of the chain are those of smil_lbs_forward (Rodrigues with |theta + 1e-8|, the root's rotation-only rule, the y flip of
+ * The semantics of the chain are those of smil_lbs_forward, stated in csrc/chain.h (Rodrigues with |theta + 1e-8|, the root's rotation-only rule, the y flip of
  * betas_trans, propagate_scaling, allow_limb_scaling, theta_mask).  No float atomics: two calls on the same inputs return the same
  * bits, the sums over frames of the shared tables' gradients included.
  * ---------------------------------------------------------------------------------------- */
@@ -1042,7 +1042,7 @@ int smil_kp2d_fit_eval(const SmilFitConfig *cfg, double w_k2d, double robust_sca
  * lr / (1 - beta1^step) likewise.  smil_adam_step_multi forms 1 - beta2^step in float32, which is up to 1e-5 off in its square root
  * for small step counts: every update is then that fraction of lr off, whatever the parameter's magnitude (2e-7 after five steps at
  * lr = 5e-3) - more than the rounding of parameters well below 1, which KeypointFitter3D's are.  Everything else is the float32
- * arithmetic of smil_adam_step_multi (csrc/joints.hip). */
+ * arithmetic of smil_adam_step_multi (csrc/fit.hip). */
 int smil_adam_step_multi_bc64(const SmilAdamTensor *tensors, int32_t count, double beta1, double beta2, float eps, void *stream);
 
 #ifdef __cplusplus

@@ -126,6 +126,14 @@ static inline int smil_check_f_scale(const char *who, double f_scale) {
 // x cam->views views (a negative count fails: the caller's own argument was missing)
 int check_cameras(const SmilCameras *cam, const char *who, int frames = 0);
 
+// frames of the window that holds local frame `local_frame` (the last one may be short): a frame's loss terms are divided by it
+__device__ __forceinline__ int window_size_of(const SmilFitConfig &c, int local_frame) {
+    const int gi = c.frame0 + local_frame;
+    const int w = c.window > 0 ? c.window : c.N_total;
+    const int start = (gi / w) * w;
+    return min(w, c.N_total - start);
+}
+
 // ---- caller-owned workspaces: every region starts on a 256-byte boundary ----
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 

@@ -6,13 +6,6 @@
 // window mean" (optimize_to_joints.py:154-157): a frame's terms are divided by the size of ITS window.
 #include "common.h"
 
-__device__ __forceinline__ int window_size_of(const SmilFitConfig &c, int local_frame) {
-    const int gi = c.frame0 + local_frame;
-    const int w = c.window > 0 ? c.window : c.N_total;
-    const int start = (gi / w) * w;
-    return min(w, c.N_total - start);
-}
-
 // element e of frame i: [0,3) global rotation, [3,3J) joint rotations, [3J,3J+3) translation.
 // pose is the combined (N,J,3) parameter buffer, mask the combined (J,3) mask.
 __device__ __forceinline__ void prior_losses_body(const SmilFitConfig &c, const float *__restrict__ pose,
@@ -445,17 +438,22 @@ extern "C" int smil_image_abs_sum(const void *images, int32_t is_u8, int32_t N, 
 // the bias corrections are float32, as before.
 static float one_minus(double beta) { return (float)(1.0 - beta); }
 
+// element i of one step; step_size = lr / (1 - beta1^step), bc2_sqrt = sqrt(1 - beta2^step)
+__device__ __forceinline__ void adam_update(float *p, const float *g, float *m, float *v, long long i, float step_size, float b2,
+                                            float omb1, float omb2, float bc2_sqrt, float eps) {
+    const float gi = g[i];
+    const float mi = m[i] + (gi - m[i]) * omb1;     // exp_avg.lerp_(grad, 1 - beta1)
+    const float vi = v[i] * b2 + omb2 * gi * gi;     // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+    m[i] = mi; v[i] = vi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    p[i] = p[i] - step_size * (mi / denom);          // param.addcdiv_(exp_avg, denom, value=-step_size)
+}
+
 __global__ void __launch_bounds__(256) k_adam(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
                                               float *__restrict__ v, long long n, float lr, float b1, float b2, float eps,
                                               float omb1, float omb2, float bc1, float bc2_sqrt) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float gi = g[i];
-        const float mi = m[i] + (gi - m[i]) * omb1;     // exp_avg.lerp_(grad, 1 - beta1)
-        const float vi = v[i] * b2 + omb2 * gi * gi;     // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-        m[i] = mi; v[i] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = p[i] - (lr / bc1) * (mi / denom);
-    }
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        adam_update(p, g, m, v, i, lr / bc1, b2, omb1, omb2, bc2_sqrt, eps);
 }
 
 struct AdamMulti {
@@ -466,34 +464,75 @@ struct AdamMulti {
 __global__ void __launch_bounds__(256) k_adam_multi(AdamMulti a, float b1, float b2, float eps, float omb1, float omb2) {
     const SmilAdamTensor &t = a.t[blockIdx.y];
     const float bc1 = a.bc1[blockIdx.y], bc2_sqrt = a.bc2_sqrt[blockIdx.y], lr = t.lr;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < t.n; i += (long long)gridDim.x * blockDim.x) {
-        const float gi = t.grad[i];
-        const float mi = t.exp_avg[i] + (gi - t.exp_avg[i]) * omb1;
-        const float vi = t.exp_avg_sq[i] * b2 + omb2 * gi * gi;
-        t.exp_avg[i] = mi; t.exp_avg_sq[i] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        t.param[i] = t.param[i] - (lr / bc1) * (mi / denom);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < t.n; i += (long long)gridDim.x * blockDim.x)
+        adam_update(t.param, t.grad, t.exp_avg, t.exp_avg_sq, i, lr / bc1, b2, omb1, omb2, bc2_sqrt, eps);
+}
+
+// The step of the keypoint fitters (fit_keypoints_base.py): k_adam_multi with the bias corrections formed in double, as
+// torch.optim.Adam forms them.  The float32 1.0f - powf(0.999f, step) above is up to 2e-5 off for small step counts (1e-5 in its
+// square root), and an Adam update has the size of lr: every parameter then drifts by that fraction of lr per step whatever its
+// magnitude - 1.9e-7 after five steps at lr = 5e-3, several times the rounding of the fitter's parameters (0.02 .. 0.4).
+struct AdamMultiBc {
+    SmilAdamTensor t[SMIL_ADAM_MAX_TENSORS];
+    float step_size[SMIL_ADAM_MAX_TENSORS], bc2_sqrt[SMIL_ADAM_MAX_TENSORS];
+};
+
+__global__ void __launch_bounds__(256) k_adam_multi_bc64(AdamMultiBc a, float b2, float eps, float omb1, float omb2) {
+    const SmilAdamTensor &t = a.t[blockIdx.y];
+    const float step_size = a.step_size[blockIdx.y], bc2_sqrt = a.bc2_sqrt[blockIdx.y];
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < t.n; i += (long long)gridDim.x * blockDim.x)
+        adam_update(t.param, t.grad, t.exp_avg, t.exp_avg_sq, i, step_size, b2, omb1, omb2, bc2_sqrt, eps);
+}
+
+// what the two multi-tensor steps share: the checks of the list and of its tensors, and the grid's width for the longest of them
+static int check_adam_count(const char *who, const SmilAdamTensor *tensors, int32_t count) {
+    SMIL_REQUIRE(tensors && count > 0 && count <= SMIL_ADAM_MAX_TENSORS, "%s: count=%d outside 1..%d", who, count, SMIL_ADAM_MAX_TENSORS);
+    return SMIL_OK;
+}
+static int check_adam_tensors(const char *who, const SmilAdamTensor *tensors, int32_t count, int *gx) {
+    long long n_max = 0;
+    for (int k = 0; k < count; ++k) {
+        const SmilAdamTensor &t = tensors[k];
+        SMIL_REQUIRE(t.param && t.grad && t.exp_avg && t.exp_avg_sq && t.n > 0 && t.step > 0, "%s: bad tensor %d", who, k);
+        n_max = std::max<long long>(n_max, t.n);
     }
+    *gx = (int)std::min<long long>(512, (n_max + 255) / 256);
+    return SMIL_OK;
 }
 
 extern "C" int smil_adam_step_multi(const SmilAdamTensor *tensors, int32_t count, double beta1_, double beta2_, float eps,
                                     void *stream_) {
     const float beta1 = (float)beta1_, beta2 = (float)beta2_;
-    SMIL_REQUIRE(tensors && count > 0 && count <= SMIL_ADAM_MAX_TENSORS, "smil_adam_step_multi: count=%d outside 1..%d", count,
-                 SMIL_ADAM_MAX_TENSORS);
     AdamMulti a;
-    long long n_max = 0;
+    int gx;
+    if (int rc = check_adam_count("smil_adam_step_multi", tensors, count)) return rc;
+    if (int rc = check_adam_tensors("smil_adam_step_multi", tensors, count, &gx)) return rc;
     for (int k = 0; k < count; ++k) {
-        const SmilAdamTensor &t = tensors[k];
-        SMIL_REQUIRE(t.param && t.grad && t.exp_avg && t.exp_avg_sq && t.n > 0 && t.step > 0, "smil_adam_step_multi: bad tensor %d", k);
-        a.t[k] = t;
-        a.bc1[k] = 1.0f - powf(beta1, (float)t.step);
-        a.bc2_sqrt[k] = sqrtf(1.0f - powf(beta2, (float)t.step));
-        n_max = std::max<long long>(n_max, t.n);
+        a.t[k] = tensors[k];
+        a.bc1[k] = 1.0f - powf(beta1, (float)tensors[k].step);
+        a.bc2_sqrt[k] = sqrtf(1.0f - powf(beta2, (float)tensors[k].step));
     }
-    const int gx = (int)std::min<long long>(512, (n_max + 255) / 256);
     hipLaunchKernelGGL(k_adam_multi, dim3(gx, count), dim3(256), 0, (hipStream_t)stream_, a, beta1, beta2, eps, one_minus(beta1_),
                        one_minus(beta2_));
+    SMIL_LAUNCH_CHECK();
+    return SMIL_OK;
+}
+
+extern "C" int smil_adam_step_multi_bc64(const SmilAdamTensor *tensors, int32_t count, double beta1, double beta2, float eps,
+                                         void *stream_) {
+    AdamMultiBc a;
+    int gx;
+    if (int rc = check_adam_count("smil_adam_step_multi_bc64", tensors, count)) return rc;
+    SMIL_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "smil_adam_step_multi_bc64: betas %g, %g outside [0, 1)", beta1,
+                 beta2);
+    if (int rc = check_adam_tensors("smil_adam_step_multi_bc64", tensors, count, &gx)) return rc;
+    for (int k = 0; k < count; ++k) {
+        a.t[k] = tensors[k];
+        a.step_size[k] = (float)((double)tensors[k].lr / (1.0 - std::pow(beta1, (double)tensors[k].step)));
+        a.bc2_sqrt[k] = (float)std::sqrt(1.0 - std::pow(beta2, (double)tensors[k].step));
+    }
+    hipLaunchKernelGGL(k_adam_multi_bc64, dim3(gx, count), dim3(256), 0, (hipStream_t)stream_, a, (float)beta2, eps, (float)(1.0 - beta1),
+                       (float)(1.0 - beta2));
     SMIL_LAUNCH_CHECK();
     return SMIL_OK;
 }
@@ -503,14 +542,8 @@ __global__ void __launch_bounds__(256) k_adam_dev(float *__restrict__ p, const f
                                                   float omb1, float omb2, const int *__restrict__ step_dev, int step_offset) {
     const float t = (float)(*step_dev - step_offset);
     const float bc1 = 1.0f - powf(b1, t), bc2_sqrt = sqrtf(1.0f - powf(b2, t));
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float gi = g[i];
-        const float mi = m[i] + (gi - m[i]) * omb1;
-        const float vi = v[i] * b2 + omb2 * gi * gi;
-        m[i] = mi; v[i] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = p[i] - (lr / bc1) * (mi / denom);
-    }
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        adam_update(p, g, m, v, i, lr / bc1, b2, omb1, omb2, bc2_sqrt, eps);
 }
 
 extern "C" int smil_adam_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr,

@@ -12,7 +12,9 @@
 // leaves what it owes its parent in its own LDS slot and the parent adds its children's slots in ascending order - no atomics.
 // Blocks loop over frames (at most JT_MAX_BLOCKS blocks); the sums over frames of the shared tables' gradients (and of the fused
 // term) are kept per wave in LDS in frame order, left as one row per block, and added in block order by the last block to finish.
-#include "common.h"
+#include <type_traits>
+
+#include "chain.h"
 
 #define JT_MAX_BLOCKS 1024
 #define JT_MAX_FPB 4   // frames (waves) per block at the most
@@ -53,41 +55,6 @@ struct LaneState {
     int dep[NJ], par[NJ];
     double R[NJ][9], S[NJ][3], IS[NJ][3], T[NJ][3], TH[NJ][3];
 };
-
-// batch_lbs.py:37-38: the norm is taken of theta + 1e-8, the axis uses the unshifted theta
-__device__ __forceinline__ void rodrigues_fwd64(const double th[3], double R[9]) {
-    const double ax = th[0] + 1e-8, ay = th[1] + 1e-8, az = th[2] + 1e-8;
-    const double angle = sqrt(ax * ax + ay * ay + az * az);
-    const double rx = th[0] / angle, ry = th[1] / angle, rz = th[2] / angle;
-    const double c = cos(angle), s = sin(angle), k = 1.0 - c;
-    R[0] = c + k * rx * rx;      R[1] = k * rx * ry - s * rz; R[2] = k * rx * rz + s * ry;
-    R[3] = k * ry * rx + s * rz; R[4] = c + k * ry * ry;      R[5] = k * ry * rz - s * rx;
-    R[6] = k * rz * rx - s * ry; R[7] = k * rz * ry + s * rx; R[8] = c + k * rz * rz;
-}
-
-// dR (3x3) -> dtheta for R = c I + (1-c) r r^T + s H(r), angle = |theta + eps|, r = theta / angle   (lbs.hip rodrigues_bwd in float64)
-__device__ __forceinline__ void rodrigues_bwd64(const double th[3], const double dR[9], double dth[3]) {
-    const double ax = th[0] + 1e-8, ay = th[1] + 1e-8, az = th[2] + 1e-8;
-    const double angle = sqrt(ax * ax + ay * ay + az * az);
-    const double inv = 1.0 / angle;
-    const double r[3] = {th[0] * inv, th[1] * inv, th[2] * inv};
-    const double c = cos(angle), s = sin(angle), k = 1.0 - c;
-    const double trace = dR[0] + dR[4] + dR[8];
-    double rdr = 0.0;
-    for (int m = 0; m < 3; ++m)
-        for (int n = 0; n < 3; ++n) rdr += dR[3 * m + n] * r[m] * r[n];
-    const double hx = dR[7] - dR[5], hy = dR[2] - dR[6], hz = dR[3] - dR[1];
-    const double dRH = r[0] * hx + r[1] * hy + r[2] * hz;
-    double dangle = -s * trace + s * rdr + c * dRH;
-    double dr[3];
-    dr[0] = k * ((dR[0] + dR[0]) * r[0] + (dR[1] + dR[3]) * r[1] + (dR[2] + dR[6]) * r[2]) + s * hx;
-    dr[1] = k * ((dR[3] + dR[1]) * r[0] + (dR[4] + dR[4]) * r[1] + (dR[5] + dR[7]) * r[2]) + s * hy;
-    dr[2] = k * ((dR[6] + dR[2]) * r[0] + (dR[7] + dR[5]) * r[1] + (dR[8] + dR[8]) * r[2]) + s * hz;
-    dangle -= (dr[0] * th[0] + dr[1] * th[1] + dr[2] * th[2]) * inv * inv;
-    dth[0] = dr[0] * inv + dangle * ax * inv;
-    dth[1] = dr[1] * inv + dangle * ay * inv;
-    dth[2] = dr[2] * inv + dangle * az * inv;
-}
 
 // the moment of pair p for this frame's shape: m[0..2] = M0 + sum_b beta_b MB_b, m[3] = M0[3]
 __device__ __forceinline__ void pair_moment(const JArgs &a, const float *__restrict__ beta, int p, double m[4]) {
@@ -130,7 +97,7 @@ __device__ __forceinline__ void chain_forward(const JArgs &a, int b, bool live, 
             const float *th = a.in.theta + ((size_t)b * J + j) * 3;
             const float *mk = a.in.theta_mask ? a.in.theta_mask + 3 * j : nullptr;
             for (int k = 0; k < 3; ++k) L.TH[q][k] = mk ? (double)th[k] * (double)mk[k] : (double)th[k];
-            rodrigues_fwd64(L.TH[q], L.R[q]);
+            rodrigues_fwd(L.TH[q], L.R[q]);
             const float *ls = a.use_scale ? a.in.logscale + (size_t)(a.in.logscale_shared ? 0 : b) * J * 3 : nullptr;
             if (ls)
                 for (int k = 0; k < 3; ++k) L.S[q][k] = exp((double)ls[3 * j + k]);
@@ -153,22 +120,12 @@ __device__ __forceinline__ void chain_forward(const JArgs &a, int b, bool live, 
             const int j = lane + WAVE * q;
             const double *R = L.R[q], *S = L.S[q], *isp = L.IS[q], *t = L.T[q];
             double G[12];
-            if (d == 0) {  // root: rotation only, own scale never applied (batch_lbs.py:151)
-                for (int m = 0; m < 3; ++m) {
-                    G[4 * m] = R[3 * m]; G[4 * m + 1] = R[3 * m + 1]; G[4 * m + 2] = R[3 * m + 2]; G[4 * m + 3] = sJ[3 * j + m];
-                }
+            if (d == 0) {
+                chain_root(R, sJ + 3 * j, G);
             } else {
                 double Lm[9];
-                for (int m = 0; m < 3; ++m)
-                    for (int n = 0; n < 3; ++n) Lm[3 * m + n] = (isp[m] * R[3 * m + n]) * S[n];
-                const double *P = sG + 12 * L.par[q];
-                for (int m = 0; m < 3; ++m) {
-                    const double p0 = P[4 * m], p1 = P[4 * m + 1], p2 = P[4 * m + 2], p3 = P[4 * m + 3];
-                    G[4 * m + 0] = p0 * Lm[0] + p1 * Lm[3] + p2 * Lm[6];
-                    G[4 * m + 1] = p0 * Lm[1] + p1 * Lm[4] + p2 * Lm[7];
-                    G[4 * m + 2] = p0 * Lm[2] + p1 * Lm[5] + p2 * Lm[8];
-                    G[4 * m + 3] = p0 * t[0] + p1 * t[1] + p2 * t[2] + p3;
-                }
+                chain_local(isp, R, S, Lm);
+                chain_compose(sG + 12 * L.par[q], Lm, t, G);
             }
             for (int i = 0; i < 12; ++i) sG[12 * j + i] = G[i];
         }
@@ -231,15 +188,9 @@ __global__ void __launch_bounds__(64 * JT_MAX_FPB) k_joints_fwd(JArgs a) {
     }
 }
 
-__device__ __forceinline__ int window_size_of(const SmilFitConfig &c, int local_frame) {  // as in fit.hip
-    const int gi = c.frame0 + local_frame;
-    const int w = c.window > 0 ? c.window : c.N_total;
-    const int start = (gi / w) * w;
-    return min(w, c.N_total - start);
-}
-
-// doubles of LDS a wave of the backward kernels needs
-__host__ __device__ static inline size_t bwd_wave_doubles(int J, int C) { return (size_t)J * 39 + (size_t)C; }
+// doubles of LDS a wave of the backward kernels needs: JT_BWD_ROW per joint (sG 12, sdG 12, 3 each of sJ sdJ sCt sCs sDJ), then its C sums
+#define JT_BWD_ROW 39
+__host__ __device__ static inline size_t bwd_wave_doubles(int J, int C) { return (size_t)J * JT_BWD_ROW + (size_t)C; }
 
 // A camera staged for the 2-D term: sixteen doubles, float64 arithmetic on the float32 tables (camera.h: X_view = X R + T,
 // k11 = 1 / tan(fov / 2), k00 = k11 / aspect, the principal point added after the division)
@@ -254,6 +205,18 @@ __device__ __forceinline__ void stage_camera64(double *row, const SmilCameras &c
     row[13] = k11;
     row[14] = c.principal ? (double)c.principal[2 * (size_t)(n % c.nPrincipal)] : 0.0;
     row[15] = c.principal ? (double)c.principal[2 * (size_t)(n % c.nPrincipal) + 1] : 0.0;
+}
+
+// A squared residual s of weight w into `loss`; returns the weight of its gradient.  sigma > 0: soft L1,
+// rho = 2 sigma^2 (u - 1) = 2 s / (u + 1), u = sqrt(1 + s / sigma^2), rho' = 1 / u; else the plain square.
+__device__ __forceinline__ double robust_sq(double s, double w, double sigma, double &loss) {
+    if (sigma > 0.0) {
+        const double u = sqrt(1.0 + s / (sigma * sigma));
+        loss += w * 2.0 * s / (u + 1.0);
+        return w / u;
+    }
+    loss += w * s;
+    return w;
 }
 
 // Backward of k_joints_fwd (FUSED false: d_joints from memory) and the fused keypoint evaluations (FUSED true: d_joints is the
@@ -322,14 +285,7 @@ __global__ void __launch_bounds__(64 * JT_MAX_FPB) k_joints_bwd(JArgs a) {
                     const double w = (a.wj ? a.wj[c] : 1.0) * scale;
                     const double r0 = pos[0] - (double)t0, r1 = pos[1] - (double)t1, r2 = pos[2] - (double)t2;
                     const double s = r0 * r0 + r1 * r1 + r2 * r2;
-                    double g = w;
-                    if (a.sigma > 0.0) {  // rho = 2 sigma^2 (u - 1) = 2 s / (u + 1), u = sqrt(1 + s / sigma^2); rho' = 1 / u
-                        const double u = sqrt(1.0 + s / (a.sigma * a.sigma));
-                        loss += w * 2.0 * s / (u + 1.0);
-                        g = w / u;
-                    } else {
-                        loss += w * s;
-                    }
+                    const double g = robust_sq(s, w, a.sigma, loss);
                     dj[0] += 2.0 * g * r0; dj[1] += 2.0 * g * r1; dj[2] += 2.0 * g * r2;
                     nvis += 1.0;
                 }
@@ -362,14 +318,7 @@ __global__ void __launch_bounds__(64 * JT_MAX_FPB) k_joints_bwd(JArgs a) {
                             const double w = wc * (double)cf;
                             const double ry = ys - (double)ty, rx = xs - (double)tx;
                             const double s = ry * ry + rx * rx;
-                            double g = w;
-                            if (a.sigma_px > 0.0) {
-                                const double u = sqrt(1.0 + s / (a.sigma_px * a.sigma_px));
-                                loss2 += w * 2.0 * s / (u + 1.0);
-                                g = w / u;
-                            } else {
-                                loss2 += w * s;
-                            }
+                            const double g = robust_sq(s, w, a.sigma_px, loss2);
                             // d y_s = 2 g ry, d x_s = 2 g rx ; y_s = hS - hS y_ndc ; then camera_project_bwd's chain in float64
                             const double dyn = -hS * 2.0 * g * ry, dxn = -hS * 2.0 * g * rx;
                             const double dvx = dxn * cm[12] * iz, dvy = dyn * cm[13] * iz, dvz = -(xn * dxn + yn * dyn) * iz;
@@ -482,7 +431,7 @@ __global__ void __launch_bounds__(64 * JT_MAX_FPB) k_joints_bwd(JArgs a) {
                 for (int k = 0; k < 3; ++k) sdJ[3 * j + k] = dJ[k];
                 if (a.d_theta) {
                     double dth[3];
-                    rodrigues_bwd64(L.TH[q], dR, dth);
+                    rodrigues_bwd(L.TH[q], dR, dth);
                     for (int k = 0; k < 3; ++k) a.d_theta[o * 3 + k] = dead ? 0.f : (float)dth[k];
                 }
                 if (a.d_logscale) {
@@ -550,7 +499,7 @@ __global__ void __launch_bounds__(64 * JT_MAX_FPB) k_joints_bwd(JArgs a) {
     if (C == 0) return;  // (uniform)
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
         double s = 0.0;
-        for (int w = 0; w < fpb; ++w) s += smem64[(size_t)w * per_wave + (size_t)J * 39 + c];
+        for (int w = 0; w < fpb; ++w) s += smem64[(size_t)w * per_wave + (size_t)J * JT_BWD_ROW + c];
         __hip_atomic_store(&a.part[(size_t)blockIdx.x * C + c], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();
@@ -612,11 +561,25 @@ static int launch_joints(K kern, const JArgs &a, size_t wave_bytes, size_t block
     return SMIL_OK;
 }
 
-// extra LDS of the 2-D term's cameras (bytes): per wave when a table has a row per image, else once per block
+// f(std::integral_constant<int, NJ>) for the joints per lane that J asks for
+template <class F>
+static int dispatch_nj(int J, F f) {
+    if (J <= WAVE) return f(std::integral_constant<int, 1>());
+    if (J <= 2 * WAVE) return f(std::integral_constant<int, 2>());
+    if (J <= 3 * WAVE) return f(std::integral_constant<int, 3>());
+    return f(std::integral_constant<int, 4>());
+}
+
+// bytes of LDS: the 2-D term's cameras (per wave when a table has a row per image, else once per block), and a backward kernel's in all
 struct CamLds { size_t wave = 0, block = 0; };
+struct BwdLdsBytes { size_t wave, block, child; };
+static BwdLdsBytes bwd_lds_bytes(int J, int C, const CamLds &cl) {
+    const size_t child = align256((size_t)J * sizeof(int));
+    return {bwd_wave_doubles(J, C) * sizeof(double) + cl.wave, child + cl.block, child};
+}
 static int joints_grid(const SmilJointTables *t, const SmilJointsInputs *in, int C, const CamLds &cl = CamLds()) {
-    const size_t wave = bwd_wave_doubles(t->J, C) * sizeof(double) + cl.wave, block = align256((size_t)t->J * sizeof(int)) + cl.block;
-    return std::min(ceil_div(in->B, frames_per_block(wave, block)), JT_MAX_BLOCKS);
+    const BwdLdsBytes lb = bwd_lds_bytes(t->J, C, cl);
+    return std::min(ceil_div(in->B, frames_per_block(lb.wave, lb.block)), JT_MAX_BLOCKS);
 }
 
 // columns of the rows that hold the sums over frames
@@ -635,20 +598,21 @@ static size_t sums_workspace(const SmilJointTables *t, const SmilJointsInputs *i
     return 256 + align256((size_t)joints_grid(t, in, s.C, cl) * s.C * sizeof(double));  // [counter | rows]
 }
 
+// what every entry point sets of the kernels' arguments
+static void joint_args(const SmilJointTables *t, const SmilJointsInputs *in, JArgs &a) {
+    a = {};
+    a.t = *t; a.in = *in;
+    a.use_scale = in->logscale && in->allow_limb_scaling;
+}
+
 extern "C" int smil_joints_forward(const SmilJointTables *t, const SmilJointsInputs *in, float *joints, float *new_J, void *stream_) {
     if (int rc = check_joint_args("smil_joints_forward", t, in)) return rc;
     SMIL_REQUIRE(joints, "smil_joints_forward: joints is missing");
-    JArgs a = {};
-    a.t = *t; a.in = *in;
-    a.use_scale = in->logscale && in->allow_limb_scaling;
+    JArgs a;
+    joint_args(t, in, a);
     a.joints = joints; a.new_J = new_J;
     const size_t wave = (size_t)t->J * 15 * sizeof(double);
-    const int J = t->J;
-    hipStream_t s = (hipStream_t)stream_;
-    if (J <= WAVE) return launch_joints(k_joints_fwd<1>, a, wave, 0, s);
-    if (J <= 2 * WAVE) return launch_joints(k_joints_fwd<2>, a, wave, 0, s);
-    if (J <= 3 * WAVE) return launch_joints(k_joints_fwd<3>, a, wave, 0, s);
-    return launch_joints(k_joints_fwd<4>, a, wave, 0, s);
+    return dispatch_nj(t->J, [&](auto nj) { return launch_joints(k_joints_fwd<decltype(nj)::value>, a, wave, 0, (hipStream_t)stream_); });
 }
 
 template <bool FUSED, bool K2D = false>
@@ -658,13 +622,11 @@ static int launch_bwd(JArgs &a, const SumColumns &sc, void *workspace, hipStream
         a.counter = (unsigned int *)workspace;
         a.part = (double *)((char *)workspace + 256);
     }
-    const int J = a.t.J;
-    const size_t wave = bwd_wave_doubles(J, sc.C) * sizeof(double) + cl.wave, block = align256((size_t)J * sizeof(int)) + cl.block;
-    a.cam_wave = (int)(cl.wave / sizeof(double)); a.cam_block = (int)(align256((size_t)J * sizeof(int)) / sizeof(double));
-    if (J <= WAVE) return launch_joints(k_joints_bwd<1, FUSED, K2D>, a, wave, block, s);
-    if (J <= 2 * WAVE) return launch_joints(k_joints_bwd<2, FUSED, K2D>, a, wave, block, s);
-    if (J <= 3 * WAVE) return launch_joints(k_joints_bwd<3, FUSED, K2D>, a, wave, block, s);
-    return launch_joints(k_joints_bwd<4, FUSED, K2D>, a, wave, block, s);
+    const BwdLdsBytes lb = bwd_lds_bytes(a.t.J, sc.C, cl);
+    a.cam_wave = (int)(cl.wave / sizeof(double)); a.cam_block = (int)(lb.child / sizeof(double));
+    return dispatch_nj(a.t.J, [&](auto nj) {
+        return launch_joints(k_joints_bwd<decltype(nj)::value, FUSED, K2D>, a, lb.wave, lb.block, s);
+    });
 }
 
 extern "C" size_t smil_joints_backward_workspace_bytes(const SmilJointTables *t, const SmilJointsInputs *in, const SmilJointsGrads *g) {
@@ -677,13 +639,32 @@ extern "C" int smil_joints_backward(const SmilJointTables *t, const SmilJointsIn
     SMIL_REQUIRE(g && g->d_joints, "smil_joints_backward: d_joints is missing");
     const SumColumns sc = sum_columns(t, in, false, g->d_beta != nullptr, g->d_logscale != nullptr, g->d_btrans != nullptr);
     SMIL_REQUIRE(sc.C == 0 || g->workspace, "smil_joints_backward: the gradient of a shared table needs the workspace");
-    JArgs a = {};
-    a.t = *t; a.in = *in;
-    a.use_scale = in->logscale && in->allow_limb_scaling;
+    JArgs a;
+    joint_args(t, in, a);
     a.d_joints = g->d_joints;
     a.d_beta = in->nB_used > 0 ? g->d_beta : nullptr;
     a.d_theta = g->d_theta; a.d_trans = g->d_trans; a.d_logscale = g->d_logscale; a.d_btrans = g->d_btrans;
     return launch_bwd<false>(a, sc, g->workspace, (hipStream_t)stream_);
+}
+
+// the checks, in their order (`present`: the caller's own pointers that must not be null), and the arguments the fused entry points share
+struct FitEvalOut { float *objs, *d_pose, *d_trans, *d_betas, *d_logscale, *d_btrans, *joints_out; void *workspace; };
+static int fit_eval_args(const char *who, const SmilFitConfig *cfg, const SmilJointTables *t, const SmilJointsInputs *in, int32_t Jc,
+                         const int32_t *canon, const double *joint_weights, double w_k3d, double robust_scale, bool present,
+                         const FitEvalOut &o, JArgs &a) {
+    if (int rc = check_joint_args(who, t, in)) return rc;
+    SMIL_REQUIRE(cfg && present && o.objs && o.workspace, "%s: null argument", who);
+    SMIL_REQUIRE(cfg->N == in->B && cfg->J == t->J, "%s: cfg holds N=%d J=%d, the inputs B=%d J=%d", who, cfg->N, cfg->J, in->B, t->J);
+    SMIL_REQUIRE(cfg->frame0 >= 0 && cfg->N_total >= cfg->frame0 + cfg->N, "%s: bad frame range", who);
+    SMIL_REQUIRE(Jc >= 1, "%s: Jc=%d", who, Jc);
+    SMIL_REQUIRE(canon || Jc <= t->J, "%s: Jc=%d above J=%d without a canon list", who, Jc, t->J);
+    joint_args(t, in, a);
+    a.joints = o.joints_out;
+    a.d_beta = in->nB_used > 0 ? o.d_betas : nullptr;
+    a.d_theta = o.d_pose; a.d_trans = o.d_trans; a.d_logscale = o.d_logscale; a.d_btrans = o.d_btrans;
+    a.cfg = *cfg; a.w_k3d = w_k3d; a.sigma = robust_scale;
+    a.Jc = Jc; a.canon = canon; a.wj = joint_weights; a.objs = o.objs;
+    return SMIL_OK;
 }
 
 extern "C" size_t smil_kp3d_fit_eval_workspace_bytes(const SmilJointTables *t, const SmilJointsInputs *in, int32_t want_betas,
@@ -696,24 +677,14 @@ extern "C" int smil_kp3d_fit_eval(const SmilFitConfig *cfg, double w_k3d, double
                                   const SmilJointsInputs *in, int32_t Jc, const int32_t *canon, const float *target,
                                   const uint8_t *visibility, const double *joint_weights, float *objs, float *d_pose, float *d_trans,
                                   float *d_betas, float *d_logscale, float *d_btrans, float *joints_out, void *workspace, void *stream_) {
-    if (int rc = check_joint_args("smil_kp3d_fit_eval", t, in)) return rc;
-    SMIL_REQUIRE(cfg && target && objs && workspace, "smil_kp3d_fit_eval: null argument");
-    SMIL_REQUIRE(cfg->N == in->B && cfg->J == t->J, "smil_kp3d_fit_eval: cfg holds N=%d J=%d, the inputs B=%d J=%d", cfg->N, cfg->J, in->B, t->J);
-    SMIL_REQUIRE(cfg->frame0 >= 0 && cfg->N_total >= cfg->frame0 + cfg->N, "smil_kp3d_fit_eval: bad frame range");
-    SMIL_REQUIRE(Jc >= 1, "smil_kp3d_fit_eval: Jc=%d", Jc);
-    SMIL_REQUIRE(canon || Jc <= t->J, "smil_kp3d_fit_eval: Jc=%d above J=%d without a canon list", Jc, t->J);
+    JArgs a;
+    if (int rc = fit_eval_args("smil_kp3d_fit_eval", cfg, t, in, Jc, canon, joint_weights, w_k3d, robust_scale, target != nullptr,
+                               {objs, d_pose, d_trans, d_betas, d_logscale, d_btrans, joints_out, workspace}, a)) return rc;
     SMIL_REQUIRE(in->trans_after_joints, "smil_kp3d_fit_eval: the term is defined on the fitter convention (trans_after_joints = 1)");
     SMIL_REQUIRE(std::isfinite(w_k3d) && std::isfinite(robust_scale) && robust_scale >= 0.0,
                  "smil_kp3d_fit_eval: w_k3d=%g robust_scale=%g", w_k3d, robust_scale);
     const SumColumns sc = sum_columns(t, in, true, d_betas != nullptr, d_logscale != nullptr, d_btrans != nullptr);
-    JArgs a = {};
-    a.t = *t; a.in = *in;
-    a.use_scale = in->logscale && in->allow_limb_scaling;
-    a.joints = joints_out;
-    a.d_beta = in->nB_used > 0 ? d_betas : nullptr;
-    a.d_theta = d_pose; a.d_trans = d_trans; a.d_logscale = d_logscale; a.d_btrans = d_btrans;
-    a.cfg = *cfg; a.w_k3d = w_k3d; a.sigma = robust_scale;
-    a.Jc = Jc; a.canon = canon; a.target = target; a.vis = visibility; a.wj = joint_weights; a.objs = objs;
+    a.target = target; a.vis = visibility;
     return launch_bwd<true>(a, sc, workspace, (hipStream_t)stream_);
 }
 
@@ -752,12 +723,9 @@ extern "C" int smil_kp2d_fit_eval(const SmilFitConfig *cfg, double w_k2d, double
                                   double w_k3d, double robust_scale, const float *target3d, const uint8_t *visibility3d, float *objs,
                                   float *d_pose, float *d_trans, float *d_betas, float *d_logscale, float *d_btrans, float *joints_out,
                                   float *yx_out, void *workspace, void *stream_) {
-    if (int rc = check_joint_args("smil_kp2d_fit_eval", t, in)) return rc;
-    SMIL_REQUIRE(cfg && objs && workspace, "smil_kp2d_fit_eval: null argument");
-    SMIL_REQUIRE(cfg->N == in->B && cfg->J == t->J, "smil_kp2d_fit_eval: cfg holds N=%d J=%d, the inputs B=%d J=%d", cfg->N, cfg->J, in->B, t->J);
-    SMIL_REQUIRE(cfg->frame0 >= 0 && cfg->N_total >= cfg->frame0 + cfg->N, "smil_kp2d_fit_eval: bad frame range");
-    SMIL_REQUIRE(Jc >= 1, "smil_kp2d_fit_eval: Jc=%d", Jc);
-    SMIL_REQUIRE(canon || Jc <= t->J, "smil_kp2d_fit_eval: Jc=%d above J=%d without a canon list", Jc, t->J);
+    JArgs a;
+    if (int rc = fit_eval_args("smil_kp2d_fit_eval", cfg, t, in, Jc, canon, joint_weights, w_k3d, robust_scale, true,
+                               {objs, d_pose, d_trans, d_betas, d_logscale, d_btrans, joints_out, workspace}, a)) return rc;
     SMIL_REQUIRE(in->trans_after_joints == 1, "smil_kp2d_fit_eval: the term is defined on the fitter convention (trans_after_joints = 1)");
     SMIL_REQUIRE(std::isfinite(w_k2d) && w_k2d >= 0.0 && std::isfinite(robust_scale_px) && robust_scale_px >= 0.0 && std::isfinite(w_k3d) &&
                  w_k3d >= 0.0 && std::isfinite(robust_scale) && robust_scale >= 0.0,
@@ -769,63 +737,8 @@ extern "C" int smil_kp2d_fit_eval(const SmilFitConfig *cfg, double w_k2d, double
     SMIL_REQUIRE(has2d || has3d, "smil_kp2d_fit_eval: neither term is asked for (w_k2d=%g with%s 2-D targets, w_k3d=%g with%s 3-D targets)",
                  w_k2d, target2d ? "" : "out", w_k3d, target3d ? "" : "out");
     const SumColumns sc = sum_columns(t, in, true, d_betas != nullptr, d_logscale != nullptr, d_btrans != nullptr, true);
-    JArgs a = {};
-    a.t = *t; a.in = *in;
-    a.use_scale = in->logscale && in->allow_limb_scaling;
-    a.joints = joints_out;
-    a.d_beta = in->nB_used > 0 ? d_betas : nullptr;
-    a.d_theta = d_pose; a.d_trans = d_trans; a.d_logscale = d_logscale; a.d_btrans = d_btrans;
-    a.cfg = *cfg; a.w_k3d = w_k3d; a.sigma = robust_scale;
-    a.Jc = Jc; a.canon = canon; a.wj = joint_weights; a.objs = objs;
     a.target = has3d ? target3d : nullptr; a.vis = visibility3d;
     a.w_k2d = w_k2d; a.sigma_px = robust_scale_px; a.cam = *cam;
     a.target2d = has2d ? target2d : nullptr; a.vis2d = visibility2d; a.conf = confidence; a.yx_out = yx_out;
     return launch_bwd<true, true>(a, sc, workspace, (hipStream_t)stream_, cl);
-}
-
-// ---------------------------------------------------------------------------------------------
-// The optimiser step of the 3-D keypoint fitter: smil_adam_step_multi (fit.hip) with the bias corrections formed in double, as
-// torch.optim.Adam forms them.  fit.hip's 1.0f - powf(0.999f, step) is up to 2e-5 off for small step counts (1e-5 in its square
-// root), and an Adam update has the size of lr: every parameter then drifts by that fraction of lr per step whatever its magnitude -
-// 1.9e-7 after five steps at lr = 5e-3, several times the rounding of the fitter's parameters (0.02 .. 0.4).
-// ---------------------------------------------------------------------------------------------
-struct AdamMultiBc {
-    SmilAdamTensor t[SMIL_ADAM_MAX_TENSORS];
-    float step_size[SMIL_ADAM_MAX_TENSORS], bc2_sqrt[SMIL_ADAM_MAX_TENSORS];
-};
-
-__global__ void __launch_bounds__(256) k_adam_multi_bc64(AdamMultiBc a, float b2, float eps, float omb1, float omb2) {
-    const SmilAdamTensor &t = a.t[blockIdx.y];
-    const float step_size = a.step_size[blockIdx.y], bc2_sqrt = a.bc2_sqrt[blockIdx.y];
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < t.n; i += (long long)gridDim.x * blockDim.x) {
-        const float gi = t.grad[i];
-        const float mi = t.exp_avg[i] + (gi - t.exp_avg[i]) * omb1;   // exp_avg.lerp_(grad, 1 - beta1)
-        const float vi = t.exp_avg_sq[i] * b2 + omb2 * gi * gi;       // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-        t.exp_avg[i] = mi; t.exp_avg_sq[i] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        t.param[i] = t.param[i] - step_size * (mi / denom);           // param.addcdiv_(exp_avg, denom, value=-step_size)
-    }
-}
-
-extern "C" int smil_adam_step_multi_bc64(const SmilAdamTensor *tensors, int32_t count, double beta1, double beta2, float eps,
-                                         void *stream_) {
-    SMIL_REQUIRE(tensors && count > 0 && count <= SMIL_ADAM_MAX_TENSORS, "smil_adam_step_multi_bc64: count=%d outside 1..%d", count,
-                 SMIL_ADAM_MAX_TENSORS);
-    SMIL_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "smil_adam_step_multi_bc64: betas %g, %g outside [0, 1)", beta1,
-                 beta2);
-    AdamMultiBc a;
-    long long n_max = 0;
-    for (int k = 0; k < count; ++k) {
-        const SmilAdamTensor &t = tensors[k];
-        SMIL_REQUIRE(t.param && t.grad && t.exp_avg && t.exp_avg_sq && t.n > 0 && t.step > 0, "smil_adam_step_multi_bc64: bad tensor %d", k);
-        a.t[k] = t;
-        a.step_size[k] = (float)((double)t.lr / (1.0 - std::pow(beta1, (double)t.step)));
-        a.bc2_sqrt[k] = (float)std::sqrt(1.0 - std::pow(beta2, (double)t.step));
-        n_max = std::max<long long>(n_max, t.n);
-    }
-    const int gx = (int)std::min<long long>(512, (n_max + 255) / 256);
-    hipLaunchKernelGGL(k_adam_multi_bc64, dim3(gx, count), dim3(256), 0, (hipStream_t)stream_, a, (float)beta2, eps, (float)(1.0 - beta1),
-                       (float)(1.0 - beta2));
-    SMIL_LAUNCH_CHECK();
-    return SMIL_OK;
 }

@@ -12,6 +12,7 @@
 
 #include <atomic>
 
+#include "chain.h"
 #include "skin.h"
 
 #define FRAMES_PER_BLOCK 4  // one wavefront per frame in the chain kernels: frames per block of a large batch ...
@@ -26,46 +27,6 @@ struct Mat34 {
     float r[9];
     float t[3];
 };
-
-__device__ __forceinline__ void rodrigues_fwd(float tx, float ty, float tz, float R[9]) {
-    // batch_lbs.py:37-38: the norm is taken of theta + 1e-8, the axis uses the unshifted theta
-    const float ax = tx + 1e-8f, ay = ty + 1e-8f, az = tz + 1e-8f;
-    const float angle = sqrtf(ax * ax + ay * ay + az * az);
-    const float rx = tx / angle, ry = ty / angle, rz = tz / angle;
-    const float c = cosf(angle), s = sinf(angle);
-    const float k = 1.0f - c;
-    R[0] = c + k * rx * rx;      R[1] = k * rx * ry - s * rz; R[2] = k * rx * rz + s * ry;
-    R[3] = k * ry * rx + s * rz; R[4] = c + k * ry * ry;      R[5] = k * ry * rz - s * rx;
-    R[6] = k * rz * rx - s * ry; R[7] = k * rz * ry + s * rx; R[8] = c + k * rz * rz;
-}
-
-// dR (3x3) -> dtheta for R = c I + (1-c) r r^T + s H(r), angle = |theta + eps|, r = theta / angle
-__device__ __forceinline__ void rodrigues_bwd(float tx, float ty, float tz, const float dR[9], float dth[3]) {
-    const float ax = tx + 1e-8f, ay = ty + 1e-8f, az = tz + 1e-8f;
-    const float angle = sqrtf(ax * ax + ay * ay + az * az);
-    const float inv = 1.0f / angle;
-    const float r[3] = {tx * inv, ty * inv, tz * inv};
-    const float c = cosf(angle), s = sinf(angle), k = 1.0f - c;
-    // d angle through cos/sin:  sum dR_mn * (-s d_mn + s r_m r_n + c H_mn)
-    const float trace = dR[0] + dR[4] + dR[8];
-    float rdr = 0.f;  // r^T dR r
-    for (int m = 0; m < 3; ++m)
-        for (int n = 0; n < 3; ++n) rdr += dR[3 * m + n] * r[m] * r[n];
-    // sum dR_mn H_mn with H = [[0,-r2,r1],[r2,0,-r0],[-r1,r0,0]]
-    const float hx = dR[7] - dR[5], hy = dR[2] - dR[6], hz = dR[3] - dR[1];
-    const float dRH = r[0] * hx + r[1] * hy + r[2] * hz;
-    float dangle = -s * trace + s * rdr + c * dRH;
-    // d r_k = (1-c) ((dR + dR^T) r)_k + s * (hx,hy,hz)_k
-    float dr[3];
-    dr[0] = k * ((dR[0] + dR[0]) * r[0] + (dR[1] + dR[3]) * r[1] + (dR[2] + dR[6]) * r[2]) + s * hx;
-    dr[1] = k * ((dR[3] + dR[1]) * r[0] + (dR[4] + dR[4]) * r[1] + (dR[5] + dR[7]) * r[2]) + s * hy;
-    dr[2] = k * ((dR[6] + dR[2]) * r[0] + (dR[7] + dR[5]) * r[1] + (dR[8] + dR[8]) * r[2]) + s * hz;
-    // r = theta / angle
-    dangle -= (dr[0] * tx + dr[1] * ty + dr[2] * tz) * inv * inv;
-    dth[0] = dr[0] * inv + dangle * ax * inv;
-    dth[1] = dr[1] * inv + dangle * ay * inv;
-    dth[2] = dr[2] * inv + dangle * az * inv;
-}
 
 // ---------------------------------------------------------------------------------------------
 // shape blend: v_shaped[s] = (v_template (+ del_v[s])) + beta[s] @ shapedirs     (smal_torch.py:240-248)
@@ -190,7 +151,8 @@ __global__ void __launch_bounds__(64 * FRAMES_PER_BLOCK) k_pose_fwd(PoseArgs a) 
             } else {
                 const float *th = a.theta + ((size_t)b * J + j) * 3;
                 const float *mk = a.theta_mask ? a.theta_mask + 3 * j : nullptr;
-                rodrigues_fwd(mk ? th[0] * mk[0] : th[0], mk ? th[1] * mk[1] : th[1], mk ? th[2] * mk[2] : th[2], Rq[q]);
+                const float thm[3] = {mk ? th[0] * mk[0] : th[0], mk ? th[1] * mk[1] : th[1], mk ? th[2] * mk[2] : th[2]};
+                rodrigues_fwd(thm, Rq[q]);
             }
             Sq[q][0] = Sq[q][1] = Sq[q][2] = 1.f;
             if (a.use_scale) {
@@ -914,7 +876,7 @@ __global__ void __launch_bounds__(64 * FRAMES_PER_BLOCK) k_chain_bwd(ChainBwdArg
                     for (int i = 0; i < 9; ++i) a.d_Rs_out[o * 9 + i] = dR[i];
                 if (a.d_theta && a.theta) {
                     float dth[3];
-                    rodrigues_bwd(THq[q][0], THq[q][1], THq[q][2], dR, dth);
+                    rodrigues_bwd(THq[q], dR, dth);
                     a.d_theta[o * 3] = dth[0]; a.d_theta[o * 3 + 1] = dth[1]; a.d_theta[o * 3 + 2] = dth[2];
                 }
             }

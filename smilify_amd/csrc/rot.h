@@ -2,7 +2,7 @@
 // Every map is a forward function that fills a small struct of what it computed on the way and a backward function that reads the
 // same struct, so the forward, backward and fused kernels evaluate the same expressions.  All of it is float64 whatever the storage
 // type.  The maps are those of pytorch3d.transforms (rotation_6d_to_matrix, axis_angle_to_matrix, matrix_to_axis_angle) as
-// include/smilfit.h states them; they are NOT skin.h's Rodrigues, which carries the reference model's +1e-8 on the angle.
+// include/smilfit.h states them; they are NOT chain.h's Rodrigues, which carries the reference model's +1e-8 on the angle.
 //
 // Derivative conventions (torch autograd's, which the backward functions reproduce): the norm of a zero vector has derivative 0,
 // max(x, eps) passes the gradient where x >= eps, and the square root of a non-positive number is 0 with derivative 0.

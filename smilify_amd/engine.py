@@ -781,15 +781,20 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, lr, step, beta1=0.5, beta2=0.999
                                           beta2, eps, step, _stream()), "smil_adam_step")
 
 
-def adam_step_multi(items, beta1=0.5, beta2=0.999, eps=1e-8):
-    """One launch for several tensors: ``items`` = [(param, grad, exp_avg, exp_avg_sq, lr, step), ...]."""
+def _adam_multi(entry, items, beta1, beta2, eps):
+    """``items`` packed as SmilAdamTensor arrays, ADAM_MAX_TENSORS to a launch of the library's ``entry``."""
     for k0 in range(0, len(items), _lib.ADAM_MAX_TENSORS):
         chunk = items[k0:k0 + _lib.ADAM_MAX_TENSORS]
         arr = (_lib.AdamTensor * len(chunk))()
         for a, (p, g, m, v, lr, step) in zip(arr, chunk):
             a.param, a.grad, a.exp_avg, a.exp_avg_sq = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
             a.n, a.lr, a.step = p.numel(), float(lr), int(step)
-        _lib.check(_lib.load().smil_adam_step_multi(arr, len(chunk), beta1, beta2, eps, _stream()), "smil_adam_step_multi")
+        _lib.check(getattr(_lib.load(), entry)(arr, len(chunk), beta1, beta2, eps, _stream()), entry)
+
+
+def adam_step_multi(items, beta1=0.5, beta2=0.999, eps=1e-8):
+    """One launch for several tensors: ``items`` = [(param, grad, exp_avg, exp_avg_sq, lr, step), ...]."""
+    _adam_multi("smil_adam_step_multi", items, beta1, beta2, eps)
 
 
 def adam_step_dev(param, grad, exp_avg, exp_avg_sq, lr, step_dev, step_offset=0, beta1=0.5, beta2=0.999, eps=1e-8):
@@ -1685,10 +1690,4 @@ def kp2d_fit_eval(cfg: _lib.FitConfig, jt: DeviceJointTables, cams: CameraSet, w
 
 def adam_step_multi_bc64(items, beta1=0.5, beta2=0.999, eps=1e-8):
     """``adam_step_multi`` through smil_adam_step_multi_bc64: the bias corrections formed in double, as torch.optim.Adam forms them."""
-    for k0 in range(0, len(items), _lib.ADAM_MAX_TENSORS):
-        chunk = items[k0:k0 + _lib.ADAM_MAX_TENSORS]
-        arr = (_lib.AdamTensor * len(chunk))()
-        for a, (p, g, m, v, lr, step) in zip(arr, chunk):
-            a.param, a.grad, a.exp_avg, a.exp_avg_sq = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
-            a.n, a.lr, a.step = p.numel(), float(lr), int(step)
-        _lib.check(_lib.load().smil_adam_step_multi_bc64(arr, len(chunk), beta1, beta2, eps, _stream()), "smil_adam_step_multi_bc64")
+    _adam_multi("smil_adam_step_multi_bc64", items, beta1, beta2, eps)
