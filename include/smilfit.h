@@ -53,7 +53,8 @@ int smil_model_create(const SmilModelDesc *desc, SmilModel **out);
 void smil_model_destroy(SmilModel *m);
 int smil_model_dims(const SmilModel *m, int32_t dims[4]); /* V,F,J,nB */
 const char *smil_last_error(void);
-const char *smil_version(void);   /* "smilfit 0.7 (gfx950; 0.3 + SmilCameras.principal (0.4) + fragments, depth visibility (0.5) + mesh-free joints, kp3d fit (0.6) + kp2d fit)".  0.7 adds
+const char *smil_version(void);   /* "smilfit 0.8 (gfx950; 0.3 + SmilCameras.principal (0.4) + fragments, depth visibility (0.5) + mesh-free joints, kp3d fit (0.6) + kp2d fit (0.7) + visual hull)".  0.8 adds
+                                    * the smil_hull_* entry points with their own struct and changes no layout.  0.7 adds
                                     * smil_kp2d_fit_eval and its workspace query and changes no layout.  0.6 adds
                                     * smil_joints_forward / smil_joints_backward / smil_kp3d_fit_eval / smil_adam_step_multi_bc64 with their own structs and changes no layout.
                                     * 0.3 = the layout of rounds 5 - 6: SmilLbsGrads carries clip_depth in front of
@@ -1044,6 +1045,65 @@ int smil_kp2d_fit_eval(const SmilFitConfig *cfg, double w_k2d, double robust_sca
  * lr = 5e-3) - more than the rounding of parameters well below 1, which KeypointFitter3D's are.  Everything else is the float32
  * arithmetic of smil_adam_step_multi (csrc/fit.hip). */
 int smil_adam_step_multi_bc64(const SmilAdamTensor *tensors, int32_t count, double beta1, double beta2, float eps, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Visual hull: multi-view voxel carving from silhouette masks (smilify_amd/csrc/visual_hull.hip, smilify_amd/visual_hull.py).  An
+ * extension: the reference has no counterpart.  A point belongs to the hull if it projects onto foreground in the views that see
+ * it.  No gradient; asynchronous on `stream`; pure gathers and integer reductions: two calls give the same bits.
+ *
+ * Camera arithmetic: exactly that of smil_kp2d_fit_eval ("Camera arithmetic" above) - float64 on the float32 SmilCameras tables,
+ * y_s = S/2 - (S/2) y_ndc, x_s likewise, S = cam->S; tables of 1, views or N * views rows indexed image % rows, image =
+ * frame * views + view; cam->N = N * views, views <= SMIL_HULL_MAX_VIEWS.  masks (N,views,H,W), uint8 or float32 (masks_f32): pixel
+ * (r, c) covers [r, r+1) x [c, c+1) in (y_s, x_s); H x W need not be S x S (with opencv_to_pinhole_camera(..., S) the screen
+ * coordinates are source pixels for any S).  View v SEES a point iff z_view > SMIL_ZNEAR = 0.001f, 0 <= y_s < H and 0 <= x_s < W, all
+ * decided in float64 before any conversion to an integer (a NaN or infinite coordinate is not seen); it is IN FRONT iff z_view >
+ * SMIL_ZNEAR.  A seen point is foreground in v iff mask[floor(y_s), floor(x_s)] > threshold (compared as float32; a NaN is
+ * background).  fg = the views in which the point is seen and foreground; seen = the views that see it, or, with outside_carves != 0,
+ * the views it is in front of (one that does not see it is then a miss).
+ *
+ * The grid: frame n's voxel (i, j, k), i < Gx fastest, has the linear index i + Gx (j + Gy k) and the centre
+ * origin[n % n_origin] + ((i, j, k) + 0.5) * voxel_size[n % n_voxel_size], each coordinate formed in float64 as written (a product
+ * and a sum, no fused multiply-add).  origin (n_origin,3) and voxel_size (n_voxel_size) are HOST arrays of 1 or N rows (they are
+ * validated on the host and uploaded into the workspace by the calls that read them); everything else is device memory.
+ * Gx Gy Gz <= 2^40; N * Gx * Gy * Gz may exceed 2^31: every index is 64-bit.
+ * ---------------------------------------------------------------------------------------- */
+#define SMIL_HULL_MAX_VIEWS 64
+#define SMIL_HULL_STATS 16
+typedef struct {
+    int32_t N;                /* frames */
+    int32_t Gx, Gy, Gz;       /* voxels per axis, each >= 1 */
+    const double *origin;     /* HOST (n_origin,3): the grid's corner (NOT the first centre) */
+    int32_t n_origin;         /* 1 or N */
+    const double *voxel_size; /* HOST (n_voxel_size): the edge of a voxel, positive and finite */
+    int32_t n_voxel_size;     /* 1 or N */
+} SmilHullGrid;
+
+/* occ (N,Gz,Gy,Gx) uint8 = seen >= min_views && seen - fg <= max_misses at every voxel centre; fg, seen (N,Gz,Gy,Gx) uint8: the
+ * counts, or NULL.  workspace: smil_hull_carve_workspace_bytes(g) bytes of device memory.  Errors (smil_last_error): views outside
+ * 1..64; cam->N != N * views; a camera table whose row count is not 1, views or N * views; a voxel_size that is not positive and
+ * finite; a non-finite origin; a grid extent < 1; min_views outside 0..views; max_misses < 0; a NaN threshold; NULL masks, occ or
+ * workspace. */
+size_t smil_hull_carve_workspace_bytes(const SmilHullGrid *g);
+int smil_hull_carve(const SmilHullGrid *g, const void *masks, int32_t masks_f32, int32_t H, int32_t W, float threshold,
+                    const SmilCameras *cam, int32_t min_views, int32_t max_misses, int32_t outside_carves, uint8_t *occ, uint8_t *fg,
+                    uint8_t *seen, void *workspace, void *stream);
+/* The same test at arbitrary points (N,P,3) float32 (converted to float64): fg, seen (N,P) uint8. */
+int smil_hull_query(const float *points, int32_t N, int64_t P, const void *masks, int32_t masks_f32, int32_t H, int32_t W, float threshold,
+                    const SmilCameras *cam, int32_t outside_carves, uint8_t *fg, uint8_t *seen, void *stream);
+/* stats (N,16) int64 over the voxels with occ != 0: count; sum i, sum j, sum k; sum i^2, sum j^2, sum k^2, sum ij, sum ik, sum jk;
+ * min i, min j, min k; max i, max j, max k.  An empty frame keeps the minima Gx, Gy, Gz and the maxima -1 (as smil_image_bounds).
+ * Exact integers (the grid must keep Gx Gy Gz max(G)^2 below 9e18).  g->origin and g->voxel_size are not read. */
+int smil_hull_stats(const SmilHullGrid *g, const uint8_t *occ, int64_t *stats, void *stream);
+/* The surface: the occupied voxels with an unoccupied 6-neighbour (the grid's border counts as unoccupied).
+ * smil_hull_surface_count fills offsets (N+1) int64 - frame n's surface voxels are rows offsets[n] .. offsets[n+1] of the packed
+ * output - and leaves per-workgroup prefixes in the workspace (smil_hull_surface_workspace_bytes(g) bytes; the table SIZES of g lay
+ * it out, the tables are not read).  smil_hull_surface_write, with the SAME g, occ and workspace, stores the centres, rounded once
+ * to float32, in points (offsets[N],3) and, if index is not NULL, the linear voxel indices in index (offsets[N]) int64: frames in
+ * order and ascending linear index within a frame, whatever the scheduling.  The caller reads offsets[N] in between to size the
+ * outputs (and skips the write when it is 0). */
+size_t smil_hull_surface_workspace_bytes(const SmilHullGrid *g);
+int smil_hull_surface_count(const SmilHullGrid *g, const uint8_t *occ, int64_t *offsets, void *workspace, void *stream);
+int smil_hull_surface_write(const SmilHullGrid *g, const uint8_t *occ, void *workspace, float *points, int64_t *index, void *stream);
 
 #ifdef __cplusplus
 }

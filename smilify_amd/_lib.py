@@ -40,6 +40,8 @@ EXPORTS = [
     "smil_joints_forward", "smil_joints_backward_workspace_bytes", "smil_joints_backward",
     "smil_kp3d_fit_eval_workspace_bytes", "smil_kp3d_fit_eval", "smil_adam_step_multi_bc64",
     "smil_kp2d_fit_eval_workspace_bytes", "smil_kp2d_fit_eval",
+    "smil_hull_carve_workspace_bytes", "smil_hull_carve", "smil_hull_query", "smil_hull_stats", "smil_hull_surface_workspace_bytes",
+    "smil_hull_surface_count", "smil_hull_surface_write",
 ]
 
 N_OBJS = 10
@@ -130,6 +132,11 @@ class JointsGrads(Structure):
     _fields_ = [(n, c_void_p) for n in ("d_joints", "d_beta", "d_theta", "d_trans", "d_logscale", "d_btrans", "workspace")]
 
 
+class HullGrid(Structure):
+    _fields_ = [("N", c_int32), ("Gx", c_int32), ("Gy", c_int32), ("Gz", c_int32), ("origin", c_void_p), ("n_origin", c_int32),
+                ("voxel_size", c_void_p), ("n_voxel_size", c_int32)]
+
+
 class MeshTopology(Structure):
     _fields_ = [("V", c_int32), ("E", c_int32), ("Q", c_int32)] + [
         (n, c_void_p) for n in ("edges", "pairs", "nbr_ptr", "nbr", "inv_deg", "vpair_ptr", "vpair")]
@@ -154,6 +161,8 @@ KP_POOLED, KP_VALID_SAMPLES, KP_SAMPLES = 0, 1, 2  # SMIL_KP_* reductions
 ALIGN_OK, ALIGN_DEGENERATE, ALIGN_EMPTY = 0, 1, 2  # SMIL_ALIGN_* status
 ALIGN_NONE, ALIGN_RIGID, ALIGN_SIMILARITY = 0, 1, 2  # SMIL_ALIGN_* modes of smil_align_errors
 ALIGN_SAVED = 40  # SMIL_ALIGN_SAVED
+HULL_MAX_VIEWS = 64  # SMIL_HULL_MAX_VIEWS
+HULL_STATS = 16  # SMIL_HULL_STATS
 
 _lib = None
 
@@ -292,6 +301,17 @@ def load():
     lib.smil_kp2d_fit_eval.argtypes = [POINTER(FitConfig), c_double, c_double, POINTER(JointTables), POINTER(JointsInputs), POINTER(Cameras),
                                        c_int32] + [c_void_p] * 5 + [c_double, c_double] + [c_void_p] * 12
     lib.smil_adam_step_multi_bc64.argtypes = [POINTER(AdamTensor), c_int32, c_double, c_double, c_float, c_void_p]
+    lib.smil_hull_carve_workspace_bytes.argtypes = [POINTER(HullGrid)]
+    lib.smil_hull_carve_workspace_bytes.restype = c_size_t
+    lib.smil_hull_carve.argtypes = [POINTER(HullGrid), c_void_p, c_int32, c_int32, c_int32, c_float, POINTER(Cameras), c_int32, c_int32, c_int32] + \
+        [c_void_p] * 5
+    lib.smil_hull_query.argtypes = [c_void_p, c_int32, c_int64, c_void_p, c_int32, c_int32, c_int32, c_float, POINTER(Cameras), c_int32] + \
+        [c_void_p] * 3
+    lib.smil_hull_stats.argtypes = [POINTER(HullGrid), c_void_p, c_void_p, c_void_p]
+    lib.smil_hull_surface_workspace_bytes.argtypes = [POINTER(HullGrid)]
+    lib.smil_hull_surface_workspace_bytes.restype = c_size_t
+    lib.smil_hull_surface_count.argtypes = [POINTER(HullGrid), c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.smil_hull_surface_write.argtypes = [POINTER(HullGrid), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.smil_profile_enable.argtypes = [c_int32]
     lib.smil_profile_read.argtypes = [POINTER(c_float), POINTER(c_int32)]
     for name in EXPORTS:

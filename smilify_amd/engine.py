@@ -1691,3 +1691,110 @@ def kp2d_fit_eval(cfg: _lib.FitConfig, jt: DeviceJointTables, cams: CameraSet, w
 def adam_step_multi_bc64(items, beta1=0.5, beta2=0.999, eps=1e-8):
     """``adam_step_multi`` through smil_adam_step_multi_bc64: the bias corrections formed in double, as torch.optim.Adam forms them."""
     _adam_multi("smil_adam_step_multi_bc64", items, beta1, beta2, eps)
+
+
+# ---- visual hull (csrc/visual_hull.hip) -----------------------------------------------------------------------------------------
+class HullGridSpec:
+    """The grid of a visual hull (``SmilHullGrid``): ``N`` frames of ``grid = (Gx, Gy, Gz)`` voxels, x fastest; ``origin`` (1 or N, 3) the
+    grid's corner and ``voxel_size`` (1 or N) the edge of a voxel, both HOST float64 (the library validates them on the host and uploads
+    them itself)."""
+
+    def __init__(self, N: int, grid, origin, voxel_size):
+        if len(tuple(grid)) != 3:
+            raise ValueError(f"grid must be (Gx, Gy, Gz), got {grid}")
+        self.N = int(N)
+        self.grid = tuple(int(g) for g in grid)
+        host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x  # noqa: E731  (a Python float stays float64)
+        self.origin = np.ascontiguousarray(np.asarray(host(origin), np.float64).reshape(-1, 3))
+        self.voxel_size = np.ascontiguousarray(np.asarray(host(voxel_size), np.float64).reshape(-1))
+        s = self.struct = _lib.HullGrid()
+        s.N, (s.Gx, s.Gy, s.Gz) = self.N, self.grid
+        s.origin, s.n_origin = self.origin.ctypes.data, self.origin.shape[0]
+        s.voxel_size, s.n_voxel_size = self.voxel_size.ctypes.data, self.voxel_size.shape[0]
+
+    @property
+    def voxels(self) -> int:
+        return self.grid[0] * self.grid[1] * self.grid[2]
+
+    def shape(self):
+        return (self.N, self.grid[2], self.grid[1], self.grid[0])
+
+
+def _hull_masks(masks: torch.Tensor, N: int, views: int) -> torch.Tensor:
+    if not isinstance(masks, torch.Tensor) or masks.dim() != 4 or masks.dtype not in (torch.uint8, torch.bool, torch.float32):
+        raise ValueError("masks must be a uint8, bool or float32 tensor (N, Nv, H, W)")
+    if masks.shape[0] != N or masks.shape[1] != views:
+        raise ValueError(f"masks must be ({N},{views},H,W), got {tuple(masks.shape)}")
+    masks = masks.contiguous()
+    return masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+
+
+def hull_carve(spec: HullGridSpec, masks: torch.Tensor, cams: CameraSet, min_views: int, max_misses: int, outside_carves: bool = False,
+               threshold: float = 0.0, want_counts: bool = False):
+    """smil_hull_carve: masks (N,Nv,H,W) uint8, bool or float32 -> ``(occ, fg, seen)``, each (N,Gz,Gy,Gx) uint8 (fg, seen None unless
+    ``want_counts``)."""
+    dev = require_gpu(masks.device)
+    N, Nv = spec.N, int(cams.views)
+    masks = _hull_masks(masks, N, Nv)
+    H, W = int(masks.shape[2]), int(masks.shape[3])
+    lib = _lib.load()
+    cam = cams.struct(N * Nv)
+    occ = torch.empty(spec.shape(), dtype=torch.uint8, device=dev)
+    fg = torch.empty_like(occ) if want_counts else None
+    seen = torch.empty_like(occ) if want_counts else None
+    ws = torch.empty(max(1, int(lib.smil_hull_carve_workspace_bytes(ctypes.byref(spec.struct)))), dtype=torch.uint8, device=dev)
+    _lib.check(lib.smil_hull_carve(ctypes.byref(spec.struct), _ptr(masks), int(masks.dtype == torch.float32), H, W, float(threshold),
+                                   ctypes.byref(cam), int(min_views), int(max_misses), int(bool(outside_carves)), _ptr(occ), _ptr(fg),
+                                   _ptr(seen), _ptr(ws), _stream()), "smil_hull_carve")
+    return occ, fg, seen
+
+
+def hull_query(points: torch.Tensor, masks: torch.Tensor, cams: CameraSet, outside_carves: bool = False, threshold: float = 0.0):
+    """smil_hull_query: points (N,P,3) float32 -> ``(fg, seen)`` (N,P) uint8."""
+    dev = require_gpu(masks.device)
+    if points.dim() != 3 or points.shape[-1] != 3:
+        raise ValueError(f"points must be (N,P,3), got {tuple(points.shape)}")
+    N, P, Nv = int(points.shape[0]), int(points.shape[1]), int(cams.views)
+    points = points.detach().to(device=dev, dtype=torch.float32).contiguous()
+    masks = _hull_masks(masks, N, Nv)
+    cam = cams.struct(N * Nv)
+    fg = torch.empty(N, P, dtype=torch.uint8, device=dev)
+    seen = torch.empty_like(fg)
+    _lib.check(_lib.load().smil_hull_query(_ptr(points), N, P, _ptr(masks), int(masks.dtype == torch.float32), int(masks.shape[2]),
+                                           int(masks.shape[3]), float(threshold), ctypes.byref(cam), int(bool(outside_carves)), _ptr(fg),
+                                           _ptr(seen), _stream()), "smil_hull_query")
+    return fg, seen
+
+
+def _hull_occ(spec: HullGridSpec, occ: torch.Tensor) -> torch.Tensor:
+    if tuple(occ.shape) != spec.shape() or occ.dtype != torch.uint8:
+        raise ValueError(f"occ must be a uint8 {spec.shape()} tensor, got {tuple(occ.shape)} {occ.dtype}")
+    require_gpu(occ.device)
+    return occ.contiguous()
+
+
+def hull_stats(spec: HullGridSpec, occ: torch.Tensor) -> torch.Tensor:
+    """smil_hull_stats: (N,16) int64 - count, the sums of i, j, k, of i^2, j^2, k^2, ij, ik, jk, the minima and the maxima of i, j, k over
+    the occupied voxels."""
+    occ = _hull_occ(spec, occ)
+    stats = torch.empty(spec.N, _lib.HULL_STATS, dtype=torch.int64, device=occ.device)
+    _lib.check(_lib.load().smil_hull_stats(ctypes.byref(spec.struct), _ptr(occ), _ptr(stats), _stream()), "smil_hull_stats")
+    return stats
+
+
+def hull_surface(spec: HullGridSpec, occ: torch.Tensor, want_index: bool = False):
+    """smil_hull_surface_count / _write: ``(points (total,3) float32, index (total,) int64 or None, offsets (N+1,) int64)``.  The host
+    waits ONCE, for ``offsets[N]``, to size the outputs."""
+    occ = _hull_occ(spec, occ)
+    dev = occ.device
+    lib = _lib.load()
+    ws = torch.empty(max(1, int(lib.smil_hull_surface_workspace_bytes(ctypes.byref(spec.struct)))), dtype=torch.uint8, device=dev)
+    offsets = torch.empty(spec.N + 1, dtype=torch.int64, device=dev)
+    _lib.check(lib.smil_hull_surface_count(ctypes.byref(spec.struct), _ptr(occ), _ptr(offsets), _ptr(ws), _stream()), "smil_hull_surface_count")
+    total = int(offsets[-1].item())
+    points = torch.empty(total, 3, dtype=torch.float32, device=dev)
+    index = torch.empty(total, dtype=torch.int64, device=dev) if want_index else None
+    if total:
+        _lib.check(lib.smil_hull_surface_write(ctypes.byref(spec.struct), _ptr(occ), _ptr(ws), _ptr(points), _ptr(index), _stream()),
+                   "smil_hull_surface_write")
+    return points, index, offsets

@@ -1,0 +1,151 @@
+"""Multi-view visual hulls from silhouette masks (voxel carving): 3-D evidence for a silhouette-only sequence.
+
+A voxel belongs to the hull if its CENTRE projects onto foreground in the views that see it.  ``carve`` tests every voxel of a regular
+grid per frame in one HIP kernel (csrc/visual_hull.hip, one byte per voxel out; nothing of size voxels x views is ever stored);
+``VisualHull`` turns the occupancy into what the 3-D side of the library takes - exact index statistics (count, centroid, covariance,
+bounds), the packed surface voxels, a fixed-size surface sample for ``fit3d.chamfer_distance`` / ``pointnet2``, and the tight bounds for a
+second, finer carve.  ``query_points`` runs the same test at arbitrary points ("does this triangulated keypoint lie inside every outline").
+
+Conventions (include/smilfit.h, "Visual hull"): the camera arithmetic is that of ``KeypointFitter2D`` (float64 on the float32 tables,
+``(y, x)`` pixels of an ``image_size`` x ``image_size`` screen; with ``cameras.opencv_to_pinhole_camera(R, t, K, S)`` and ``image_size=S`` the
+screen coordinates are source pixels for ANY ``S``, so masks of full, non-square camera frames need no crop).  ``cameras`` is a
+``cameras.FoVCameras`` or the dict ``KeypointFitter2D`` takes; every table holds 1, ``views`` or ``N * views`` rows.  Pixel ``(r, c)`` of a mask
+covers ``[r, r+1) x [c, c+1)``; a view sees a point iff it lies more than the near plane (0.001) in front of the camera and inside the
+``H x W`` mask; a seen point is foreground iff the mask value is ``> threshold`` (a float NaN is background).
+
+Limits.  A voxel is tested at its centre only: keep ``voxel_size`` at or below a pixel's footprint (``z / (image_size/2 * k11)``) or thin
+limbs fall between the centres.  One wrong mask or a calibration error carves for good: for noisy masks or calibration, dilate the masks
+first (``torch.nn.functional.max_pool2d(masks.float(), 2 r + 1, 1, r)``) or raise ``max_misses``.  There are no gradients.  At most 64
+views.  ``origin`` and ``voxel_size`` are host values (a device tensor is copied back, which waits for the device).
+"""
+from __future__ import annotations
+
+from typing import NamedTuple, Tuple
+
+import torch
+
+from . import _lib, engine
+from .fit_keypoints2d import _camera_set
+
+MAX_VIEWS = _lib.HULL_MAX_VIEWS
+
+
+class HullStats(NamedTuple):
+    count: torch.Tensor       # (N,) int64: occupied voxels
+    centroid: torch.Tensor    # (N,3) float64, world units; NaN for an empty frame
+    covariance: torch.Tensor  # (N,3,3) float64, world units squared (population covariance of the occupied centres); NaN if empty
+    index_min: torch.Tensor   # (N,3) int64 (i, j, k); the grid's extent for an empty frame
+    index_max: torch.Tensor   # (N,3) int64; -1 for an empty frame
+
+
+def _check_masks(masks) -> Tuple[int, int]:
+    if not isinstance(masks, torch.Tensor) or masks.dim() != 4:
+        raise ValueError("masks must be a tensor (N, Nv, H, W)")
+    N, Nv = int(masks.shape[0]), int(masks.shape[1])
+    if not 1 <= Nv <= MAX_VIEWS:
+        raise _lib.SmilError(f"visual hull: views={Nv} outside 1..{MAX_VIEWS}")
+    return N, Nv
+
+
+def _image_size(image_size) -> int:
+    if int(image_size) != image_size or int(image_size) < 1:
+        raise ValueError(f"image_size must be a positive integer, got {image_size}")
+    return int(image_size)
+
+
+class VisualHull:
+    """The result of ``carve``: ``occupancy (N,Gz,Gy,Gx)`` uint8, ``fg`` / ``seen`` (the per-voxel view counts, or None), and the grid
+    (``origin (1 or N,3)``, ``voxel_size (1 or N)`` float64 on the host, ``grid = (Gx, Gy, Gz)``).  Voxel ``(i, j, k)`` has the centre
+    ``origin + ((i, j, k) + 0.5) * voxel_size`` and the linear index ``i + Gx (j + Gy k)``."""
+
+    def __init__(self, occupancy, fg, seen, spec: engine.HullGridSpec):
+        self.occupancy, self.fg, self.seen = occupancy, fg, seen
+        self._spec = spec
+        self.grid = spec.grid
+        self.origin = torch.from_numpy(spec.origin.copy())
+        self.voxel_size = torch.from_numpy(spec.voxel_size.copy())
+
+    def _raw_stats(self) -> torch.Tensor:
+        return engine.hull_stats(self._spec, self.occupancy)
+
+    def stats(self) -> HullStats:
+        """Count, centroid, covariance and index bounds of the occupied voxels of every frame.  The kernel returns exact int64 sums of the
+        voxel indices; the float64 moments are formed from them with tensor operations on the device (no synchronisation).  A frame
+        with no occupied voxel returns NaN rows (and ``index_min = grid``, ``index_max = -1``); it does not raise."""
+        s = self._raw_stats()
+        dev = s.device
+        n = s[:, 0].to(torch.float64)
+        mean = s[:, 1:4].to(torch.float64) / n[:, None]  # (0 / 0 = NaN for an empty frame)
+        second = torch.empty(s.shape[0], 3, 3, dtype=torch.float64, device=dev)
+        for (a, b), col in (((0, 0), 4), ((1, 1), 5), ((2, 2), 6), ((0, 1), 7), ((0, 2), 8), ((1, 2), 9)):
+            second[:, a, b] = second[:, b, a] = s[:, col].to(torch.float64) / n
+        origin = self.origin.to(dev).expand(s.shape[0], 3)
+        voxel = self.voxel_size.to(dev).expand(s.shape[0])
+        cov = (second - mean[:, :, None] * mean[:, None, :]) * (voxel * voxel)[:, None, None]
+        return HullStats(s[:, 0], origin + (mean + 0.5) * voxel[:, None], cov, s[:, 10:13], s[:, 13:16])
+
+    def surface_points(self, return_index: bool = False):
+        """``(points (total,3) float32, offsets (N+1,) int64)``: the centres of the surface voxels - occupied, with an unoccupied
+        6-neighbour, the grid's border counting as unoccupied - packed frame after frame in ascending linear voxel index; frame ``n``
+        owns rows ``offsets[n]:offsets[n+1]``.  ``return_index``: ``(points, index (total,) int64, offsets)`` with the linear voxel indices.
+        This call SYNCHRONISES the host once, to read the total and size the output."""
+        points, index, offsets = engine.hull_surface(self._spec, self.occupancy, want_index=return_index)
+        return (points, index, offsets) if return_index else (points, offsets)
+
+    def sample_surface(self, num_samples: int, seed: int = 0) -> torch.Tensor:
+        """(N,S,3) float32: ``num_samples`` surface points per frame, drawn uniformly with replacement by ``engine.sample_vertices`` from the
+        packed surface - the fixed-size cloud ``fit3d.chamfer_distance`` and ``pointnet2`` take.  A frame with an empty hull gives zeros, as
+        that function documents.  One host synchronisation (``surface_points``)."""
+        points, offsets = self.surface_points()
+        N = self._spec.N
+        if points.shape[0] == 0:
+            return torch.zeros(N, int(num_samples), 3, dtype=torch.float32, device=points.device)
+        if points.shape[0] >= 2**31:
+            raise _lib.SmilError(f"sample_surface: {points.shape[0]} surface voxels exceed the sampler's 32-bit offsets")
+        values = torch.zeros(points.shape[0], dtype=torch.float32, device=points.device)
+        out, _, _ = engine.sample_vertices(points, values, offsets.to(torch.int32), N, int(num_samples), seed)
+        return out
+
+    def tight_bounds(self, margin_voxels: int = 1):
+        """``(origin (N,3), voxel_size (N,))`` float64 of a grid of the same ``grid`` extent around every frame's occupied index range
+        ``index_min .. index_max`` widened by ``margin_voxels`` coarse voxels on every side: the second pass of a coarse-to-fine carve
+        (``carve(..., origin=origin, voxel_size=voxel_size, grid=hull.grid)``).  The new voxels are cubes sized by the axis that needs the
+        largest ones, the box is centred on the occupied range.  A frame with an empty hull keeps its grid."""
+        s = self._raw_stats()
+        dev = s.device
+        N = s.shape[0]
+        origin = self.origin.to(dev).expand(N, 3)
+        voxel = self.voxel_size.to(dev).expand(N)
+        G = torch.tensor(self.grid, dtype=torch.float64, device=dev)
+        lo = (s[:, 10:13] - int(margin_voxels)).to(torch.float64)
+        hi = (s[:, 13:16] + 1 + int(margin_voxels)).to(torch.float64)
+        new_voxel = ((hi - lo) / G).amax(dim=1) * voxel
+        centre = origin + 0.5 * (lo + hi) * voxel[:, None]
+        new_origin = centre - 0.5 * G * new_voxel[:, None]
+        empty = (s[:, 0] == 0)
+        return torch.where(empty[:, None], origin, new_origin), torch.where(empty, voxel, new_voxel)
+
+
+def carve(masks, cameras, *, image_size: int, origin, voxel_size, grid, min_views: int = 2, max_misses: int = 0,
+          outside_carves: bool = False, threshold: float = 0.0, return_counts: bool = False) -> VisualHull:
+    """Carve a ``grid = (Gx, Gy, Gz)`` of cubic voxels per frame from ``masks (N,Nv,H,W)`` (uint8, bool or float32, on the GPU).
+
+    ``origin`` ((3,) or (N,3)) is the grid's corner, ``voxel_size`` (a number or (N,)) the edge of a voxel.  A voxel is occupied iff
+    ``seen >= min_views and seen - fg <= max_misses``, with ``seen`` the views that see its centre and ``fg`` those in which it is foreground.
+    ``outside_carves``: a view in front of which the centre lies but outside the image counts as seen and as a miss (by default such a view
+    does not vote).  ``return_counts``: keep the per-voxel ``fg`` and ``seen`` (two more bytes per voxel)."""
+    N, Nv = _check_masks(masks)
+    dev = engine.require_gpu(masks.device)
+    cams = _camera_set(cameras, Nv, N, _image_size(image_size), dev)
+    spec = engine.HullGridSpec(N, grid, origin, voxel_size)
+    occ, fg, seen = engine.hull_carve(spec, masks, cams, min_views, max_misses, outside_carves, threshold, want_counts=return_counts)
+    return VisualHull(occ, fg, seen, spec)
+
+
+def query_points(points, masks, cameras, *, image_size: int, threshold: float = 0.0, outside_carves: bool = False):
+    """``(fg, seen)`` (N,P) uint8: in how many views each of ``points (N,P,3)`` is foreground, and how many see it (``outside_carves``: are in
+    front of it) - the test of ``carve`` at arbitrary points.  A point lies inside every outline iff ``fg == seen == Nv``."""
+    N, Nv = _check_masks(masks)
+    dev = engine.require_gpu(masks.device)
+    cams = _camera_set(cameras, Nv, N, _image_size(image_size), dev)
+    return engine.hull_query(torch.as_tensor(points), masks, cams, outside_carves, threshold)
