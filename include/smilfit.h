@@ -53,7 +53,8 @@ int smil_model_create(const SmilModelDesc *desc, SmilModel **out);
 void smil_model_destroy(SmilModel *m);
 int smil_model_dims(const SmilModel *m, int32_t dims[4]); /* V,F,J,nB */
 const char *smil_last_error(void);
-const char *smil_version(void);   /* "smilfit 0.8 (gfx950; 0.3 + SmilCameras.principal (0.4) + fragments, depth visibility (0.5) + mesh-free joints, kp3d fit (0.6) + kp2d fit (0.7) + visual hull)".  0.8 adds
+const char *smil_version(void);   /* "smilfit 0.9 (gfx950; 0.3 + SmilCameras.principal (0.4) + fragments, depth visibility (0.5) + mesh-free joints, kp3d fit (0.6) + kp2d fit (0.7) + visual hull (0.8) + distance fields)".  0.9 adds
+                                    * smil_hull_edt, its workspace query and smil_field_sample and changes no layout.  0.8 adds
                                     * the smil_hull_* entry points with their own struct and changes no layout.  0.7 adds
                                     * smil_kp2d_fit_eval and its workspace query and changes no layout.  0.6 adds
                                     * smil_joints_forward / smil_joints_backward / smil_kp3d_fit_eval / smil_adam_step_multi_bc64 with their own structs and changes no layout.
@@ -1104,6 +1105,45 @@ int smil_hull_stats(const SmilHullGrid *g, const uint8_t *occ, int64_t *stats, v
 size_t smil_hull_surface_workspace_bytes(const SmilHullGrid *g);
 int smil_hull_surface_count(const SmilHullGrid *g, const uint8_t *occ, int64_t *offsets, void *workspace, void *stream);
 int smil_hull_surface_write(const SmilHullGrid *g, const uint8_t *occ, void *workspace, float *points, int64_t *index, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Distance fields: the exact Euclidean distance transform of an occupancy grid (or of a batch of 2-D masks: Gz = 1, every image a
+ * frame of grid (W, H, 1)) and a differentiable sampler of the field (smilify_amd/csrc/distance_field.hip).  An extension: the
+ * reference has no counterpart.  Asynchronous on `stream`, no atomics, no host synchronisation; two calls give the same bits.
+ *
+ * The transform.  The feature set F of frame n is its voxels with occ != 0 (invert != 0: with occ == 0).
+ * d2[n,k,j,i] = min over (i',j',k') in F of (i-i')^2 + (j-j')^2 + (k-k')^2: an int32 in voxel units, in the layout of occ, centre to
+ * centre (a feature voxel reads 0).  border != 0: the one-voxel layer around the grid - the index -1 or G on any axis - counts as
+ * features too (as the grid's border counts as unoccupied for the surface), so the inside distance of a full grid is finite:
+ * min(i+1, Gx-i, j+1, Gy-j, k+1, Gz-k)^2.  A frame with an empty F and border == 0 reads SMIL_EDT_NONE everywhere.  g->origin and
+ * g->voxel_size are not read.  workspace: smil_hull_edt_workspace_bytes(g) bytes of device memory (a second int32 grid when Gz, or Gy
+ * of a slice of more than 65 536 cells, exceeds the 512 cells of a line the LDS path holds; 256 bytes otherwise).  Errors
+ * (smil_last_error): a NULL g, occ, d2 or workspace; a grid extent < 1; (Gx+1)^2 + (Gy+1)^2 + (Gz+1)^2 >= 2^31 (the result must fit an
+ * int32).  Every linear index is 64-bit: N Gx Gy Gz may exceed 2^31.
+ * ---------------------------------------------------------------------------------------- */
+#define SMIL_EDT_NONE 2147483647
+size_t smil_hull_edt_workspace_bytes(const SmilHullGrid *g);
+int smil_hull_edt(const SmilHullGrid *g, const uint8_t *occ, int32_t invert, int32_t border, int32_t *d2, void *workspace, void *stream);
+/* The field at points (N,P,point_dim) float32, float64 arithmetic, every output rounded once to float32: value (N,P) and, unless
+ * NULL, grad (N,P,point_dim), the exact derivative of value with respect to the point, in world units.  d2_out: a transform of the
+ * hull; d2_in: NULL (an unsigned field) or the transform of its complement (a signed field, negative inside).
+ * Per axis (origin, voxel: the frame's rows of g, HOST tables of 1 or N rows as for smil_hull_carve; G: the axis' extent):
+ *   u = (p - origin) / voxel - 0.5     the continuous index: cell centres lie on the integers
+ *   c = clamp(u, 0, G-1);  i0 = min(floor(c), G-2), or 0 when G == 1;  i1 = min(i0+1, G-1);  t = c - i0
+ * A cell's value is r = sqrt((double)d2_out) - sqrt((double)d2_in) in voxels (no second term without d2_in); a d2_in equal to
+ * SMIL_EDT_NONE counts as 0 and a cell whose d2_out is SMIL_EDT_NONE reads r = 0, so a frame without a hull gives value 0 and
+ * gradient 0 inside the grid, not inf or NaN.
+ *   value = voxel * ( trilinear(r; t) + |u - c|_2 ),   the interpolation (1-t) r[i0] + t r[i1] along x, then y, then z.
+ * The second term is the distance from the point to the box of cell centres: it keeps the field continuous and pulls a point
+ * outside the grid back towards it.  grad = the interpolation's slope (r[i1] - r[i0] along the axis, interpolated along the other
+ * two; 0 on an axis whose u was clamped, u != c, and on an axis with G == 1) plus the unit vector (u - c) / |u - c| where that is
+ * non-zero; the voxel size cancels.  At an integer u the rule for i0 - the cell to the right, except at the last - decides the
+ * slope.  point_dim == 2: points are (y, x) pixels, the grid must have Gz == 1, y maps to axis j and x to axis i, there is no z, and
+ * grad is (dy, dx).  A point with a non-finite coordinate gives value 0 and gradient 0.  workspace:
+ * smil_hull_carve_workspace_bytes(g) bytes (the uploaded tables).  Errors: point_dim outside {2, 3}; point_dim == 2 with Gz != 1;
+ * NULL d2_out, points, value or workspace; the grid and table checks of smil_hull_carve. */
+int smil_field_sample(const SmilHullGrid *g, const int32_t *d2_out, const int32_t *d2_in, const float *points, int32_t point_dim, int64_t P,
+                      float *value, float *grad, void *workspace, void *stream);
 
 #ifdef __cplusplus
 }

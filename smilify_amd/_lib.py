@@ -42,6 +42,7 @@ EXPORTS = [
     "smil_kp2d_fit_eval_workspace_bytes", "smil_kp2d_fit_eval",
     "smil_hull_carve_workspace_bytes", "smil_hull_carve", "smil_hull_query", "smil_hull_stats", "smil_hull_surface_workspace_bytes",
     "smil_hull_surface_count", "smil_hull_surface_write",
+    "smil_hull_edt_workspace_bytes", "smil_hull_edt", "smil_field_sample",
 ]
 
 N_OBJS = 10
@@ -163,6 +164,7 @@ ALIGN_NONE, ALIGN_RIGID, ALIGN_SIMILARITY = 0, 1, 2  # SMIL_ALIGN_* modes of smi
 ALIGN_SAVED = 40  # SMIL_ALIGN_SAVED
 HULL_MAX_VIEWS = 64  # SMIL_HULL_MAX_VIEWS
 HULL_STATS = 16  # SMIL_HULL_STATS
+EDT_NONE = 2147483647  # SMIL_EDT_NONE
 
 _lib = None
 
@@ -312,6 +314,10 @@ def load():
     lib.smil_hull_surface_workspace_bytes.restype = c_size_t
     lib.smil_hull_surface_count.argtypes = [POINTER(HullGrid), c_void_p, c_void_p, c_void_p, c_void_p]
     lib.smil_hull_surface_write.argtypes = [POINTER(HullGrid), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.smil_hull_edt_workspace_bytes.argtypes = [POINTER(HullGrid)]
+    lib.smil_hull_edt_workspace_bytes.restype = c_size_t
+    lib.smil_hull_edt.argtypes = [POINTER(HullGrid), c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
+    lib.smil_field_sample.argtypes = [POINTER(HullGrid), c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.smil_profile_enable.argtypes = [c_int32]
     lib.smil_profile_read.argtypes = [POINTER(c_float), POINTER(c_int32)]
     for name in EXPORTS:

@@ -1798,3 +1798,43 @@ def hull_surface(spec: HullGridSpec, occ: torch.Tensor, want_index: bool = False
         _lib.check(lib.smil_hull_surface_write(ctypes.byref(spec.struct), _ptr(occ), _ptr(ws), _ptr(points), _ptr(index), _stream()),
                    "smil_hull_surface_write")
     return points, index, offsets
+
+
+# ---- distance fields (csrc/distance_field.hip) ----------------------------------------------------------------------------------
+def hull_edt(spec: HullGridSpec, occ: torch.Tensor, invert: bool = False, border: bool = False) -> torch.Tensor:
+    """smil_hull_edt: occ (N,Gz,Gy,Gx) uint8 -> d2 (N,Gz,Gy,Gx) int32, the squared voxel distance of every voxel to the nearest one with
+    ``occ != 0`` (``invert``: ``== 0``; ``border``: the one-voxel layer around the grid counts too); ``_lib.EDT_NONE`` where there is none."""
+    occ = _hull_occ(spec, occ)
+    lib = _lib.load()
+    d2 = torch.empty(spec.shape(), dtype=torch.int32, device=occ.device)
+    ws = torch.empty(max(1, int(lib.smil_hull_edt_workspace_bytes(ctypes.byref(spec.struct)))), dtype=torch.uint8, device=occ.device)
+    _lib.check(lib.smil_hull_edt(ctypes.byref(spec.struct), _ptr(occ), int(bool(invert)), int(bool(border)), _ptr(d2), _ptr(ws), _stream()),
+               "smil_hull_edt")
+    return d2
+
+
+def _field_grid(spec: HullGridSpec, d2: torch.Tensor, name: str) -> torch.Tensor:
+    if tuple(d2.shape) != spec.shape() or d2.dtype != torch.int32:
+        raise ValueError(f"{name} must be an int32 {spec.shape()} tensor, got {tuple(d2.shape)} {d2.dtype}")
+    require_gpu(d2.device)
+    return d2.contiguous()
+
+
+def field_sample(spec: HullGridSpec, d2_out: torch.Tensor, d2_in: Optional[torch.Tensor], points: torch.Tensor, want_grad: bool = True):
+    """smil_field_sample: points (N,P,3), or (N,P,2) ``(y, x)`` on a grid with Gz = 1 -> ``(value (N,P), grad (N,P,dim) or None)`` float32."""
+    d2_out = _field_grid(spec, d2_out, "d2_out")
+    d2_in = None if d2_in is None else _field_grid(spec, d2_in, "d2_in")
+    dev = d2_out.device
+    if points.dim() != 3 or points.shape[0] != spec.N or points.shape[2] not in (2, 3):
+        raise ValueError(f"points must be ({spec.N},P,2 or 3), got {tuple(points.shape)}")
+    P, dim = int(points.shape[1]), int(points.shape[2])
+    points = _f32(points, dev)
+    lib = _lib.load()
+    value = torch.empty(spec.N, P, dtype=torch.float32, device=dev)
+    grad = torch.empty(spec.N, P, dim, dtype=torch.float32, device=dev) if want_grad else None
+    if P == 0:  # (an empty tensor has no address to pass)
+        return value, grad
+    ws = torch.empty(max(1, int(lib.smil_hull_carve_workspace_bytes(ctypes.byref(spec.struct)))), dtype=torch.uint8, device=dev)
+    _lib.check(lib.smil_field_sample(ctypes.byref(spec.struct), _ptr(d2_out), _ptr(d2_in), _ptr(points), dim, P, _ptr(value), _ptr(grad),
+                                     _ptr(ws), _stream()), "smil_field_sample")
+    return value, grad

@@ -313,3 +313,51 @@ def prepare_targets(frames, masks, K, dist, windows, S, joints_yx=None):
         else:
             joints = np.stack([cameras.crop_points_yx(np.asarray(joints_yx)[n], win[n], S) for n in range(N)])
     return _back(rgb_out, frames), _back(sil_out, masks), joints
+
+
+# ---- distance transforms of masks (csrc/distance_field.hip: every image a frame of grid (W, H, 1)) -------------------------------------
+def mask_distance_transform(masks, threshold: float = 0.0, inside: bool = False) -> torch.Tensor:
+    """int32, the shape of ``masks`` ((N,Nv,H,W) or (N,H,W), any real dtype or bool, on the GPU): the exact squared distance in pixels from
+    every pixel to the nearest pixel ``> threshold`` (a NaN is background, as in ``visual_hull.carve``).  ``inside``: to the nearest
+    background pixel instead (the surroundings of the image do not count: an image is one slice of a grid, whose border would lie one
+    cell above and below every pixel).  Centre to centre: a target pixel reads 0.  An image without a target reads 2^31 - 1 everywhere.  The kernel is the visual hull's
+    ``distance_transform``."""
+    if not isinstance(masks, torch.Tensor) or masks.dim() not in (3, 4):
+        raise ValueError("masks must be a tensor (N,Nv,H,W) or (N,H,W)")
+    dev = engine.require_gpu(masks.device)
+    H, W = int(masks.shape[-2]), int(masks.shape[-1])
+    fg = ((masks.float() if masks.dtype == torch.bool else masks) > threshold).to(torch.uint8).reshape(-1, 1, H, W)
+    spec = engine.HullGridSpec(fg.shape[0], (W, H, 1), (0.0, 0.0, 0.0), 1.0)
+    return engine.hull_edt(spec, fg.to(dev), invert=inside).reshape(masks.shape)
+
+
+class _MaskSampleFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, d2):
+        H, W = int(d2.shape[-2]), int(d2.shape[-1])
+        spec = engine.HullGridSpec(d2.numel() // (H * W), (W, H, 1), (0.0, 0.0, 0.0), 1.0)
+        want = points.requires_grad
+        value, grad = engine.field_sample(spec, d2.reshape(spec.shape()), None, points.reshape(spec.N, -1, 2), want_grad=want)
+        ctx.save_for_backward(grad) if want else ctx.save_for_backward()
+        ctx.want = want
+        return value.reshape(points.shape[:-1])
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.want:
+            return None, None
+        (grad,) = ctx.saved_tensors
+        return g[..., None] * grad.reshape(g.shape + (2,)), None
+
+
+def sample_mask_distance(d2, points_yx) -> torch.Tensor:
+    """float32 ``(..., P)``: the distance in pixels of ``points_yx (..., P, 2)`` - ``(y, x)`` pixels, the project's order - to the
+    foreground of the masks whose ``mask_distance_transform`` is ``d2 (..., H, W)`` (the same leading shape), differentiable in the points.
+    Pixel ``(r, c)`` covers ``[r, r+1) x [c, c+1)``, its centre lies at ``(r + 0.5, c + 0.5)`` (the convention of ``visual_hull``); the value
+    is ``sqrt(d2)`` at a centre, bilinear between centres, and grows by the distance to the box of pixel centres outside it.  Centre to
+    centre: a point inside a foreground pixel but off its centre reads a small positive value next to background.  A NaN or infinite
+    point reads 0 with gradient 0; an image without foreground reads 0 everywhere."""
+    if not (isinstance(d2, torch.Tensor) and isinstance(points_yx, torch.Tensor)) or d2.dim() < 3 or points_yx.dim() != d2.dim() \
+            or points_yx.shape[-1] != 2 or points_yx.shape[:-2] != d2.shape[:-2]:
+        raise ValueError("sample_mask_distance: d2 (..., H, W) and points_yx (..., P, 2) with the same leading shape")
+    return _MaskSampleFn.apply(points_yx, d2)

@@ -15,7 +15,8 @@ covers ``[r, r+1) x [c, c+1)``; a view sees a point iff it lies more than the ne
 
 Limits.  A voxel is tested at its centre only: keep ``voxel_size`` at or below a pixel's footprint (``z / (image_size/2 * k11)``) or thin
 limbs fall between the centres.  One wrong mask or a calibration error carves for good: for noisy masks or calibration, dilate the masks
-first (``torch.nn.functional.max_pool2d(masks.float(), 2 r + 1, 1, r)``) or raise ``max_misses``.  There are no gradients.  At most 64
+first (``torch.nn.functional.max_pool2d(masks.float(), 2 r + 1, 1, r)``) or raise ``max_misses``.  There are no gradients through the
+carve itself; ``VisualHull.distance_field`` gives the differentiable term that pulls points towards (or into) a carved hull.  At most 64
 views.  ``origin`` and ``voxel_size`` are host values (a device tensor is copied back, which waits for the device).
 """
 from __future__ import annotations
@@ -106,6 +107,19 @@ class VisualHull:
         out, _, _ = engine.sample_vertices(points, values, offsets.to(torch.int32), N, int(num_samples), seed)
         return out
 
+    def distance_transform(self, inside: bool = False, border: bool = False) -> torch.Tensor:
+        """(N,Gz,Gy,Gx) int32: the exact squared Euclidean distance, in voxels, from every voxel to the nearest occupied one (``inside``:
+        to the nearest unoccupied one).  ``border``: the one-voxel layer around the grid counts as a target too (for ``inside`` this is
+        ``surface_points``' rule that the border is unoccupied, and keeps the inside distance of a full grid finite).  Centre to centre:
+        a target voxel reads 0.  A frame without a target reads ``_lib.EDT_NONE`` (2^31 - 1) everywhere.  Integer arithmetic: the result
+        is the definition's, bit for bit."""
+        return engine.hull_edt(self._spec, self.occupancy, invert=inside, border=border)
+
+    def distance_field(self, signed: bool = False) -> "HullDistanceField":
+        """The hull's distance field for ``HullDistanceField.sample`` / ``containment_loss``: ``distance_transform()``, and for ``signed``
+        also ``distance_transform(inside=True, border=True)``; the signed field is negative inside the hull and positive outside."""
+        return HullDistanceField(self._spec, self.distance_transform(), self.distance_transform(inside=True, border=True) if signed else None)
+
     def tight_bounds(self, margin_voxels: int = 1):
         """``(origin (N,3), voxel_size (N,))`` float64 of a grid of the same ``grid`` extent around every frame's occupied index range
         ``index_min .. index_max`` widened by ``margin_voxels`` coarse voxels on every side: the second pass of a coarse-to-fine carve
@@ -124,6 +138,62 @@ class VisualHull:
         new_origin = centre - 0.5 * G * new_voxel[:, None]
         empty = (s[:, 0] == 0)
         return torch.where(empty[:, None], origin, new_origin), torch.where(empty, voxel, new_voxel)
+
+
+class _FieldSampleFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, spec, d2_out, d2_in):
+        want = points.requires_grad
+        value, grad = engine.field_sample(spec, d2_out, d2_in, points, want_grad=want)
+        ctx.save_for_backward(grad) if want else ctx.save_for_backward()
+        ctx.want = want
+        return value
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.want:
+            return None, None, None, None
+        (grad,) = ctx.saved_tensors
+        return g[..., None] * grad, None, None, None
+
+
+class HullDistanceField:
+    """A distance field on the grid of a hull: ``d2_out (N,Gz,Gy,Gx)`` int32 (squared voxel distances to the hull), ``d2_in`` (to its
+    complement; None for an unsigned field), and the grid (``origin``, ``voxel_size``, ``grid`` as on ``VisualHull``).
+
+    The field at a point (include/smilfit.h, "Distance fields"): per axis ``u = (p - origin) / voxel_size - 0.5`` is the continuous index
+    (cell centres on the integers); the cell values ``voxel_size * (sqrt(d2_out) - sqrt(d2_in))`` are interpolated trilinearly between the
+    centres, and outside the box of cell centres the distance to that box is added, so the field is continuous and a point outside the
+    grid is pulled back to it.  A frame without a hull reads 0 everywhere (no pull), a point with a NaN or infinite coordinate reads 0
+    with gradient 0 (the keypoint fitters' "not there").  The transform is centre to centre: a point inside an occupied voxel but off its
+    centre reads a small positive interpolated value near the surface.  At an integer ``u`` the slope is that of the cell to the right
+    (to the left at the last cell)."""
+
+    def __init__(self, spec: engine.HullGridSpec, d2_out: torch.Tensor, d2_in=None):
+        self._spec, self.d2_out, self.d2_in = spec, d2_out, d2_in
+        self.grid = spec.grid
+        self.origin = torch.from_numpy(spec.origin.copy())
+        self.voxel_size = torch.from_numpy(spec.voxel_size.copy())
+
+    @property
+    def signed(self) -> bool:
+        return self.d2_in is not None
+
+    def sample(self, points: torch.Tensor) -> torch.Tensor:
+        """(N,P) float32: the field at ``points (N,P,3)`` (world units), differentiable in the points (one gather kernel forward, which also
+        stores the gradient; the backward multiplies).  There is no gradient to the field."""
+        if not isinstance(points, torch.Tensor) or points.dim() != 3 or points.shape[-1] != 3:
+            raise ValueError(f"points must be a tensor (N,P,3), got {tuple(getattr(points, 'shape', ()))}")
+        return _FieldSampleFn.apply(points, self._spec, self.d2_out, self.d2_in)
+
+    def containment_loss(self, points: torch.Tensor, weights=None) -> torch.Tensor:
+        """The mean of ``sample(points) ** 2`` (with ``weights (N,P)``: the weighted mean, ``sum(w s^2) / sum(w)``): zero when every point
+        lies on a hull voxel's centre (unsigned field), growing with the squared distance to the hull."""
+        s2 = self.sample(points) ** 2
+        if weights is None:
+            return s2.mean()
+        w = torch.as_tensor(weights, dtype=s2.dtype, device=s2.device)
+        return (w * s2).sum() / w.sum()
 
 
 def carve(masks, cameras, *, image_size: int, origin, voxel_size, grid, min_views: int = 2, max_misses: int = 0,
