@@ -53,7 +53,8 @@ int smil_model_create(const SmilModelDesc *desc, SmilModel **out);
 void smil_model_destroy(SmilModel *m);
 int smil_model_dims(const SmilModel *m, int32_t dims[4]); /* V,F,J,nB */
 const char *smil_last_error(void);
-const char *smil_version(void);   /* "smilfit 0.9 (gfx950; 0.3 + SmilCameras.principal (0.4) + fragments, depth visibility (0.5) + mesh-free joints, kp3d fit (0.6) + kp2d fit (0.7) + visual hull (0.8) + distance fields)".  0.9 adds
+const char *smil_version(void);   /* "smilfit 0.10 (gfx950; 0.3 + SmilCameras.principal (0.4) + fragments, depth visibility (0.5) + mesh-free joints, kp3d fit (0.6) + kp2d fit (0.7) + visual hull (0.8) + distance fields (0.9) + hull meshes)".  0.10 adds
+                                    * the smil_hull_mesh_* entry points and changes no layout.  0.9 adds
                                     * smil_hull_edt, its workspace query and smil_field_sample and changes no layout.  0.8 adds
                                     * the smil_hull_* entry points with their own struct and changes no layout.  0.7 adds
                                     * smil_kp2d_fit_eval and its workspace query and changes no layout.  0.6 adds
@@ -1144,6 +1145,53 @@ int smil_hull_edt(const SmilHullGrid *g, const uint8_t *occ, int32_t invert, int
  * NULL d2_out, points, value or workspace; the grid and table checks of smil_hull_carve. */
 int smil_field_sample(const SmilHullGrid *g, const int32_t *d2_out, const int32_t *d2_in, const float *points, int32_t point_dim, int64_t P,
                       float *value, float *grad, void *workspace, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Hull meshes: a watertight, consistently oriented triangle mesh with vertex normals per frame of an occupancy grid - surface nets
+ * on the lattice of voxel centres (smilify_amd/csrc/hull_mesh.hip).  An extension: the reference has no counterpart.  No gradient;
+ * asynchronous on `stream`; ballots and gathers, no atomics: two calls give the same bits.  tests/hull_mesh_ref.py restates the rules.
+ *
+ * Samples.  Sample (i, j, k) is inside iff occ != 0; the lattice is padded by one layer of outside samples, index -1 and G on every
+ * axis (the grid's border is unoccupied, as for the surface), which closes the mesh where a hull touches the grid.
+ * Cubes.  Cube (i, j, k), every index in -1 .. G-1, spans samples i..i+1 x j..j+1 x k..k+1; its linear index is
+ * (i+1) + (Gx+1)((j+1) + (Gy+1)(k+1)).  A cube is active iff its 8 corners are not all of one kind.
+ * Vertices.  One per active cube, frames packed in order, ascending cube index within a frame.  The start position, in continuous
+ * index coordinates (sample i at u = i), is the mean of the midpoints of the cube's sign-changing edges - edges enumerated by axis
+ * a = x, y, z and, with u = (a+1) % 3, v = (a+2) % 3, corner offsets (u, v) = (0,0), (1,0), (0,1), (1,1); every summand is a multiple of
+ * 0.5, so the sum is exact, and there is one division.  (Crossings interpolated from the signed distance field would be the same
+ * midpoints: across a sign-changing lattice edge both squared distances are 1.  Hence occupancy is the only input.)
+ * Faces.  Cube (i, j, k) owns the lattice edges from sample (i, j, k) along +x, +y, +z.  An owned edge along a whose samples differ in
+ * kind emits the quad of the four cubes around it, cube offsets (du, dv) = (-1,-1), (0,-1), (0,0), (-1,0), in the reversed order
+ * when the edge's lower sample is the outside one - (v1 - v0) x (v2 - v0) then points out of the hull - as the triangles (q0,q1,q2),
+ * (q0,q2,q3).  Frames packed in order; within a frame ascending owner cube, then axis, then the two triangles.  Indices are
+ * frame-local int64.
+ * Relaxation.  weights (n_steps) HOST float64; step s moves every vertex by v += w_s (mean(neighbours) - v) and clamps it into its
+ * own cube [i,i+1] x [j,j+1] x [k,k+1].  The neighbours of a cube are the cubes across those of its faces whose 4 samples are not all
+ * of one kind, summed in the order -x, +x, -y, +y, -z, +z; a vertex without a neighbour stays.  Jacobi steps on float64 index
+ * coordinates, no fused multiply-add.
+ * Output.  verts = origin + (u + 0.5) * voxel_size per axis in float64 (three roundings, the frame's rows of the HOST tables as for
+ * smil_hull_carve), rounded once to float32.  normals (or NULL): per vertex, over its cube's 12 edges in the order above, every
+ * sign-changing edge names a quad; (v1 - v0) x (v2 - v0) of each of that quad's triangles that holds the vertex is added, on the
+ * final float64 index coordinates scaled by voxel_size; the sum is normalised (a zero sum gives (0,0,0)) and rounded once to float32.
+ *
+ * Calls.  smil_hull_mesh_count fills vert_offsets and face_offsets (N+1) int64 - frame n owns rows offsets[n] .. offsets[n+1] of the
+ * packed outputs, faces counted in triangles - and leaves masks and prefixes in the workspace (smil_hull_mesh_workspace_bytes(g)
+ * bytes, 12 bytes per 64 cubes; the table SIZES of g lay it out, the tables are not read).  The caller reads the two totals, sizes
+ * the outputs and a scratch buffer of smil_hull_mesh_scratch_bytes(n_verts, n_steps) bytes (the float64 positions - two buffers when
+ * n_steps > 0 - and 9 bytes per vertex; what a workspace sized before the count could only hold for the worst case of a vertex per
+ * cube), and calls smil_hull_mesh_write with the SAME g, occ and workspace and n_verts = vert_offsets[N], n_faces =
+ * face_offsets[N]: verts (n_verts,3) float32, normals (n_verts,3) float32 or NULL, faces (n_faces,3) int64.  Figures that are not
+ * the workspace's own leave the outputs unwritten (no kernel turns them into an index); both 0: nothing is launched.
+ * Errors (smil_last_error): the grid and table checks of smil_hull_carve; a NULL pointer; a non-finite weight; n_steps < 0; NULL
+ * weights with n_steps > 0; negative counts; a frame of 2^31 or more cubes, (Gx+1)(Gy+1)(Gz+1) (its vertex count could reach
+ * 2^31); more than 2^28 workgroups of 2 048 cubes in all.  N (Gx+1)(Gy+1)(Gz+1) may exceed 2^31: every global index is 64-bit.
+ * ---------------------------------------------------------------------------------------- */
+size_t smil_hull_mesh_workspace_bytes(const SmilHullGrid *g);
+int smil_hull_mesh_count(const SmilHullGrid *g, const uint8_t *occ, int64_t *vert_offsets, int64_t *face_offsets, void *workspace,
+                         void *stream);
+size_t smil_hull_mesh_scratch_bytes(int64_t n_verts, int32_t n_steps);
+int smil_hull_mesh_write(const SmilHullGrid *g, const uint8_t *occ, void *workspace, void *scratch, int64_t n_verts, int64_t n_faces,
+                         const double *weights, int32_t n_steps, float *verts, float *normals, int64_t *faces, void *stream);
 
 #ifdef __cplusplus
 }

@@ -43,6 +43,7 @@ EXPORTS = [
     "smil_hull_carve_workspace_bytes", "smil_hull_carve", "smil_hull_query", "smil_hull_stats", "smil_hull_surface_workspace_bytes",
     "smil_hull_surface_count", "smil_hull_surface_write",
     "smil_hull_edt_workspace_bytes", "smil_hull_edt", "smil_field_sample",
+    "smil_hull_mesh_workspace_bytes", "smil_hull_mesh_count", "smil_hull_mesh_scratch_bytes", "smil_hull_mesh_write",
 ]
 
 N_OBJS = 10
@@ -318,6 +319,13 @@ def load():
     lib.smil_hull_edt_workspace_bytes.restype = c_size_t
     lib.smil_hull_edt.argtypes = [POINTER(HullGrid), c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
     lib.smil_field_sample.argtypes = [POINTER(HullGrid), c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.smil_hull_mesh_workspace_bytes.argtypes = [POINTER(HullGrid)]
+    lib.smil_hull_mesh_workspace_bytes.restype = c_size_t
+    lib.smil_hull_mesh_count.argtypes = [POINTER(HullGrid), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.smil_hull_mesh_scratch_bytes.argtypes = [c_int64, c_int32]
+    lib.smil_hull_mesh_scratch_bytes.restype = c_size_t
+    lib.smil_hull_mesh_write.argtypes = [POINTER(HullGrid), c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p,
+                                         c_void_p, c_void_p]
     lib.smil_profile_enable.argtypes = [c_int32]
     lib.smil_profile_read.argtypes = [POINTER(c_float), POINTER(c_int32)]
     for name in EXPORTS:

@@ -1,4 +1,4 @@
-// What the translation units that work on a SmilHullGrid share (visual_hull.hip, distance_field.hip): the launch constants the
+// What the translation units that work on a SmilHullGrid share (visual_hull.hip, distance_field.hip, hull_mesh.hip): the launch constants the
 // grid's checks depend on, the device view of a grid, its validation, and the workspace layout that carries the caller's host tables.
 #pragma once
 #include <algorithm>

@@ -1800,6 +1800,30 @@ def hull_surface(spec: HullGridSpec, occ: torch.Tensor, want_index: bool = False
     return points, index, offsets
 
 
+# ---- hull meshes (csrc/hull_mesh.hip) --------------------------------------------------------------------------------------------
+def hull_mesh(spec: HullGridSpec, occ: torch.Tensor, weights=(), want_normals: bool = True):
+    """smil_hull_mesh_count / _write: ``(verts (Vt,3) float32, normals (Vt,3) float32 or None, faces (Ft,3) int64 frame-local, vert_offsets
+    (N+1,) int64, face_offsets (N+1,) int64)``.  ``weights``: the relaxation schedule, host float64.  The host waits ONCE, for the two
+    totals, to size the outputs; nothing is launched for the write when both are 0."""
+    occ = _hull_occ(spec, occ)
+    dev = occ.device
+    w = np.ascontiguousarray(np.asarray(tuple(weights), np.float64).reshape(-1))
+    lib = _lib.load()
+    grid = ctypes.byref(spec.struct)
+    ws = torch.empty(max(1, int(lib.smil_hull_mesh_workspace_bytes(grid))), dtype=torch.uint8, device=dev)
+    offsets = torch.empty(2, spec.N + 1, dtype=torch.int64, device=dev)
+    _lib.check(lib.smil_hull_mesh_count(grid, _ptr(occ), _ptr(offsets[0]), _ptr(offsets[1]), _ptr(ws), _stream()), "smil_hull_mesh_count")
+    n_verts, n_faces = (int(t) for t in offsets[:, -1].tolist())
+    verts = torch.empty(n_verts, 3, dtype=torch.float32, device=dev)
+    normals = torch.empty(n_verts, 3, dtype=torch.float32, device=dev) if want_normals else None
+    faces = torch.empty(n_faces, 3, dtype=torch.int64, device=dev)
+    # (both totals 0: the call validates its arguments and launches nothing)
+    scratch = torch.empty(max(1, int(lib.smil_hull_mesh_scratch_bytes(n_verts, len(w)))), dtype=torch.uint8, device=dev)
+    _lib.check(lib.smil_hull_mesh_write(grid, _ptr(occ), _ptr(ws), _ptr(scratch), n_verts, n_faces, w.ctypes.data if len(w) else None, len(w),
+                                        _ptr(verts), _ptr(normals), _ptr(faces), _stream()), "smil_hull_mesh_write")
+    return verts, normals, faces, offsets[0], offsets[1]
+
+
 # ---- distance fields (csrc/distance_field.hip) ----------------------------------------------------------------------------------
 def hull_edt(spec: HullGridSpec, occ: torch.Tensor, invert: bool = False, border: bool = False) -> torch.Tensor:
     """smil_hull_edt: occ (N,Gz,Gy,Gx) uint8 -> d2 (N,Gz,Gy,Gx) int32, the squared voxel distance of every voxel to the nearest one with

@@ -52,14 +52,21 @@ def _gpu_f32(t: torch.Tensor) -> torch.Tensor:
 
 def sample_points_from_meshes(meshes: Meshes, num_samples: int = 10000, return_normals: bool = False, return_textures: bool = False):
     """(N, num_samples, 3) points on the surfaces of ``meshes``, faces chosen with probability proportional to their area
-    (pytorch3d.ops.sample_points_from_meshes, trainer.py:376).  No gradient: raises if the vertices require one."""
-    if return_normals or return_textures:
-        raise NotImplementedError("sample_points_from_meshes: return_normals / return_textures are not supported")
+    (pytorch3d.ops.sample_points_from_meshes, trainer.py:376).  ``return_normals``: ``(points, normals)``, the normals (N, num_samples, 3)
+    being the unit normals of the faces the points were drawn on (pytorch3d's rule), gathered from the sampler's face indices with
+    tensor operations.  No gradient: raises if the vertices require one."""
+    if return_textures:
+        raise NotImplementedError("sample_points_from_meshes: return_textures is not supported")
     vl = meshes.verts_list()
     if any(v.requires_grad for v in vl):
         raise NotImplementedError("sample_points_from_meshes: the HIP sampler has no gradient; detach the vertices first")
-    pts, _ = sample_points_with_faces(meshes, num_samples)
-    return pts
+    pts, face = sample_points_with_faces(meshes, num_samples)
+    if not return_normals:
+        return pts
+    first = torch.tensor([0] + meshes.num_faces_per_mesh()[:-1], dtype=torch.int64).cumsum(0).to(face.device)
+    tri = _gpu_f32(meshes.verts_packed())[meshes.faces_packed().to(face.device)[face.to(torch.int64) + first[:, None]]]  # (N,S,3,3)
+    n = torch.linalg.cross(tri[..., 1, :] - tri[..., 0, :], tri[..., 2, :] - tri[..., 0, :])
+    return pts, n / n.norm(dim=-1, keepdim=True).clamp(min=torch.finfo(torch.float32).tiny)
 
 
 def sample_points_with_faces(meshes: Meshes, num_samples: int, seed: Optional[int] = None):

@@ -4,7 +4,8 @@ A voxel belongs to the hull if its CENTRE projects onto foreground in the views 
 grid per frame in one HIP kernel (csrc/visual_hull.hip, one byte per voxel out; nothing of size voxels x views is ever stored);
 ``VisualHull`` turns the occupancy into what the 3-D side of the library takes - exact index statistics (count, centroid, covariance,
 bounds), the packed surface voxels, a fixed-size surface sample for ``fit3d.chamfer_distance`` / ``pointnet2``, and the tight bounds for a
-second, finer carve.  ``query_points`` runs the same test at arbitrary points ("does this triangulated keypoint lie inside every outline").
+second, finer carve; ``VisualHull.extract_mesh`` the watertight triangle mesh with vertex normals (csrc/hull_mesh.hip) that ``fit3d``,
+``mesh3d`` and ``sdf`` are written against.  ``query_points`` runs the same test at arbitrary points ("does this triangulated keypoint lie inside every outline").
 
 Conventions (include/smilfit.h, "Visual hull"): the camera arithmetic is that of ``KeypointFitter2D`` (float64 on the float32 tables,
 ``(y, x)`` pixels of an ``image_size`` x ``image_size`` screen; with ``cameras.opencv_to_pinhole_camera(R, t, K, S)`` and ``image_size=S`` the
@@ -21,7 +22,7 @@ views.  ``origin`` and ``voxel_size`` are host values (a device tensor is copied
 """
 from __future__ import annotations
 
-from typing import NamedTuple, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -52,6 +53,79 @@ def _image_size(image_size) -> int:
     if int(image_size) != image_size or int(image_size) < 1:
         raise ValueError(f"image_size must be a positive integer, got {image_size}")
     return int(image_size)
+
+
+def gibson_steps(n: int) -> Tuple[float, ...]:
+    """``n`` steps of weight 0.5: Gibson's constrained SurfaceNets relaxation (smooths, and shrinks)."""
+    return (0.5,) * int(n)
+
+
+def taubin_steps(n: int) -> Tuple[float, ...]:
+    """``n`` pairs (0.5, -0.53): Taubin's lambda | mu smoothing, which keeps the volume."""
+    return (0.5, -0.53) * int(n)
+
+
+class HullMesh:
+    """The triangle meshes of a hull's frames, packed: ``verts (Vt,3)`` float32 (world units), ``normals (Vt,3)`` float32 unit vertex
+    normals pointing out of the hull (None unless asked for), ``faces (Ft,3)`` int64 indices into the frame's OWN vertices,
+    ``vert_offsets`` / ``face_offsets (N+1,)`` int64: frame ``n`` owns ``verts[vert_offsets[n]:vert_offsets[n+1]]`` and
+    ``faces[face_offsets[n]:face_offsets[n+1]]``.  Every frame's mesh is closed and consistently oriented (each directed edge is met by
+    its reverse).  There is no gradient through the extraction."""
+
+    def __init__(self, verts, normals, faces, vert_offsets, face_offsets):
+        self.verts, self.normals, self.faces = verts, normals, faces
+        self.vert_offsets, self.face_offsets = vert_offsets, face_offsets
+        self._bounds = None
+
+    def __len__(self) -> int:
+        return int(self.vert_offsets.shape[0]) - 1
+
+    def _host_offsets(self):
+        if self._bounds is None:  # (one copy for both tables)
+            self._bounds = torch.stack([self.vert_offsets, self.face_offsets]).tolist()
+        return self._bounds
+
+    def _split(self, packed, which: int) -> List[torch.Tensor]:
+        off = self._host_offsets()[which]
+        return [packed[off[n]:off[n + 1]] for n in range(len(self))]
+
+    def verts_list(self) -> List[torch.Tensor]:
+        return self._split(self.verts, 0)
+
+    def normals_list(self) -> List[torch.Tensor]:
+        if self.normals is None:
+            raise ValueError("this mesh was extracted with return_normals=False")
+        return self._split(self.normals, 0)
+
+    def faces_list(self) -> List[torch.Tensor]:
+        return self._split(self.faces, 1)
+
+    def to_meshes(self, keep: Optional[Sequence[int]] = None):
+        """``mesh3d.Meshes`` of the frames (``keep``: of these frames, in this order), built from lists.  A frame without a hull has no
+        mesh: it raises a ValueError that names the frame - select the others with ``keep``."""
+        from .mesh3d import Meshes
+
+        frames = list(range(len(self))) if keep is None else [int(n) for n in keep]
+        verts, faces = self.verts_list(), self.faces_list()
+        for n in frames:
+            if not -len(self) <= n < len(self):
+                raise ValueError(f"to_meshes: frame {n} outside the hull's {len(self)} frames")
+            if verts[n].shape[0] == 0:
+                raise ValueError(f"to_meshes: frame {n} has an empty hull and no mesh; pass keep= to select the other frames")
+        return Meshes(verts=[verts[n] for n in frames], faces=[faces[n] for n in frames])
+
+    def volume(self) -> torch.Tensor:
+        """(N,) float64: the signed volume every frame's mesh encloses (the divergence theorem's sum over its triangles, in float64 tensor
+        operations on the device); positive, since the faces point outwards; 0 for a frame without a hull."""
+        N = len(self)
+        out = torch.zeros(N, dtype=torch.float64, device=self.verts.device)
+        if self.faces.shape[0] == 0:
+            return out
+        rows = torch.arange(self.faces.shape[0], device=self.faces.device)
+        frame = torch.searchsorted(self.face_offsets[1:].contiguous(), rows, right=True)
+        tri = self.verts.to(torch.float64)[self.faces + self.vert_offsets[frame][:, None]]
+        six = (tri[:, 0] * torch.linalg.cross(tri[:, 1], tri[:, 2])).sum(-1)
+        return out.index_add_(0, frame, six) / 6.0
 
 
 class VisualHull:
@@ -106,6 +180,18 @@ class VisualHull:
         values = torch.zeros(points.shape[0], dtype=torch.float32, device=points.device)
         out, _, _ = engine.sample_vertices(points, values, offsets.to(torch.int32), N, int(num_samples), seed)
         return out
+
+    def extract_mesh(self, relax_steps: Sequence[float] = (), return_normals: bool = True) -> HullMesh:
+        """The hull's boundary as a ``HullMesh``: surface nets on the lattice of voxel centres (include/smilfit.h, "Hull meshes").  One
+        vertex per cube of 8 neighbouring voxel centres that are not all of one kind, one quad (two triangles) per pair of 6-neighbours
+        of which exactly one is occupied - the grid's border counting as unoccupied, so a hull that touches the grid is closed there.
+        ``relax_steps``: a schedule of relaxation weights, each step moving every vertex towards the mean of its neighbours and back
+        into its own cube - ``gibson_steps(n)`` smooths and shrinks, ``taubin_steps(n)`` smooths and keeps the volume; the default ``()``
+        leaves the vertices at the mean of their cube's edge crossings (which cuts corners: a single voxel becomes a cube of a third
+        of its edge).  Voxels that touch only along an edge share that edge four-fold: the mesh stays closed and oriented, but is not a
+        manifold there.  ``return_normals``: area-weighted unit vertex normals.  No gradient.  This call SYNCHRONISES the host once,
+        to read the two totals and size the outputs."""
+        return HullMesh(*engine.hull_mesh(self._spec, self.occupancy, relax_steps, want_normals=return_normals))
 
     def distance_transform(self, inside: bool = False, border: bool = False) -> torch.Tensor:
         """(N,Gz,Gy,Gx) int32: the exact squared Euclidean distance, in voxels, from every voxel to the nearest occupied one (``inside``:
