@@ -53,7 +53,9 @@ int smil_model_create(const SmilModelDesc *desc, SmilModel **out);
 void smil_model_destroy(SmilModel *m);
 int smil_model_dims(const SmilModel *m, int32_t dims[4]); /* V,F,J,nB */
 const char *smil_last_error(void);
-const char *smil_version(void);   /* "smilfit 0.10 (gfx950; 0.3 + SmilCameras.principal (0.4) + fragments, depth visibility (0.5) + mesh-free joints, kp3d fit (0.6) + kp2d fit (0.7) + visual hull (0.8) + distance fields (0.9) + hull meshes)".  0.10 adds
+const char *smil_version(void);   /* "smilfit 0.11 (gfx950; 0.3 + SmilCameras.principal (0.4) + fragments, depth visibility (0.5) + mesh-free joints, kp3d fit (0.6) + kp2d fit (0.7) + visual hull (0.8) + distance fields (0.9) + hull meshes + point-mesh distances)".  0.11 adds
+                                    * smil_point_face_distance / smil_face_point_distance / smil_point_mesh_backward and their
+                                    * workspace query and changes no layout.  0.10 adds
                                     * the smil_hull_mesh_* entry points and changes no layout.  0.9 adds
                                     * smil_hull_edt, its workspace query and smil_field_sample and changes no layout.  0.8 adds
                                     * the smil_hull_* entry points with their own struct and changes no layout.  0.7 adds
@@ -1192,6 +1194,50 @@ int smil_hull_mesh_count(const SmilHullGrid *g, const uint8_t *occ, int64_t *ver
 size_t smil_hull_mesh_scratch_bytes(int64_t n_verts, int32_t n_steps);
 int smil_hull_mesh_write(const SmilHullGrid *g, const uint8_t *occ, void *workspace, void *scratch, int64_t n_verts, int64_t n_faces,
                          const double *weights, int32_t n_steps, float *verts, float *normals, int64_t *faces, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Exact distances between point clouds and triangle meshes with gradients (smilify_amd/csrc/point_mesh.hip).  An extension: the
+ * reference has no counterpart (pytorch3d names the operation loss.point_mesh_face_distance).  The distance is the true Euclidean
+ * distance to the CLOSED triangle by its seven Voronoi regions; degenerate faces are legal (an edge of zero length acts as its end
+ * point, a face of zero area as the nearest of its three segments, three equal vertices as a point); pytorch3d's min_triangle_area
+ * rule is not reproduced.  A brute-force float32 search over ALL faces decides WHICH face (strict <, a float32 tie goes to the
+ * smaller index whatever `splits`), its value is the same formula in float64 from the float32 inputs, rounded once.  No float
+ * atomics: two calls give the same bits.  tests/point_mesh_ref.py restates the rules.
+ *
+ * Inputs of all three: N meshes packed - verts (n_verts,3), faces (F_total,3) int32 into the packed verts, face_off (N+1) int32 the
+ * first face of every mesh, max_faces the most faces of one mesh - and a padded cloud points (N,P,3) with lengths (N) int32 or NULL
+ * (every cloud has P points).  A coordinate that is NaN, inf or above 3e38 in magnitude is not usable: a face with such a vertex, or
+ * with a vertex index outside [0, n_verts), never wins, and such a point is treated as a non-finite one, in every call.
+ * face_off, max_faces (and vert_off, max_verts) are the caller's statement about the meshes and are trusted: they size the launches,
+ * and a max_faces / max_verts below a mesh's true count leaves that mesh's last rows of the outputs unwritten, without an error.
+ * splits: over how many workgroups the candidates of one query are divided, 0 = chosen from the sizes.
+ * workspace: smil_point_mesh_workspace_bytes(N, F_total, P, n_verts) bytes (0: bad sizes), one layout for the three calls.
+ *
+ * smil_point_face_distance: for every point the nearest face of its mesh: dist2 (N,P), face (N,P) int32 within the mesh, bary (N,P,3)
+ * of the closest point (b >= 0, sum 1).  A non-finite point, a point at or beyond its cloud's length and a mesh in which no face
+ * can win give +inf, -1 and 0.
+ * smil_face_point_distance: for every face the nearest point of its mesh's cloud: dist2 (F_total), point (F_total) int32 within the
+ * cloud, bary (F_total,3) of the closest point ON THE FACE.  A cloud of length 0 (or without a finite point) gives +inf, -1 and 0.
+ * smil_point_mesh_backward: the gradient of sum_r g_r dist2_r over the records of one direction (by_face 0: idx = face (N,P) and g
+ * (N,P); 1: idx = point (F_total) and g (F_total)).  With c the closest point of the recorded pair, recomputed in float64, and
+ * e = p - c: d_points += 2 g e, d_verts[v_k] += -2 g b_k e (c minimises over the triangle; at a region boundary the selected
+ * region's one-sided value).  Records with idx -1, out of range, or naming a point or face with an unusable coordinate add
+ * nothing.  The barycentrics of the forward are not an input: they are outputs for the caller's use only.  d_points (N,P,3) and d_verts (n_verts,3) are
+ * written in full.  vert_off (N+1) int32: the first vertex of every mesh; max_verts: the most vertices of one mesh.  Shared sums
+ * are int64 fixed point with a unit that follows the mesh's largest addend: scaling every input by a power of two scales the
+ * gradients exactly, and a permutation of the points leaves d_verts bit-identical.
+ * ---------------------------------------------------------------------------------------- */
+size_t smil_point_mesh_workspace_bytes(int32_t N, int32_t F_total, int32_t P, int32_t n_verts);
+int smil_point_face_distance(const float *verts, int32_t n_verts, const int32_t *faces, const int32_t *face_off, int32_t N,
+                             int32_t F_total, int32_t max_faces, const float *points, int32_t P, const int32_t *lengths, int32_t splits,
+                             float *dist2, int32_t *face, float *bary, void *workspace, void *stream);
+int smil_face_point_distance(const float *verts, int32_t n_verts, const int32_t *faces, const int32_t *face_off, int32_t N,
+                             int32_t F_total, int32_t max_faces, const float *points, int32_t P, const int32_t *lengths, int32_t splits,
+                             float *dist2, int32_t *point, float *bary, void *workspace, void *stream);
+int smil_point_mesh_backward(const float *verts, int32_t n_verts, const int32_t *faces, const int32_t *face_off, const int32_t *vert_off,
+                             int32_t N, int32_t F_total, int32_t max_faces, int32_t max_verts, const float *points, int32_t P,
+                             const int32_t *lengths, int32_t by_face, const int32_t *idx, const float *g, float *d_points,
+                             float *d_verts, void *workspace, void *stream);
 
 #ifdef __cplusplus
 }

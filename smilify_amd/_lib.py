@@ -44,6 +44,7 @@ EXPORTS = [
     "smil_hull_surface_count", "smil_hull_surface_write",
     "smil_hull_edt_workspace_bytes", "smil_hull_edt", "smil_field_sample",
     "smil_hull_mesh_workspace_bytes", "smil_hull_mesh_count", "smil_hull_mesh_scratch_bytes", "smil_hull_mesh_write",
+    "smil_point_mesh_workspace_bytes", "smil_point_face_distance", "smil_face_point_distance", "smil_point_mesh_backward",
 ]
 
 N_OBJS = 10
@@ -326,6 +327,13 @@ def load():
     lib.smil_hull_mesh_scratch_bytes.restype = c_size_t
     lib.smil_hull_mesh_write.argtypes = [POINTER(HullGrid), c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p,
                                          c_void_p, c_void_p]
+    lib.smil_point_mesh_workspace_bytes.argtypes = [c_int32] * 4
+    lib.smil_point_mesh_workspace_bytes.restype = c_size_t
+    _pm = [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32] + [c_void_p] * 5
+    lib.smil_point_face_distance.argtypes = _pm
+    lib.smil_face_point_distance.argtypes = _pm
+    lib.smil_point_mesh_backward.argtypes = [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32,
+                                             c_void_p, c_int32] + [c_void_p] * 6
     lib.smil_profile_enable.argtypes = [c_int32]
     lib.smil_profile_read.argtypes = [POINTER(c_float), POINTER(c_int32)]
     for name in EXPORTS:

@@ -1,0 +1,451 @@
+// Exact distances between point clouds and triangle meshes, both directions, with gradients, for gfx950.
+//
+// An extension (the reference never asks "how far is this point from this surface"): pytorch3d names the operation
+// loss.point_mesh_face_distance; the definition here is the true Euclidean distance to the CLOSED triangle, degenerate faces included
+// (point_tri.h), without pytorch3d's min_triangle_area rule.
+//
+//  * k_pm_extent    the largest finite |coordinate| of every mesh's face vertices and points, as the bits of a float (atomicMax).  The
+//                   search runs in the mesh's FRAME: every coordinate times 2^-ex, the power of two that brings that largest value
+//                   below 1.  Scaling by a power of two is exact, so the float32 search sees the same roundings whatever the data's
+//                   unit, its degree-4 products (va, vb, vc of point_tri.h) neither overflow nor underflow for data of any extent, and
+//                   scaling all inputs by a power of two changes no selection.
+//  * k_pm_table     thread per face: {v0, e1 = v1 - v0, e2 = v2 - v0} in the frame as three float4, written once per call.  A face
+//                   with a non-finite vertex or a vertex index outside [0, n_verts) gets v0 = NaN: its distance is NaN, which is never
+//                   < the running minimum, so it never wins.
+//  * k_pm_points    points -> faces.  lane = one point; face tiles stream through LDS and every lane reads the same face (three
+//                   ds_read_b128 broadcasts against ~110 VALU instructions per point).  Running minimum of the float32 squared
+//                   distance with a strict <.  The face range may be split over blockIdx.y; the splits merge through a 64-bit atomicMin
+//                   of {bits of d^2, face}: d^2 >= 0, so the bits order like the values, the result does not depend on the order
+//                   and a tie goes to the smaller face index, as one sequential scan gives (k_chamfer_nn's merge, mesh3d.hip).
+//  * k_pm_faces     faces -> points: the same device function with the roles swapped.  lane = one face (its table entry in registers),
+//                   the cloud's points stream through LDS in the frame, the point range may be split, the same merge.
+//  * k_pm_finish    thread per query (point or face): the winner's closest point once more in float64 from the float32 inputs (the
+//                   float32 search decides WHICH, the value is the float64 formula's, rounded once), the barycentrics and the index.
+//                   No winner (a non-finite or padded point, a mesh without a face that can win, an empty cloud): +inf, -1, 0.
+//  * k_pm_bwd_*     the gradient of records (query, index) with an upstream gradient g per record: with c the closest point (float64,
+//                   recomputed at the recorded pair) and e = p - c, d/dp = 2 g e and d/dv_k = -2 g b_k e.  The side that owns the
+//                   record (the point, points -> faces) writes directly; vertices (shared by faces, faces hit by many points) and the
+//                   points picked by many faces are summed as int64 fixed point whose unit follows the mesh's largest addend and its
+//                   record count (common.h "order-independent scatter sums"): no float atomics, two calls give equal bits, a
+//                   permutation of the points leaves the vertex gradients bit-identical.
+//
+// There is no BVH, grid or cull: the exact minimum over ALL faces is the contract, as in raycast.hip.
+#include <algorithm>
+
+#include "common.h"
+#include "point_tri.h"
+
+#define PM_BLOCK 256
+#define PM_TILE 128  // faces (48 B) or points (16 B) staged in LDS per step
+
+struct PmArgs {
+    const float *verts;       // (n_verts, 3) packed
+    const int *faces;         // (F_total, 3) into the packed verts
+    const int *face_off;      // (N + 1)
+    const int *vert_off;      // (N + 1), the backward only
+    const float *points;      // (N, P, 3)
+    const int *lengths;       // (N) or NULL: P
+    float4 *table;            // (F_total, 3) {v0, e1, e2} in the mesh's frame
+    unsigned int *ext;        // (N) bits of the largest finite |coordinate| of mesh n
+    unsigned long long *key;  // (N, P) or (F_total): {bits of d^2 in the frame, index}, all ones: none
+    float *dist2;             // (N, P) or (F_total)
+    int *idx;                 // (N, P) face within its mesh or (F_total) point within its cloud, -1: none
+    float *bary;              // (N, P, 3) or (F_total, 3)
+    const float *g;           // upstream gradient per record
+    long long *acc_v;         // (n_verts, 3)
+    long long *acc_p;         // (N, P, 3)
+    unsigned int *dmax;       // (N) bits of the largest |2 g e| component of mesh n's records
+    float *d_points;          // (N, P, 3)
+    float *d_verts;           // (n_verts, 3)
+    int N, P, n_verts, F_total, splits, by_face;
+};
+
+struct PmMesh { int f0, F, len; };  // first packed face, faces, points of mesh n
+
+__device__ __forceinline__ PmMesh pm_mesh(const PmArgs &a, int n) {
+    PmMesh m;
+    m.f0 = min(max(a.face_off[n], 0), a.F_total);
+    m.F = min(max(a.face_off[n + 1], m.f0), a.F_total) - m.f0;
+    m.len = a.lengths ? min(max(a.lengths[n], 0), a.P) : a.P;
+    return m;
+}
+
+__device__ __forceinline__ float pm_finite_abs(float x) { return fabsf(x) <= 3.0e38f ? fabsf(x) : 0.f; }  // NaN, inf: 0
+
+// the three vertex ids of packed face j, or false when one is outside [0, n_verts)
+__device__ __forceinline__ bool pm_face_ids(const PmArgs &a, size_t j, int (&id)[3]) {
+    id[0] = a.faces[3 * j]; id[1] = a.faces[3 * j + 1]; id[2] = a.faces[3 * j + 2];
+    return (unsigned)id[0] < (unsigned)a.n_verts && (unsigned)id[1] < (unsigned)a.n_verts && (unsigned)id[2] < (unsigned)a.n_verts;
+}
+
+// (every lane of every wave reaches fix_record_max)
+__global__ void __launch_bounds__(256) k_pm_extent(PmArgs a) {
+    const int n = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
+    const PmMesh m = pm_mesh(a, n);
+    float big = 0.f;
+    int id[3];
+    if (t < m.F && pm_face_ids(a, (size_t)m.f0 + t, id)) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float *v = a.verts + 3 * (size_t)id[k];
+            big = fmaxf(big, fmaxf(pm_finite_abs(v[0]), fmaxf(pm_finite_abs(v[1]), pm_finite_abs(v[2]))));
+        }
+    }
+    if (t < m.len) {
+        const float *p = a.points + ((size_t)n * a.P + t) * 3;
+        big = fmaxf(big, fmaxf(pm_finite_abs(p[0]), fmaxf(pm_finite_abs(p[1]), pm_finite_abs(p[2]))));
+    }
+    fix_record_max(&a.ext[n], big);
+}
+
+// the frame of mesh n: coordinates are multiplied by 2^pm_frame (exactly)
+__device__ __forceinline__ int pm_frame(const PmArgs &a, int n) { return -fix_max_exp(a.ext[n]); }
+
+__global__ void __launch_bounds__(256) k_pm_table(PmArgs a) {
+    const int n = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
+    const PmMesh m = pm_mesh(a, n);
+    if (t >= m.F) return;
+    const size_t j = (size_t)m.f0 + t;
+    const int sh = pm_frame(a, n);
+    const float nan = __builtin_nanf("");
+    float4 v0 = make_float4(nan, nan, nan, 0.f), e1 = make_float4(0.f, 0.f, 0.f, 0.f), e2 = e1;
+    int id[3];
+    if (pm_face_ids(a, j, id)) {
+        float c[9];
+        bool finite = true;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const float x = a.verts[3 * (size_t)id[k / 3] + k % 3];
+            finite &= fabsf(x) <= 3.0e38f;
+            c[k] = ldexpf(x, sh);
+        }
+        if (finite) {
+            v0 = make_float4(c[0], c[1], c[2], 0.f);
+            e1 = make_float4(c[3] - c[0], c[4] - c[1], c[5] - c[2], 0.f);
+            e2 = make_float4(c[6] - c[0], c[7] - c[1], c[8] - c[2], 0.f);
+        }
+    }
+    a.table[3 * j] = v0;
+    a.table[3 * j + 1] = e1;
+    a.table[3 * j + 2] = e2;
+}
+
+// A point in the frame; NaN (it never wins and nothing wins for it) when a coordinate is not usable: NaN, inf or above 3e38, as for
+// the vertices of a face, whatever the frame does to it.
+__device__ __forceinline__ void pm_load_point(const float *p, int sh, float &x, float &y, float &z) {
+    const bool usable = fabsf(p[0]) <= 3.0e38f && fabsf(p[1]) <= 3.0e38f && fabsf(p[2]) <= 3.0e38f;
+    const float nan = __builtin_nanf("");
+    x = usable ? ldexpf(p[0], sh) : nan; y = usable ? ldexpf(p[1], sh) : nan; z = usable ? ldexpf(p[2], sh) : nan;
+}
+
+__device__ __forceinline__ void pm_put_key(const PmArgs &a, size_t at, float best, int bi) {
+    if (!(best < __builtin_inff())) return;  // nothing won in this split
+    const unsigned long long kv = ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(uint32_t)bi;
+    if (a.splits == 1) a.key[at] = kv;
+    else atomicMin(&a.key[at], kv);
+}
+
+// rows [begin, end) of `count` rows that split blockIdx.y of a.splits takes, in whole tiles
+__device__ __forceinline__ void pm_split_range(const PmArgs &a, int count, int &begin, int &end) {
+    const int chunk = ((count + a.splits - 1) / a.splits + PM_TILE - 1) / PM_TILE * PM_TILE;
+    begin = (int)min((long long)blockIdx.y * chunk, (long long)count);
+    end = min(count, begin + chunk);
+}
+
+__global__ void __launch_bounds__(PM_BLOCK) k_pm_points(PmArgs a) {
+    __shared__ float4 tile[3 * PM_TILE];
+    const int n = blockIdx.z;
+    const PmMesh m = pm_mesh(a, n);
+    const int q = blockIdx.x * PM_BLOCK + threadIdx.x;
+    if ((int)(blockIdx.x * PM_BLOCK) >= m.len) return;  // (block-uniform, as the next)
+    int f_begin, f_end;
+    pm_split_range(a, m.F, f_begin, f_end);
+    if (f_begin >= f_end) return;
+    const int sh = pm_frame(a, n);
+    const float *Q = a.points + (size_t)n * a.P * 3;
+    float px, py, pz;  // (a lane behind the cloud's end repeats its last point and writes nothing)
+    pm_load_point(Q + 3 * (size_t)min(q, m.len - 1), sh, px, py, pz);
+    float best = __builtin_inff();
+    int bi = 0x7FFFFFFF;
+    const float4 *table = a.table + 3 * (size_t)m.f0;
+    for (int f0 = f_begin; f0 < f_end; f0 += PM_TILE) {
+        const int cnt = min(PM_TILE, f_end - f0);
+        __syncthreads();
+        for (int i = threadIdx.x; i < 3 * cnt; i += PM_BLOCK) tile[i] = table[3 * (size_t)f0 + i];
+        __syncthreads();
+        for (int j = 0; j < cnt; ++j) {
+            const float4 v0 = tile[3 * j], e1 = tile[3 * j + 1], e2 = tile[3 * j + 2];
+            const TriPoint<float> r = closest_on_triangle<float>(px - v0.x, py - v0.y, pz - v0.z, e1.x, e1.y, e1.z, e2.x, e2.y, e2.z);
+            const bool take = r.dist2 < best;
+            best = take ? r.dist2 : best;
+            bi = take ? f0 + j : bi;
+        }
+    }
+    if (q < m.len) pm_put_key(a, (size_t)n * a.P + q, best, bi);
+}
+
+__global__ void __launch_bounds__(PM_BLOCK) k_pm_faces(PmArgs a) {
+    __shared__ float4 tile[PM_TILE];
+    const int n = blockIdx.z;
+    const PmMesh m = pm_mesh(a, n);
+    const int t = blockIdx.x * PM_BLOCK + threadIdx.x;
+    if ((int)(blockIdx.x * PM_BLOCK) >= m.F) return;  // (block-uniform, as the next)
+    int p_begin, p_end;
+    pm_split_range(a, m.len, p_begin, p_end);
+    if (p_begin >= p_end) return;
+    const int sh = pm_frame(a, n);
+    const size_t j = (size_t)m.f0 + min(t, m.F - 1);
+    const float4 v0 = a.table[3 * j], e1 = a.table[3 * j + 1], e2 = a.table[3 * j + 2];
+    const float *Q = a.points + (size_t)n * a.P * 3;
+    float best = __builtin_inff();
+    int bi = 0x7FFFFFFF;
+    for (int p0 = p_begin; p0 < p_end; p0 += PM_TILE) {
+        const int cnt = min(PM_TILE, p_end - p0);
+        __syncthreads();
+        if ((int)threadIdx.x < cnt) {
+            float x, y, z;
+            pm_load_point(Q + 3 * (size_t)(p0 + threadIdx.x), sh, x, y, z);
+            tile[threadIdx.x] = make_float4(x, y, z, 0.f);
+        }
+        __syncthreads();
+#pragma unroll 2
+        for (int i = 0; i < cnt; ++i) {
+            const float4 p = tile[i];
+            const TriPoint<float> r = closest_on_triangle<float>(p.x - v0.x, p.y - v0.y, p.z - v0.z, e1.x, e1.y, e1.z, e2.x, e2.y, e2.z);
+            const bool take = r.dist2 < best;
+            best = take ? r.dist2 : best;
+            bi = take ? p0 + i : bi;
+        }
+    }
+    if (t < m.F) pm_put_key(a, (size_t)m.f0 + t, best, bi);
+}
+
+// The closest point of packed face j to point p of mesh n's cloud in float64, from the float32 inputs.  false: the pair does not
+// exist, or one of its coordinates is not usable.
+__device__ __forceinline__ bool pm_pair64(const PmArgs &a, int n, const PmMesh &m, int face, int point, TriPoint<double> &r, double (&e)[3],
+                                          int (&id)[3]) {
+    if (face < 0 || face >= m.F || point < 0 || point >= m.len) return false;
+    if (!pm_face_ids(a, (size_t)m.f0 + face, id)) return false;
+    const float *p = a.points + ((size_t)n * a.P + point) * 3;
+    const float *v0 = a.verts + 3 * (size_t)id[0], *v1 = a.verts + 3 * (size_t)id[1], *v2 = a.verts + 3 * (size_t)id[2];
+    bool usable = true;  // (the search never pairs these, a hand-made record of the backward may)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) usable &= fabsf(p[k]) <= 3.0e38f && fabsf(v0[k]) <= 3.0e38f && fabsf(v1[k]) <= 3.0e38f && fabsf(v2[k]) <= 3.0e38f;
+    if (!usable) return false;
+    const double e1[3] = {(double)v1[0] - v0[0], (double)v1[1] - v0[1], (double)v1[2] - v0[2]};
+    const double e2[3] = {(double)v2[0] - v0[0], (double)v2[1] - v0[1], (double)v2[2] - v0[2]};
+    const double ap[3] = {(double)p[0] - v0[0], (double)p[1] - v0[1], (double)p[2] - v0[2]};
+    r = closest_on_triangle<double>(ap[0], ap[1], ap[2], e1[0], e1[1], e1[2], e2[0], e2[1], e2[2]);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) e[k] = ap[k] - r.v * e1[k] - r.w * e2[k];
+    return true;
+}
+
+// query t of mesh n is point t (a.by_face == 0) or face t; `at` its row in the outputs and keys, or false when there is no such query
+__device__ __forceinline__ bool pm_query(const PmArgs &a, int n, const PmMesh &m, int t, size_t &at) {
+    at = a.by_face ? (size_t)m.f0 + t : (size_t)n * a.P + t;
+    return t < (a.by_face ? m.F : a.P);
+}
+
+__global__ void __launch_bounds__(256) k_pm_finish(PmArgs a) {
+    const int n = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
+    const PmMesh m = pm_mesh(a, n);
+    size_t at;
+    if (!pm_query(a, n, m, t, at)) return;
+    const unsigned long long kv = a.key[at];
+    const int other = (int)(uint32_t)(kv & 0xFFFFFFFFull);
+    TriPoint<double> r;
+    double e[3];
+    int id[3];
+    const bool none = kv == ~0ull || !pm_pair64(a, n, m, a.by_face ? t : other, a.by_face ? other : t, r, e, id);
+    a.dist2[at] = none ? __builtin_inff() : (float)r.dist2;
+    a.idx[at] = none ? -1 : other;
+    a.bary[3 * at] = none ? 0.f : (float)r.b0;
+    a.bary[3 * at + 1] = none ? 0.f : (float)r.v;
+    a.bary[3 * at + 2] = none ? 0.f : (float)r.w;
+}
+
+// ---- backward -----------------------------------------------------------------------------------------------------------------
+// record t of mesh n: the pair, its barycentrics and the point's gradient 2 g e (float64); false: the record contributes nothing
+__device__ __forceinline__ bool pm_record(const PmArgs &a, int n, const PmMesh &m, int t, size_t &at, int &point, double (&b)[3], double (&ge)[3],
+                                          int (&id)[3]) {
+    if (!pm_query(a, n, m, t, at)) return false;
+    const int other = a.idx[at];
+    point = a.by_face ? other : t;
+    TriPoint<double> r;
+    double e[3];
+    if (!pm_pair64(a, n, m, a.by_face ? t : other, point, r, e, id)) return false;
+    const double g2 = 2.0 * (double)a.g[at];
+    b[0] = r.b0; b[1] = r.v; b[2] = r.w;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) ge[k] = g2 * e[k];
+    return true;
+}
+
+// Unit exponent of mesh n's sums: every addend is a component of 2 g e times a barycentric <= 1, and at most three addends per record
+// (a face may name one vertex three times) of at most max(P, F_n) records meet in one element.
+__device__ __forceinline__ int pm_fix_exp(const PmArgs &a, int n, const PmMesh &m) {
+    return fix_unit_exp(fix_max_exp(a.dmax[n]), 3ll * max(a.by_face ? m.F : a.P, 1) + 1);
+}
+
+__global__ void __launch_bounds__(256) k_pm_bwd_max(PmArgs a) {
+    const int n = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
+    const PmMesh m = pm_mesh(a, n);
+    size_t at;
+    int point, id[3];
+    double b[3], ge[3];
+    float big = 0.f;
+    if (pm_record(a, n, m, t, at, point, b, ge, id))
+        big = fmaxf(pm_finite_abs((float)ge[0]), fmaxf(pm_finite_abs((float)ge[1]), pm_finite_abs((float)ge[2])));
+    fix_record_max(&a.dmax[n], big);
+}
+
+__global__ void __launch_bounds__(256) k_pm_bwd_add(PmArgs a) {
+    const int n = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
+    const PmMesh m = pm_mesh(a, n);
+    size_t at;
+    int point, id[3];
+    double b[3], ge[3];
+    const bool ok = pm_record(a, n, m, t, at, point, b, ge, id);
+    if (!a.by_face && t < a.P) {  // the point owns its record
+        float *d = a.d_points + ((size_t)n * a.P + t) * 3;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) d[k] = ok ? (float)ge[k] : 0.f;
+    }
+    if (!ok) return;
+    const int fix = pm_fix_exp(a, n, m);
+    if (a.by_face) {
+        long long *acc = a.acc_p + ((size_t)n * a.P + point) * 3;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) fix_add(&acc[k], ge[k], fix);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        long long *acc = a.acc_v + 3 * (size_t)id[c];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) fix_add(&acc[k], -b[c] * ge[k], fix);
+    }
+}
+
+// thread t of mesh n: vertex t of the mesh, and (faces -> points) point t of its cloud
+__global__ void __launch_bounds__(256) k_pm_bwd_out(PmArgs a) {
+    const int n = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
+    const PmMesh m = pm_mesh(a, n);
+    const int fix = pm_fix_exp(a, n, m);
+    const int v0 = min(max(a.vert_off[n], 0), a.n_verts), v1 = min(max(a.vert_off[n + 1], v0), a.n_verts);
+    if (t < v1 - v0) {
+        const size_t v = (size_t)v0 + t;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) a.d_verts[3 * v + k] = fix_read(a.acc_v[3 * v + k], fix);
+    }
+    if (a.by_face && t < a.P) {
+        const size_t p = (size_t)n * a.P + t;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) a.d_points[3 * p + k] = fix_read(a.acc_p[3 * p + k], fix);
+    }
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------------------
+static size_t pm_layout(int N, int F_total, int P, int n_verts, char *base, PmArgs &a) {
+    Workspace w{base};
+    a.table = w.take<float4>((size_t)F_total * 3);
+    a.key = w.take<unsigned long long>(std::max((size_t)N * P, (size_t)F_total));
+    a.ext = w.take<unsigned int>((size_t)N);
+    a.dmax = w.take<unsigned int>((size_t)N);
+    a.acc_v = w.take<long long>((size_t)n_verts * 3);
+    a.acc_p = w.take<long long>((size_t)N * P * 3);
+    return w.used;
+}
+
+static bool pm_sizes_ok(int64_t N, int64_t F_total, int64_t P, int64_t n_verts) {
+    return N > 0 && N <= 65535 && F_total > 0 && P > 0 && n_verts > 0 && N * P <= 0x7FFFFFFF / 4 && F_total <= 0x7FFFFFFF / 4 &&
+           n_verts <= 0x7FFFFFFF / 4;
+}
+
+extern "C" size_t smil_point_mesh_workspace_bytes(int32_t N, int32_t F_total, int32_t P, int32_t n_verts) {
+    PmArgs a;
+    return pm_sizes_ok(N, F_total, P, n_verts) ? pm_layout(N, F_total, P, n_verts, nullptr, a) : 0;
+}
+
+static int pm_fill(PmArgs &a, const char *who, const float *verts, int32_t n_verts, const int32_t *faces, const int32_t *face_off, int32_t N,
+                   int32_t F_total, int32_t max_faces, const float *points, int32_t P, const int32_t *lengths, void *workspace) {
+    SMIL_REQUIRE(verts && faces && face_off && points && workspace, "%s: null argument", who);
+    SMIL_REQUIRE(pm_sizes_ok(N, F_total, P, n_verts), "%s: bad sizes N=%d F=%d P=%d V=%d", who, N, F_total, P, n_verts);
+    SMIL_REQUIRE(max_faces >= 1 && max_faces <= F_total, "%s: max_faces=%d outside 1 .. F=%d", who, max_faces, F_total);
+    a = PmArgs{};
+    pm_layout(N, F_total, P, n_verts, (char *)workspace, a);
+    a.verts = verts; a.faces = (const int *)faces; a.face_off = (const int *)face_off; a.points = points; a.lengths = (const int *)lengths;
+    a.N = N; a.P = P; a.n_verts = n_verts; a.F_total = F_total;
+    return SMIL_OK;
+}
+
+// the forward of either direction: `rows` queries and `cols` candidates per mesh at most
+static int pm_forward(PmArgs &a, int max_faces, int32_t splits, hipStream_t stream) {
+    const int rows = a.by_face ? max_faces : a.P, cols = a.by_face ? a.P : max_faces;
+    const size_t n_keys = a.by_face ? (size_t)a.F_total : (size_t)a.N * a.P;
+    const int qblocks = ceil_div(rows, PM_BLOCK);
+    // splits: enough workgroups for the whole GPU (>= 2048) while every split still streams >= 2 tiles
+    const int max_split = std::max(1, cols / (2 * PM_TILE));
+    a.splits = splits > 0 ? splits : std::max(1, std::min(std::min(max_split, 65535), ceil_div(2048, qblocks * a.N)));
+    SMIL_HIP(hipMemsetAsync(a.key, 0xFF, n_keys * sizeof(unsigned long long), stream));
+    SMIL_HIP(hipMemsetAsync(a.ext, 0, (size_t)a.N * sizeof(unsigned int), stream));
+    hipLaunchKernelGGL(k_pm_extent, dim3(ceil_div(std::max(max_faces, a.P), 256), a.N), dim3(256), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_pm_table, dim3(ceil_div(max_faces, 256), a.N), dim3(256), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    const dim3 grid(qblocks, a.splits, a.N);
+    if (a.by_face) hipLaunchKernelGGL(k_pm_faces, grid, dim3(PM_BLOCK), 0, stream, a);
+    else hipLaunchKernelGGL(k_pm_points, grid, dim3(PM_BLOCK), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_pm_finish, dim3(ceil_div(rows, 256), a.N), dim3(256), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    return SMIL_OK;
+}
+
+extern "C" int smil_point_face_distance(const float *verts, int32_t n_verts, const int32_t *faces, const int32_t *face_off, int32_t N,
+                                        int32_t F_total, int32_t max_faces, const float *points, int32_t P, const int32_t *lengths,
+                                        int32_t splits, float *dist2, int32_t *face, float *bary, void *workspace, void *stream) {
+    PmArgs a;
+    const int rc = pm_fill(a, "smil_point_face_distance", verts, n_verts, faces, face_off, N, F_total, max_faces, points, P, lengths, workspace);
+    if (rc != SMIL_OK) return rc;
+    SMIL_REQUIRE(dist2 && face && bary, "smil_point_face_distance: null output");
+    SMIL_REQUIRE(splits >= 0 && splits <= 65535, "smil_point_face_distance: splits=%d outside 0 .. 65535", splits);
+    a.dist2 = dist2; a.idx = (int *)face; a.bary = bary; a.by_face = 0;
+    return pm_forward(a, max_faces, splits, (hipStream_t)stream);
+}
+
+extern "C" int smil_face_point_distance(const float *verts, int32_t n_verts, const int32_t *faces, const int32_t *face_off, int32_t N,
+                                        int32_t F_total, int32_t max_faces, const float *points, int32_t P, const int32_t *lengths,
+                                        int32_t splits, float *dist2, int32_t *point, float *bary, void *workspace, void *stream) {
+    PmArgs a;
+    const int rc = pm_fill(a, "smil_face_point_distance", verts, n_verts, faces, face_off, N, F_total, max_faces, points, P, lengths, workspace);
+    if (rc != SMIL_OK) return rc;
+    SMIL_REQUIRE(dist2 && point && bary, "smil_face_point_distance: null output");
+    SMIL_REQUIRE(splits >= 0 && splits <= 65535, "smil_face_point_distance: splits=%d outside 0 .. 65535", splits);
+    a.dist2 = dist2; a.idx = (int *)point; a.bary = bary; a.by_face = 1;
+    return pm_forward(a, max_faces, splits, (hipStream_t)stream);
+}
+
+extern "C" int smil_point_mesh_backward(const float *verts, int32_t n_verts, const int32_t *faces, const int32_t *face_off,
+                                        const int32_t *vert_off, int32_t N, int32_t F_total, int32_t max_faces, int32_t max_verts,
+                                        const float *points, int32_t P, const int32_t *lengths, int32_t by_face, const int32_t *idx,
+                                        const float *g, float *d_points, float *d_verts, void *workspace, void *stream_) {
+    PmArgs a;
+    const int rc = pm_fill(a, "smil_point_mesh_backward", verts, n_verts, faces, face_off, N, F_total, max_faces, points, P, lengths, workspace);
+    if (rc != SMIL_OK) return rc;
+    SMIL_REQUIRE(vert_off && idx && g && d_points && d_verts, "smil_point_mesh_backward: null argument");
+    SMIL_REQUIRE(max_verts >= 1 && max_verts <= n_verts, "smil_point_mesh_backward: max_verts=%d outside 1 .. V=%d", max_verts, n_verts);
+    hipStream_t stream = (hipStream_t)stream_;
+    a.vert_off = (const int *)vert_off; a.idx = (int *)idx; a.g = g; a.d_points = d_points; a.d_verts = d_verts; a.by_face = by_face != 0;
+    const int rows = a.by_face ? max_faces : P;
+    SMIL_HIP(hipMemsetAsync(a.dmax, 0, (size_t)N * sizeof(unsigned int), stream));
+    SMIL_HIP(hipMemsetAsync(a.acc_v, 0, (size_t)n_verts * 3 * sizeof(long long), stream));
+    if (a.by_face) SMIL_HIP(hipMemsetAsync(a.acc_p, 0, (size_t)N * P * 3 * sizeof(long long), stream));
+    hipLaunchKernelGGL(k_pm_bwd_max, dim3(ceil_div(rows, 256), N), dim3(256), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_pm_bwd_add, dim3(ceil_div(rows, 256), N), dim3(256), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_pm_bwd_out, dim3(ceil_div(std::max(max_verts, a.by_face ? P : 1), 256), N), dim3(256), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    return SMIL_OK;
+}

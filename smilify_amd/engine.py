@@ -976,6 +976,72 @@ def ray_diameters(verts: torch.Tensor, faces: torch.Tensor, origins: torch.Tenso
     return diam, ray_t
 
 
+# ---- exact point <-> triangle-mesh distances (point_mesh.hip) --------------------------------------------------------------------
+class MeshTables(NamedTuple):
+    """N packed meshes as the point-mesh kernels take them (``mesh3d.Meshes.face_tables``): faces (F_total,3) int32 into the packed
+    vertices, face_off / vert_off (N+1) int32 on the device, and the sizes the launches need on the host."""
+    faces: torch.Tensor
+    face_off: torch.Tensor
+    vert_off: torch.Tensor
+    n_meshes: int
+    n_faces: int
+    max_faces: int
+    n_verts: int
+    max_verts: int
+
+
+def _point_mesh_inputs(who: str, verts: torch.Tensor, mt: MeshTables, points: torch.Tensor, lengths: Optional[torch.Tensor]):
+    if verts.dtype != torch.float32 or points.dtype != torch.float32:
+        raise ValueError(f"{who}: verts and points must be float32")
+    if tuple(verts.shape) != (mt.n_verts, 3) or points.dim() != 3 or points.shape[0] != mt.n_meshes or points.shape[2] != 3:
+        raise ValueError(f"{who}: verts ({mt.n_verts},3) packed and points ({mt.n_meshes},P,3), got {tuple(verts.shape)} and "
+                         f"{tuple(points.shape)}")
+    if mt.n_faces < 1 or points.shape[1] < 1:
+        raise ValueError(f"{who}: needs at least one face and one point per cloud (F={mt.n_faces}, P={int(points.shape[1])})")
+    if lengths is not None:
+        if tuple(lengths.shape) != (mt.n_meshes,):
+            raise ValueError(f"{who}: lengths ({mt.n_meshes},), got {tuple(lengths.shape)}")
+        lengths = lengths.to(device=verts.device, dtype=torch.int32).contiguous()
+    lib = _lib.load()
+    nbytes = int(lib.smil_point_mesh_workspace_bytes(mt.n_meshes, mt.n_faces, int(points.shape[1]), mt.n_verts))
+    if nbytes == 0:
+        raise _lib.SmilError(f"{who}: sizes N={mt.n_meshes} F={mt.n_faces} P={int(points.shape[1])} V={mt.n_verts} are not supported")
+    return lib, verts.contiguous(), points.contiguous(), lengths, torch.empty(nbytes, dtype=torch.uint8, device=verts.device)
+
+
+def point_mesh_distance(verts: torch.Tensor, mt: MeshTables, points: torch.Tensor, lengths: Optional[torch.Tensor] = None,
+                        by_face: bool = False, splits: int = 0):
+    """The nearest face of its mesh for every point of points (N,P,3) (``by_face`` False: dist2 (N,P), face (N,P) int32, bary (N,P,3)),
+    or the nearest point of its mesh's cloud for every face (True: dist2 (F_total), point (F_total) int32, bary (F_total,3) of the
+    closest point on the face).  -1 and +inf where there is none.  ``splits``: 0 = automatic (smil_point_face_distance)."""
+    who = "face_point_distance" if by_face else "point_face_distance"
+    lib, verts, points, lengths, ws = _point_mesh_inputs(who, verts, mt, points, lengths)
+    rows = (mt.n_faces,) if by_face else (mt.n_meshes, int(points.shape[1]))
+    dist2 = torch.empty(rows, device=verts.device, dtype=torch.float32)
+    idx = torch.empty(rows, device=verts.device, dtype=torch.int32)
+    bary = torch.empty(rows + (3,), device=verts.device, dtype=torch.float32)
+    fn = lib.smil_face_point_distance if by_face else lib.smil_point_face_distance
+    _lib.check(fn(_ptr(verts), mt.n_verts, _ptr(mt.faces), _ptr(mt.face_off), mt.n_meshes, mt.n_faces, mt.max_faces, _ptr(points),
+                  int(points.shape[1]), _ptr(lengths), int(splits), _ptr(dist2), _ptr(idx), _ptr(bary), _ptr(ws), _stream()), f"smil_{who}")
+    return dist2, idx, bary
+
+
+def point_mesh_backward(verts: torch.Tensor, mt: MeshTables, points: torch.Tensor, lengths: Optional[torch.Tensor], idx: torch.Tensor,
+                        g: torch.Tensor, by_face: bool = False):
+    """(d_points (N,P,3), d_verts (n_verts,3)) of sum_r g_r dist2_r over the records ``idx`` of one direction of point_mesh_distance."""
+    lib, verts, points, lengths, ws = _point_mesh_inputs("point_mesh_backward", verts, mt, points, lengths)
+    rows = (mt.n_faces,) if by_face else (mt.n_meshes, int(points.shape[1]))
+    if tuple(idx.shape) != rows or idx.dtype != torch.int32 or tuple(g.shape) != rows or g.dtype != torch.float32:
+        raise ValueError(f"point_mesh_backward: idx int32 and g float32 of shape {rows}")
+    d_points = torch.empty_like(points)
+    d_verts = torch.empty_like(verts)
+    _lib.check(lib.smil_point_mesh_backward(_ptr(verts), mt.n_verts, _ptr(mt.faces), _ptr(mt.face_off), _ptr(mt.vert_off), mt.n_meshes,
+                                            mt.n_faces, mt.max_faces, mt.max_verts, _ptr(points), int(points.shape[1]), _ptr(lengths),
+                                            int(bool(by_face)), _ptr(idx.contiguous()), _ptr(g.contiguous()), _ptr(d_points), _ptr(d_verts),
+                                            _ptr(ws), _stream()), "smil_point_mesh_backward")
+    return d_points, d_verts
+
+
 # ---- PointNet++ set-abstraction operations (pointnet2.hip) ---------------------------------------------------------------------
 def _check_cloud(what: str, name: str, t: torch.Tensor, B: Optional[int] = None, last: Optional[int] = 3) -> None:
     if not (isinstance(t, torch.Tensor) and t.dim() == 3 and t.dtype == torch.float32 and (last is None or t.shape[2] == last)

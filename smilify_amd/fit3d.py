@@ -302,6 +302,70 @@ def mesh_laplacian_smoothing(meshes: Meshes, method: str = "uniform"):
     return mesh_regularisers(meshes, False, False, True)[2]
 
 
+# ---- exact point <-> mesh distances (csrc/point_mesh.hip; an extension, pytorch3d's loss.point_mesh_face_distance) -----------------
+class _PointMeshFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, verts_packed, points, mt, lengths, by_face):
+        v, p = _gpu_f32(verts_packed), _gpu_f32(points)
+        dist2, idx, _ = engine.point_mesh_distance(v, mt, p, lengths, by_face)
+        ctx.save_for_backward(v, p, idx)
+        ctx.call = (mt, lengths, by_face)
+        idx = idx.long()
+        ctx.mark_non_differentiable(idx)
+        return dist2, idx
+
+    @staticmethod
+    def backward(ctx, g, _):
+        v, p, idx = ctx.saved_tensors
+        mt, lengths, by_face = ctx.call
+        d_points, d_verts = engine.point_mesh_backward(v, mt, p, lengths, idx, g.to(torch.float32).contiguous(), by_face)
+        return d_verts, d_points, None, None, None
+
+
+def _point_mesh(meshes: Meshes, points, lengths, by_face: bool):
+    if not (isinstance(points, torch.Tensor) and points.dim() == 3 and points.shape[2] == 3 and points.shape[0] == len(meshes)):
+        raise ValueError(f"points ({len(meshes)},P,3) for {len(meshes)} meshes")
+    engine.require_gpu(meshes.device)
+    return _PointMeshFn.apply(meshes.verts_packed(), points, meshes.face_tables(), lengths, by_face)
+
+
+def point_face_distance(meshes: Meshes, points: torch.Tensor, lengths: Optional[torch.Tensor] = None):
+    """(dist2 (N,P), face (N,P) int64): for every point of ``points`` (N,P,3) the squared Euclidean distance to the nearest closed
+    triangle of its mesh and that face's index within the mesh.  Differentiable in ``points`` and in the meshes' vertices (through
+    ``offset_verts`` too); the indices carry no gradient.  Points at or beyond ``lengths`` (N), non-finite points and meshes without a
+    usable face give ``inf`` and -1 and receive no gradient.  Exact: a brute-force search, no acceleration structure."""
+    return _point_mesh(meshes, points, lengths, False)
+
+
+def face_point_distance(meshes: Meshes, points: torch.Tensor, lengths: Optional[torch.Tensor] = None):
+    """(dist2 (F_total), point (F_total) int64): for every face of the packed meshes the squared distance to the nearest point of its
+    mesh's cloud and that point's index within the cloud (-1 and ``inf`` for a cloud without a finite point).  Differentiable as
+    ``point_face_distance``."""
+    return _point_mesh(meshes, points, lengths, True)
+
+
+def point_mesh_face_distance(meshes: Meshes, points: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pytorch3d.loss.point_mesh_face_distance's normalisation on the exact distances: the mean over each cloud's points of the
+    point -> face term plus the mean over each mesh's faces of the face -> point term, averaged over the batch.  Entries without a
+    partner (index -1) add 0.  The true distance to the closed triangle; pytorch3d's min_triangle_area rule is not reproduced."""
+    N, P = len(meshes), int(points.shape[1])
+    d_pf, face = point_face_distance(meshes, points, lengths)
+    d_fp, point = face_point_distance(meshes, points, lengths)
+    mt = meshes.face_tables()
+    n_pts = torch.full((N,), float(P), device=d_pf.device) if lengths is None else lengths.to(d_pf.device, torch.float32).clamp(min=1.0)
+    n_faces = (mt.face_off[1:] - mt.face_off[:-1]).to(torch.float32).clamp(min=1.0)
+    mesh_of_face = torch.repeat_interleave(torch.arange(N, device=d_pf.device), (mt.face_off[1:] - mt.face_off[:-1]).long(),
+                                           output_size=mt.n_faces)
+    per_cloud = torch.where(face >= 0, d_pf, torch.zeros_like(d_pf)).sum(1) / n_pts
+    per_mesh = torch.zeros(N, device=d_pf.device, dtype=d_fp.dtype).index_add(0, mesh_of_face,
+                                                                               torch.where(point >= 0, d_fp, torch.zeros_like(d_fp)))
+    return (per_cloud.sum() + (per_mesh / n_faces).sum()) / N
+
+
+def _masked_mean(dist2: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    return torch.where(idx >= 0, dist2, torch.zeros_like(dist2)).mean()
+
+
 # ---- model ----------------------------------------------------------------------------------------------------------------------
 def get_meshes(verts, faces, device="cuda"):
     return Meshes(verts=verts, faces=faces).to(device)
@@ -388,7 +452,9 @@ class SMALParamGroup:
 
 class Stage:
     """trainer.py:294-509: one optimisation stage (Adam over a scheme's parameters, chamfer to 3000 fresh target samples per
-    iteration plus the mesh regularisers, and the SDF-guided term when ``w_sdf`` > 0 and both value sets are given)."""
+    iteration plus the mesh regularisers, and the SDF-guided term when ``w_sdf`` > 0 and both value sets are given).  An extension:
+    ``loss_weights["w_surface"]`` > 0 (absent from ``default_weights``: off) adds ``comps["surface"]``, the mean exact squared distance
+    of the iteration's target samples to the source surface plus that of the source vertices to the target surfaces."""
 
     def __init__(self, nits: int, scheme: str, smal_3d_fitter: SMAL3DFitter, target_meshes: Meshes, mesh_names=(), name="optimise",
                  loss_weights=None, lr=1e-3, out_dir="static_fits_output", custom_lrs=None, device="cuda", plot_normals=False,
@@ -448,6 +514,12 @@ class Stage:
             comps["sdf"] = SDF_distance(src_pts, tgt_pts, src_sdf, tgt_sdf, k=50, batch_reduction="mean", point_reduction="mean",
                                         norm=2, single_directional=False)
             loss = loss + self.loss_weights["w_sdf"] * comps["sdf"]
+        w_surface = self.loss_weights.get("w_surface", 0)
+        if w_surface > 0:  # an extension: exact distances to the surfaces instead of chamfer between samples and vertices
+            to_source = _masked_mean(*point_face_distance(src_mesh, target_verts))  # reaches the model through the barycentrics
+            to_target = _masked_mean(*point_face_distance(self.target_meshes, src_mesh.verts_padded()))  # ... through the points
+            comps["surface"] = to_source + to_target
+            loss = loss + w_surface * comps["surface"]
         return loss, comps
 
     def step(self, epoch):
@@ -581,6 +653,8 @@ def build_parser():
     p.add_argument("--use_sdf", action="store_true", help="add the SDF-guided term (needs --sdf_dir)")
     p.add_argument("--sdf_dir", type=str, default=None,
                    help="directory of NAME_sdf.npz / NAME_sdf.pkl files (vertex_sdf) for the source model and the target meshes")
+    p.add_argument("--w_surface", type=float, default=0.0,
+                   help="weight of the exact point-to-surface term of every stage (an extension; 0: off, nothing changes)")
     return p
 
 
@@ -628,13 +702,17 @@ def main(args):
             tv = check_and_load_sdf_values(names, args.sdf_dir, args.device)
             if all(v is not None for v in tv):  # (the reference hands over the list as it is and fails on a None inside)
                 kw.update(sdf_values=tv, source_sdf_values=source_sdf_values)
+        surface = dict(w_surface=float(args.w_surface)) if getattr(args, "w_surface", 0) > 0 else None
         if stage_options is not None:
             for stage_name, skw in stage_options.items():
+                if surface is not None:  # under the stage's own weights
+                    skw = dict(skw, loss_weights=dict(surface, **(skw.get("loss_weights") or {})))
                 manager.add_stage(Stage(name=f"{stage_name}_batch_{b}" if n_batches > 1 else stage_name, **skw, **kw))
                 if b == 0:
                     stage_names.append(stage_name)
         else:
-            manager.add_stage(Stage(scheme=args.scheme, nits=args.nits, lr=args.lr, name=f"stage_batch_{b}" if n_batches > 1 else "stage", **kw))
+            manager.add_stage(Stage(scheme=args.scheme, nits=args.nits, lr=args.lr, name=f"stage_batch_{b}" if n_batches > 1 else "stage",
+                                    loss_weights=surface, **kw))
             if b == 0:
                 stage_names.append("stage")
         manager.run()

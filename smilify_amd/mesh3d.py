@@ -7,11 +7,14 @@
   need: the regulariser ``Topology`` of a shared face array and the float64 cumulative-area table used by surface sampling.
 * ``Topology(faces, V)`` builds, once per face array: unique edges ``(v0 < v1)``, normal-consistency pairs ``(v0, v1, a, b)``,
   the Laplacian neighbour CSR with ``1/deg`` and the vertex -> pair incidence CSR.
+* ``closest_points(meshes, points)`` (an extension): for every point the exact closest point of its mesh's surface - squared
+  distance, face, barycentrics - on the kernels of csrc/point_mesh.hip: the registration metric.
 """
 from __future__ import annotations
 
 import hashlib
 import os
+from collections import namedtuple
 from typing import List, Optional
 
 import numpy as np
@@ -227,6 +230,17 @@ class Meshes:
             self._shared["topology"] = topology_for(f0, nv[0])
         return self._shared["topology"]
 
+    def face_tables(self) -> "engine.MeshTables":
+        """The packed int32 faces with the face and vertex offsets of every mesh, as the point-mesh kernels take them: built from the
+        shapes without a host synchronisation, cached with the face arrays (kept by offset_verts())."""
+        if "face_tables" not in self._shared:
+            nv, nf = self.num_verts_per_mesh(), self.num_faces_per_mesh()
+            dev = self.device
+            off = lambda counts: torch.from_numpy(np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)).to(dev)  # noqa: E731
+            self._shared["face_tables"] = engine.MeshTables(self.faces_packed().to(device=dev, dtype=torch.int32).contiguous(), off(nf),
+                                                            off(nv), len(self), int(sum(nf)), int(max(nf)), int(sum(nv)), int(max(nv)))
+        return self._shared["face_tables"]
+
     def sampling_tables(self):
         """(faces_packed int32, face_off int32, cum_area float64) on the device: per-mesh inclusive cumulative face areas divided
         by the mesh's total, computed on the host in float64 from the current vertices and cached (targets are fixed for a run)."""
@@ -248,3 +262,23 @@ class Meshes:
                 torch.from_numpy(np.asarray(off, np.int32)).to(dev),
                 torch.from_numpy(np.concatenate(cum)).to(dev))
         return self._sampling
+
+
+ClosestPoints = namedtuple("ClosestPoints", "dist2 face bary points")
+
+
+def closest_points(meshes: Meshes, points: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> ClosestPoints:
+    """For every point of ``points`` (N,P,3) the closest point of the surface of its mesh: squared distance (N,P), face within the mesh
+    (N,P) int64, barycentrics (N,P,3) and the closest points themselves (N,P,3).  ``dist2.sqrt()`` is the surface error per point - the
+    registration metric.  Exact (the true Euclidean distance to the closed triangles, a brute-force search over every face, the value
+    in float64); not differentiable (``fit3d.point_face_distance`` is); no host synchronisation.  ``lengths`` (N): points at or beyond
+    a cloud's length, non-finite points and meshes without a usable face give ``inf``, face -1 and zeros."""
+    engine.require_gpu(meshes.device)
+    verts = meshes.verts_packed().detach().to(torch.float32).contiguous()
+    pts = points.detach().to(device=verts.device, dtype=torch.float32).contiguous()
+    mt = meshes.face_tables()
+    dist2, face, bary = engine.point_mesh_distance(verts, mt, pts, lengths)
+    face = face.long()
+    first = mt.face_off[:-1].long()[:, None]
+    tri = verts[mt.faces.long()[(face.clamp(min=0) + first)]]  # (N,P,3,3)
+    return ClosestPoints(dist2, face, bary, (bary[..., None] * tri).sum(-2))
