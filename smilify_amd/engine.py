@@ -31,6 +31,11 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _workspace(nbytes: int, device) -> torch.Tensor:
+    """Caller-owned scratch of the size a ``smil_*_workspace_bytes`` query returned."""
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+
+
 def _f32(t: Optional[torch.Tensor], device) -> Optional[torch.Tensor]:
     if t is None:
         return None
@@ -56,7 +61,7 @@ class DeviceModel:
     def __init__(self, tables: SmilModelTables, device):
         self.device = require_gpu(device)
         self.tables = tables
-        lib = _lib.load()
+        lib = _lib.checked()
         t = tables
         arrs = dict(
             v_template=np.ascontiguousarray(t.v_template, np.float32),
@@ -82,7 +87,7 @@ class DeviceModel:
         d.static_joints = 1 if t.static_joints else 0
         handle = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(lib.smil_model_create(ctypes.byref(d), ctypes.byref(handle)), "smil_model_create")
+            lib.smil_model_create(ctypes.byref(d), ctypes.byref(handle))
         self.handle = handle
         self.V, self.F, self.J, self.nB = t.V, t.F, t.J, t.nB
         self.static_joints = bool(t.static_joints)
@@ -116,7 +121,7 @@ class DeviceModel:
         key = self._ws_key()
         ws = _SHARED_WS.get(key)
         if ws is None or ws.numel() < need:
-            ws = _SHARED_WS[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws = _SHARED_WS[key] = _workspace(need, self.device)
         self._ws = ws
         return ws
 
@@ -172,7 +177,7 @@ class CameraSet:
         return c
 
 
-TIE_RULES = {"depth_face_id": 0, "reference_queue": 1}
+TIE_RULES = {"depth_face_id": _lib.TIE_DEPTH_FACE_ID, "reference_queue": _lib.TIE_REFERENCE_QUEUE}
 
 
 class ClipDepth:
@@ -229,8 +234,7 @@ def clip_depth_backward(cams: "CameraSet", clip_depth: ClipDepth, d_verts: torch
     """``d_verts`` (frames,V,3) += the depth gradients of ``clip_depth`` carried through the cameras (separate-kernel route)."""
     N = d_verts.shape[0] * cams.views
     c = cams.struct(N)
-    _lib.check(_lib.load().smil_clip_depth_backward(ctypes.byref(c), ctypes.byref(clip_depth._struct), N, d_verts.shape[1], _ptr(d_verts),
-                                                    _stream()), "smil_clip_depth_backward")
+    _lib.checked().smil_clip_depth_backward(ctypes.byref(c), ctypes.byref(clip_depth._struct), N, d_verts.shape[1], _ptr(d_verts), _stream())
 
 
 def raster_settings(blur=BLUR_RADIUS, sigma=SIGMA, K=FACES_PER_PIXEL, tie_rule="depth_face_id") -> _lib.RasterSettings:
@@ -290,10 +294,9 @@ def lbs_forward(model: DeviceModel, beta, theta, trans=None, logscale=None, btra
         ndc = f(N, V, 3) if project.get("ndc", True) else None
         yx = f(N, J, 2) if project.get("yx", True) else None
         c = cams.struct(N)
-        _lib.check(_lib.load().smil_lbs_forward_project(model.handle, ctypes.byref(i), ctypes.byref(o), ctypes.byref(c), _ptr(ndc), _ptr(yx), _stream()),
-                   "smil_lbs_forward_project")
+        _lib.checked().smil_lbs_forward_project(model.handle, ctypes.byref(i), ctypes.byref(o), ctypes.byref(c), _ptr(ndc), _ptr(yx), _stream())
     else:
-        _lib.check(_lib.load().smil_lbs_forward(model.handle, ctypes.byref(i), ctypes.byref(o), _stream()), "smil_lbs_forward")
+        _lib.checked().smil_lbs_forward(model.handle, ctypes.byref(i), ctypes.byref(o), _stream())
     if ndc is not None:
         out["ndc"] = ndc
     if yx is not None:
@@ -310,6 +313,7 @@ FUSED_LBS_BACKWARD = os.environ.get("SMILFIT_UNFUSED_LBS") != "1"  # the fit ite
 
 def lbs_backward_ndc_supported(model: DeviceModel, nB_used: int, views: int) -> bool:
     """Whether ``lbs_backward(..., ndc_upstream=...)`` (one kernel from the image plane) handles this model and call."""
+    # a predicate, not a status: asked of the raw library, where a non-zero answer raises nothing
     return bool(_lib.load().smil_lbs_backward_ndc_supported(model.handle, int(nB_used), int(views)))
 
 
@@ -375,13 +379,11 @@ def lbs_backward(model: DeviceModel, saved: Dict, d_verts, d_joints, need_beta=T
         if up.get("clip_depth") is not None:
             gs.clip_depth = up["clip_depth"].pointer()
         c = cams.struct(B * cams.views)
-        _lib.check(_lib.load().smil_lbs_backward_ndc(model.handle, ctypes.byref(i), ctypes.byref(o), ctypes.byref(gs), ctypes.byref(c),
-                                                     _ptr(up.get("d_ndc")), _ptr(up.get("d_ndc_scale")), _ptr(up.get("d_yx")),
-                                                     _ptr(g["d_joints"]), _ptr(up.get("d_fov_img")), _stream()),
-                   "smil_lbs_backward_ndc")
+        _lib.checked().smil_lbs_backward_ndc(model.handle, ctypes.byref(i), ctypes.byref(o), ctypes.byref(gs), ctypes.byref(c), _ptr(up.get("d_ndc")),
+                                             _ptr(up.get("d_ndc_scale")), _ptr(up.get("d_yx")), _ptr(g["d_joints"]), _ptr(up.get("d_fov_img")),
+                                             _stream())
         return g
-    _lib.check(_lib.load().smil_lbs_backward(model.handle, ctypes.byref(i), ctypes.byref(o), ctypes.byref(gs), _stream()),
-               "smil_lbs_backward")
+    _lib.checked().smil_lbs_backward(model.handle, ctypes.byref(i), ctypes.byref(o), ctypes.byref(gs), _stream())
     return g
 
 
@@ -394,7 +396,7 @@ def project(cams: CameraSet, pts: torch.Tensor, want_ndc=True, want_yx=True):
     ndc = torch.empty(N, P, 3, dtype=torch.float32, device=pts.device) if want_ndc else None
     yx = torch.empty(N, P, 2, dtype=torch.float32, device=pts.device) if want_yx else None
     c = cams.struct(N)
-    _lib.check(_lib.load().smil_project(ctypes.byref(c), _ptr(pts), P, _ptr(ndc), _ptr(yx), _stream()), "smil_project")
+    _lib.checked().smil_project(ctypes.byref(c), _ptr(pts), P, _ptr(ndc), _ptr(yx), _stream())
     return ndc, yx
 
 
@@ -408,8 +410,8 @@ def project_backward(cams: CameraSet, pts: torch.Tensor, d_ndc=None, d_yx=None, 
     if d_fov_img is None:
         d_fov_img = torch.zeros(N, dtype=torch.float32, device=pts.device)
     c = cams.struct(N)
-    _lib.check(_lib.load().smil_project_backward(ctypes.byref(c), _ptr(pts), P, _ptr(d_ndc), _ptr(d_yx), _ptr(d_pts),
-                                                 _ptr(d_fov_img), int(accumulate), _ptr(d_ndc_scale), _stream()), "smil_project_backward")
+    _lib.checked().smil_project_backward(ctypes.byref(c), _ptr(pts), P, _ptr(d_ndc), _ptr(d_yx), _ptr(d_pts), _ptr(d_fov_img), int(accumulate),
+                                         _ptr(d_ndc_scale), _stream())
     return d_pts, d_fov_img
 
 
@@ -420,8 +422,7 @@ def project_verts_and_joints(cams: CameraSet, verts: torch.Tensor, joints: torch
     ndc = torch.empty(N, V, 3, dtype=torch.float32, device=verts.device)
     yx = torch.empty(N, J, 2, dtype=torch.float32, device=verts.device)
     c = cams.struct(N)
-    _lib.check(_lib.load().smil_project2(ctypes.byref(c), _ptr(verts), V, _ptr(ndc), None, _ptr(joints), J, None, _ptr(yx), _stream()),
-               "smil_project2")
+    _lib.checked().smil_project2(ctypes.byref(c), _ptr(verts), V, _ptr(ndc), None, _ptr(joints), J, None, _ptr(yx), _stream())
     return ndc, yx
 
 
@@ -432,9 +433,8 @@ def project_backward_verts_and_joints(cams: CameraSet, verts, d_ndc, joints, d_y
     N = verts.shape[0] * cams.views
     d_verts, d_joints = torch.empty_like(verts), torch.empty_like(joints)
     c = cams.struct(N)
-    _lib.check(_lib.load().smil_project_backward2(ctypes.byref(c), _ptr(verts), V, _ptr(d_ndc), None, _ptr(d_verts), _ptr(joints), J, None,
-                                                  _ptr(d_yx), _ptr(d_joints), _ptr(d_fov_img), _ptr(d_ndc_scale), _stream()),
-               "smil_project_backward2")
+    _lib.checked().smil_project_backward2(ctypes.byref(c), _ptr(verts), V, _ptr(d_ndc), None, _ptr(d_verts), _ptr(joints), J, None, _ptr(d_yx),
+                                          _ptr(d_joints), _ptr(d_fov_img), _ptr(d_ndc_scale), _stream())
     return d_verts, d_joints
 
 
@@ -443,18 +443,17 @@ def fit_epilogue(cfg, pose, trans, betas, mean_betas, betas_prec, mask, objs, d_
     """prior_losses + sil_objective + fov_reduce in one launch (the tail of a fit iteration)."""
     n_img = 0 if loss_img is None else loss_img.numel()
     c = None if cams is None else cams.struct(d_fov_img.numel())
-    _lib.check(_lib.load().smil_fit_epilogue(ctypes.byref(cfg), _ptr(pose), _ptr(trans), _ptr(betas), _ptr(mean_betas), _ptr(betas_prec),
-                                             _ptr(mask), _ptr(halo_prev), _ptr(halo_next), _ptr(objs), _ptr(d_pose), _ptr(d_trans),
-                                             _ptr(d_betas), int(accumulate), _ptr(loss_img), _ptr(pix_scale), n_img,
-                                             None if c is None else ctypes.byref(c), _ptr(d_fov_img), _ptr(d_fov), _stream()),
-               "smil_fit_epilogue")
+    _lib.checked().smil_fit_epilogue(ctypes.byref(cfg), _ptr(pose), _ptr(trans), _ptr(betas), _ptr(mean_betas), _ptr(betas_prec), _ptr(mask),
+                                     _ptr(halo_prev), _ptr(halo_next), _ptr(objs), _ptr(d_pose), _ptr(d_trans), _ptr(d_betas), int(accumulate),
+                                     _ptr(loss_img), _ptr(pix_scale), n_img, None if c is None else ctypes.byref(c), _ptr(d_fov_img), _ptr(d_fov),
+                                     _stream())
 
 
 def fov_reduce(cams: CameraSet, d_fov_img: torch.Tensor) -> torch.Tensor:
     N = d_fov_img.numel()
     d_fov = torch.empty(cams.fov.numel(), dtype=torch.float32, device=d_fov_img.device)
     c = cams.struct(N)
-    _lib.check(_lib.load().smil_fov_reduce(ctypes.byref(c), _ptr(d_fov_img), _ptr(d_fov), _stream()), "smil_fov_reduce")
+    _lib.checked().smil_fov_reduce(ctypes.byref(c), _ptr(d_fov_img), _ptr(d_fov), _stream())
     return d_fov
 
 
@@ -496,7 +495,7 @@ def raster_stats(model: DeviceModel, N: int) -> dict:
     if model._ws is None or user is None or user[0] is not model:
         return zero  # this model has not rasterised, or another model / topology has used the shared workspace since
     out = (ctypes.c_uint32 * 4)()
-    _lib.check(_lib.load().smil_raster_stats(model.handle, _ptr(model._ws), _stream(), out), "smil_raster_stats")
+    _lib.checked().smil_raster_stats(model.handle, _ptr(model._ws), _stream(), out)
     return {"straddling_faces": int(out[0]), "tiles": int(out[1]), "unclipped_faces": int(out[2]), "tie_pixels": int(out[3])}
 
 
@@ -508,8 +507,8 @@ def silhouette_forward(model: DeviceModel, verts_ndc: torch.Tensor, S: int, rs=N
     ws = model.workspace(step, S)
     model._claim_workspace()
     for n0, n1 in _slices(N, step):
-        _lib.check(_lib.load().smil_silhouette_forward(model.handle, _ptr(verts_ndc[n0:n1]), n1 - n0, S, ctypes.byref(rs),
-                                                       _ptr(sil[n0:n1]), _ptr(ws), _stream()), "smil_silhouette_forward")
+        _lib.checked().smil_silhouette_forward(model.handle, _ptr(verts_ndc[n0:n1]), n1 - n0, S, ctypes.byref(rs), _ptr(sil[n0:n1]), _ptr(ws),
+                                               _stream())
     return sil
 
 
@@ -523,9 +522,8 @@ def silhouette_backward(model: DeviceModel, verts_ndc: torch.Tensor, S: int, gra
     ws = model.workspace(step, S)
     model._claim_workspace()
     for n0, n1 in _slices(N, step):
-        _lib.check(_lib.load().smil_silhouette_backward(model.handle, _ptr(verts_ndc[n0:n1]), n1 - n0, S, ctypes.byref(_rs_for_slice(rs, clip_depth, n0)),
-                                                        _ptr(grad_sil[n0:n1]), _ptr(d_ndc[n0:n1]), _ptr(ws), _stream()),
-                   "smil_silhouette_backward")
+        _lib.checked().smil_silhouette_backward(model.handle, _ptr(verts_ndc[n0:n1]), n1 - n0, S, ctypes.byref(_rs_for_slice(rs, clip_depth, n0)),
+                                                _ptr(grad_sil[n0:n1]), _ptr(d_ndc[n0:n1]), _ptr(ws), _stream())
     return d_ndc
 
 
@@ -549,11 +547,11 @@ def silhouette_l1_fused(model: DeviceModel, verts_ndc, S, target, target_sum, pi
     if target.dtype not in (torch.float32, torch.uint8):
         raise _lib.SmilError(f"target silhouettes must be float32 or uint8, got {target.dtype}")
     for n0, n1 in _slices(N, step):
-        _lib.check(_lib.load().smil_silhouette_l1_fused(
-            model.handle, _ptr(verts_ndc[n0:n1]), n1 - n0, S, ctypes.byref(_rs_for_slice(rs, clip_depth, n0)), _ptr(target[n0:n1]), int(target.dtype == torch.uint8),
-            _ptr(target_sum[n0:n1]), _ptr(pix_scale[n0:n1]), _ptr(loss_img[n0:n1]), _ptr(d_ndc[n0:n1]),
-            _ptr(None if sil is None else sil[n0:n1]), _ptr(None if scale is None else scale[n0:n1]), _ptr(ws), _stream()),
-            "smil_silhouette_l1_fused")
+        _lib.checked().smil_silhouette_l1_fused(model.handle, _ptr(verts_ndc[n0:n1]), n1 - n0, S, ctypes.byref(_rs_for_slice(rs, clip_depth, n0)),
+                                                _ptr(target[n0:n1]), int(target.dtype == torch.uint8), _ptr(target_sum[n0:n1]),
+                                                _ptr(pix_scale[n0:n1]), _ptr(loss_img[n0:n1]), _ptr(d_ndc[n0:n1]),
+                                                _ptr(None if sil is None else sil[n0:n1]), _ptr(None if scale is None else scale[n0:n1]), _ptr(ws),
+                                                _stream())
     return (loss_img, d_ndc, sil, scale) if packed_out else (loss_img, d_ndc, sil)
 
 
@@ -569,7 +567,7 @@ def _colour_workspace(model: DeviceModel, N: int, S: int, size_of=None) -> torch
     key = model._ws_key()
     ws = _COLOUR_WS.get(key)
     if ws is None or ws.numel() < need:
-        ws = _COLOUR_WS[key] = torch.empty(need, dtype=torch.uint8, device=model.device)
+        ws = _COLOUR_WS[key] = _workspace(need, model.device)
     return ws
 
 
@@ -590,7 +588,7 @@ def render_colour(model: DeviceModel, cams: CameraSet, verts: torch.Tensor, mesh
     image = torch.empty(N, 3, S, S, dtype=torch.float32, device=dev)
     p2f = torch.empty(N, S, S, dtype=torch.int32, device=dev) if want_pix_to_face else None
     rgb = (ctypes.c_float * 3)(*[float(c) for c in mesh_color])
-    lib = _lib.load()
+    lib = _lib.checked()
     step = frames  # frames per launch
     while step > 1 and int(lib.smil_colour_workspace_bytes(model.handle, step * views, S)) > MAX_COLOUR_WORKSPACE_BYTES:
         step = (step + 1) // 2
@@ -604,9 +602,8 @@ def render_colour(model: DeviceModel, cams: CameraSet, verts: torch.Tensor, mesh
         part = CameraSet(rows(cams.R), rows(cams.T), rows(cams.fov.reshape(-1)), rows(None if cams.aspect is None else cams.aspect.reshape(-1)),
                          views, S, rows(cams.principal))
         c = part.struct(n1 - n0)
-        _lib.check(lib.smil_render_colour(model.handle, ctypes.byref(c), _ptr(verts[f0:f1]), _ptr(verts_ndc[n0:n1]), rgb,
-                                          _ptr(image[n0:n1]), _ptr(None if p2f is None else p2f[n0:n1]), _ptr(ws), _stream()),
-                   "smil_render_colour")
+        lib.smil_render_colour(model.handle, ctypes.byref(c), _ptr(verts[f0:f1]), _ptr(verts_ndc[n0:n1]), rgb, _ptr(image[n0:n1]),
+                               _ptr(None if p2f is None else p2f[n0:n1]), _ptr(ws), _stream())
     return (image, p2f) if want_pix_to_face else image
 
 
@@ -653,7 +650,7 @@ def render_fragments(model: DeviceModel, cams: CameraSet, verts: torch.Tensor, v
     shapes = dict(pix_to_face=((N, S, S), torch.int32), zbuf=((N, S, S), torch.float32), bary=((N, S, S, 3), torch.float32),
                   dist=((N, S, S), torch.float32))
     out = {k: (torch.empty(*shapes[k][0], dtype=shapes[k][1], device=dev) if k in want else None) for k in FRAGMENT_OUTPUTS}
-    lib = _lib.load()
+    lib = _lib.checked()
     step = max(1, min(frames, MAX_IMAGES_PER_LAUNCH // views))  # frames per launch
     while step > 1 and int(lib.smil_fragments_workspace_bytes(model.handle, step * views, S)) > MAX_COLOUR_WORKSPACE_BYTES:
         step = (step + 1) // 2
@@ -663,8 +660,7 @@ def render_fragments(model: DeviceModel, cams: CameraSet, verts: torch.Tensor, v
         n0, n1 = f0 * views, f1 * views
         c = _camera_rows(cams, N, n0, n1).struct(n1 - n0)
         part = [_ptr(None if out[k] is None else out[k][n0:n1]) for k in FRAGMENT_OUTPUTS]
-        _lib.check(lib.smil_render_fragments(model.handle, ctypes.byref(c), _ptr(verts[f0:f1]), _ptr(verts_ndc[n0:n1]), *part, _ptr(ws),
-                                             _stream()), "smil_render_fragments")
+        lib.smil_render_fragments(model.handle, ctypes.byref(c), _ptr(verts[f0:f1]), _ptr(verts_ndc[n0:n1]), *part, _ptr(ws), _stream())
     return Fragments(**out)
 
 
@@ -701,10 +697,9 @@ def depth_visibility(depth: torch.Tensor, kp_norm: torch.Tensor, kp_dist: torch.
     depth, kp_norm, kp_dist, visibility = depth.contiguous(), kp_norm.contiguous(), kp_dist.contiguous(), visibility.contiguous()
     out = torch.empty(B, P, dtype=torch.float32, device=dev)
     surface = torch.empty(B, P, dtype=torch.float64, device=dev) if want_surface else None
-    _lib.check(_lib.load().smil_depth_visibility(_ptr(depth), int(depth.dtype == torch.uint8), channels,
-                                                 float(0.0 if depth_max is None else depth_max), B, H, W, _ptr(kp_norm), _ptr(kp_dist), P,
-                                                 _ptr(visibility), float(tolerance), int(neighborhood), _ptr(out), _ptr(surface), _stream()),
-               "smil_depth_visibility")
+    _lib.checked().smil_depth_visibility(_ptr(depth), int(depth.dtype == torch.uint8), channels, float(0.0 if depth_max is None else depth_max), B, H,
+                                         W, _ptr(kp_norm), _ptr(kp_dist), P, _ptr(visibility), float(tolerance), int(neighborhood), _ptr(out),
+                                         _ptr(surface), _stream())
     return (out, surface) if want_surface else out
 
 
@@ -712,8 +707,7 @@ def image_abs_sum(images: torch.Tensor) -> torch.Tensor:
     N = images.shape[0]
     pixels = images[0].numel()
     out = torch.empty(N, dtype=torch.float32, device=images.device)
-    _lib.check(_lib.load().smil_image_abs_sum(_ptr(images), int(images.dtype == torch.uint8), N, pixels, _ptr(out), _stream()),
-               "smil_image_abs_sum")
+    _lib.checked().smil_image_abs_sum(_ptr(images), int(images.dtype == torch.uint8), N, pixels, _ptr(out), _stream())
     return out
 
 
@@ -734,34 +728,32 @@ def fit_config(N, J, nB, window, weights, w_temp=0.0, frame0=0, N_total=None, li
 
 def pix_scale(cfg: _lib.FitConfig, views: int, S: int, device) -> torch.Tensor:
     out = torch.empty(cfg.N * views, dtype=torch.float32, device=device)
-    _lib.check(_lib.load().smil_pix_scale(ctypes.byref(cfg), views, S, _ptr(out), _stream()), "smil_pix_scale")
+    _lib.checked().smil_pix_scale(ctypes.byref(cfg), views, S, _ptr(out), _stream())
     return out
 
 
 def prior_losses(cfg, pose, trans, betas, mean_betas, betas_prec, mask, objs, d_pose, d_trans, d_betas, halo_prev=None,
                  halo_next=None, accumulate=True):
     """pose (N,J,3) = [global_rotation ; joint_rotations], mask (J,3) = [global_mask ; rotation_mask]."""
-    _lib.check(_lib.load().smil_prior_losses(ctypes.byref(cfg), _ptr(pose), _ptr(trans), _ptr(betas), _ptr(mean_betas),
-                                             _ptr(betas_prec), _ptr(mask), _ptr(halo_prev), _ptr(halo_next), _ptr(objs),
-                                             _ptr(d_pose), _ptr(d_trans), _ptr(d_betas), int(accumulate), _stream()),
-               "smil_prior_losses")
+    _lib.checked().smil_prior_losses(ctypes.byref(cfg), _ptr(pose), _ptr(trans), _ptr(betas), _ptr(mean_betas), _ptr(betas_prec), _ptr(mask),
+                                     _ptr(halo_prev), _ptr(halo_next), _ptr(objs), _ptr(d_pose), _ptr(d_trans), _ptr(d_betas), int(accumulate),
+                                     _stream())
 
 
 def mask_rows(x: torch.Tensor, mask: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     cols = mask.numel()
     out = torch.empty_like(x) if out is None else out
-    _lib.check(_lib.load().smil_mask_rows(_ptr(x), _ptr(mask), x.numel() // cols, cols, _ptr(out), _stream()), "smil_mask_rows")
+    _lib.checked().smil_mask_rows(_ptr(x), _ptr(mask), x.numel() // cols, cols, _ptr(out), _stream())
     return out
 
 
 def joint_loss(cfg, views, Jc, canon, proj, target, visibility, objs, d_proj):
-    _lib.check(_lib.load().smil_joint_loss(ctypes.byref(cfg), views, Jc, _ptr(canon), _ptr(proj), _ptr(target),
-                                           _ptr(visibility), _ptr(objs), _ptr(d_proj), _stream()), "smil_joint_loss")
+    _lib.checked().smil_joint_loss(ctypes.byref(cfg), views, Jc, _ptr(canon), _ptr(proj), _ptr(target), _ptr(visibility), _ptr(objs), _ptr(d_proj),
+                                   _stream())
 
 
 def sil_objective(loss_img, pscale, objs):
-    _lib.check(_lib.load().smil_sil_objective(_ptr(loss_img), _ptr(pscale), loss_img.numel(), _ptr(objs), _stream()),
-               "smil_sil_objective")
+    _lib.checked().smil_sil_objective(_ptr(loss_img), _ptr(pscale), loss_img.numel(), _ptr(objs), _stream())
 
 
 def window_terms(cfg, views, Jc, canon, proj, target, visibility, pose, mask, objs_total, loss_img, pscale) -> torch.Tensor:
@@ -770,15 +762,13 @@ def window_terms(cfg, views, Jc, canon, proj, target, visibility, pose, mask, ob
     w = cfg.window if cfg.window > 0 else cfg.N_total
     n_win = (cfg.N + w - 1) // w
     out = torch.empty(n_win, 6, dtype=torch.float32, device=pose.device)
-    _lib.check(_lib.load().smil_window_terms(ctypes.byref(cfg), views, Jc, _ptr(canon), _ptr(proj), _ptr(target), _ptr(visibility), _ptr(pose),
-                                             _ptr(mask), _ptr(objs_total), _ptr(loss_img), _ptr(pscale), _ptr(out), n_win, _stream()),
-               "smil_window_terms")
+    _lib.checked().smil_window_terms(ctypes.byref(cfg), views, Jc, _ptr(canon), _ptr(proj), _ptr(target), _ptr(visibility), _ptr(pose), _ptr(mask),
+                                     _ptr(objs_total), _ptr(loss_img), _ptr(pscale), _ptr(out), n_win, _stream())
     return out
 
 
 def adam_step(param, grad, exp_avg, exp_avg_sq, lr, step, beta1=0.5, beta2=0.999, eps=1e-8):
-    _lib.check(_lib.load().smil_adam_step(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), lr, beta1,
-                                          beta2, eps, step, _stream()), "smil_adam_step")
+    _lib.checked().smil_adam_step(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), lr, beta1, beta2, eps, step, _stream())
 
 
 def _adam_multi(entry, items, beta1, beta2, eps):
@@ -789,7 +779,7 @@ def _adam_multi(entry, items, beta1, beta2, eps):
         for a, (p, g, m, v, lr, step) in zip(arr, chunk):
             a.param, a.grad, a.exp_avg, a.exp_avg_sq = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
             a.n, a.lr, a.step = p.numel(), float(lr), int(step)
-        _lib.check(getattr(_lib.load(), entry)(arr, len(chunk), beta1, beta2, eps, _stream()), entry)
+        getattr(_lib.checked(), entry)(arr, len(chunk), beta1, beta2, eps, _stream())
 
 
 def adam_step_multi(items, beta1=0.5, beta2=0.999, eps=1e-8):
@@ -799,18 +789,18 @@ def adam_step_multi(items, beta1=0.5, beta2=0.999, eps=1e-8):
 
 def adam_step_dev(param, grad, exp_avg, exp_avg_sq, lr, step_dev, step_offset=0, beta1=0.5, beta2=0.999, eps=1e-8):
     """Adam update whose step count is ``step_dev[0] - step_offset`` (int32 device tensor): capturable in a hipGraph."""
-    _lib.check(_lib.load().smil_adam_step_dev(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), lr, beta1,
-                                              beta2, eps, _ptr(step_dev), int(step_offset), _stream()), "smil_adam_step_dev")
+    _lib.checked().smil_adam_step_dev(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), lr, beta1, beta2, eps, _ptr(step_dev),
+                                      int(step_offset), _stream())
 
 
 def profile_enable(on: bool) -> None:
-    _lib.check(_lib.load().smil_profile_enable(int(on)), "smil_profile_enable")
+    _lib.checked().smil_profile_enable(int(on))
 
 
 def profile_read():
     """(summed tile-kernel milliseconds, launches) since the last enable/read."""
     ms, n = ctypes.c_float(), ctypes.c_int32()
-    _lib.check(_lib.load().smil_profile_read(ctypes.byref(ms), ctypes.byref(n)), "smil_profile_read")
+    _lib.checked().smil_profile_read(ctypes.byref(ms), ctypes.byref(n))
     return float(ms.value), int(n.value)
 
 
@@ -822,9 +812,8 @@ def sample_points(verts_packed: torch.Tensor, faces_packed: torch.Tensor, face_o
     dev = verts_packed.device
     out = torch.empty(n_meshes, num_samples, 3, device=dev, dtype=torch.float32)
     fidx = torch.empty(n_meshes, num_samples, device=dev, dtype=torch.int32) if want_faces else None
-    _lib.check(_lib.load().smil_sample_points(_ptr(verts_packed), int(verts_packed.shape[0]), _ptr(faces_packed), _ptr(face_off),
-                                              _ptr(cum_area), int(n_meshes), int(num_samples), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out),
-                                              _ptr(fidx), _stream()), "smil_sample_points")
+    _lib.checked().smil_sample_points(_ptr(verts_packed), int(verts_packed.shape[0]), _ptr(faces_packed), _ptr(face_off), _ptr(cum_area),
+                                      int(n_meshes), int(num_samples), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out), _ptr(fidx), _stream())
     return out, fidx
 
 
@@ -832,15 +821,15 @@ def chamfer(x: torch.Tensor, y: torch.Tensor, single_directional=False, point_su
     """Chamfer loss of x (N,P1,3) and y (N,P2,3): (loss (1,), idx_x (N,P1), idx_y (N,P2) or None, d_x, d_y or None)."""
     N, P1, P2 = int(x.shape[0]), int(x.shape[1]), int(y.shape[1])
     dev = x.device
-    lib = _lib.load()
-    ws = torch.empty(int(lib.smil_chamfer_workspace_bytes(N, P1, P2)), dtype=torch.uint8, device=dev)
+    lib = _lib.checked()
+    ws = _workspace(lib.smil_chamfer_workspace_bytes(N, P1, P2), dev)
     loss = torch.empty(1, device=dev, dtype=torch.float32)
     idx_x = torch.empty(N, P1, device=dev, dtype=torch.int32)
     idx_y = None if single_directional else torch.empty(N, P2, device=dev, dtype=torch.int32)
     d_x = torch.empty_like(x) if want_grad else None
     d_y = torch.empty_like(y) if want_grad else None
-    _lib.check(lib.smil_chamfer(_ptr(x), _ptr(y), N, P1, P2, int(bool(single_directional)), int(bool(point_sum)), int(bool(batch_sum)),
-                                _ptr(loss), _ptr(idx_x), _ptr(idx_y), _ptr(d_x), _ptr(d_y), _ptr(ws), _stream()), "smil_chamfer")
+    lib.smil_chamfer(_ptr(x), _ptr(y), N, P1, P2, int(bool(single_directional)), int(bool(point_sum)), int(bool(batch_sum)), _ptr(loss), _ptr(idx_x),
+                     _ptr(idx_y), _ptr(d_x), _ptr(d_y), _ptr(ws), _stream())
     return loss, idx_x, idx_y, d_x, d_y
 
 
@@ -863,13 +852,13 @@ def knn(x: torch.Tensor, y: torch.Tensor, K: int, both: bool = False):
     N, P1, P2, K = int(x.shape[0]), int(x.shape[1]), int(y.shape[1]), int(K)
     _check_knn_sizes("knn", P1, P2, K, both)
     dev = x.device
-    lib = _lib.load()
-    ws = torch.empty(int(lib.smil_knn_workspace_bytes(N, P1, P2, K)), dtype=torch.uint8, device=dev)
+    lib = _lib.checked()
+    ws = _workspace(lib.smil_knn_workspace_bytes(N, P1, P2, K), dev)
     dx = torch.empty(N, P1, K, device=dev, dtype=torch.float32)
     ix = torch.empty(N, P1, K, device=dev, dtype=torch.int32)
     dy = torch.empty(N, P2, K, device=dev, dtype=torch.float32) if both else None
     iy = torch.empty(N, P2, K, device=dev, dtype=torch.int32) if both else None
-    _lib.check(lib.smil_knn(_ptr(x), _ptr(y), N, P1, P2, K, _ptr(dx), _ptr(ix), _ptr(dy), _ptr(iy), _ptr(ws), _stream()), "smil_knn")
+    lib.smil_knn(_ptr(x), _ptr(y), N, P1, P2, K, _ptr(dx), _ptr(ix), _ptr(dy), _ptr(iy), _ptr(ws), _stream())
     return dx, ix, dy, iy, _insertions(ws)
 
 
@@ -880,8 +869,8 @@ def sdf_distance(x: torch.Tensor, y: torch.Tensor, x_sdf: torch.Tensor, y_sdf: t
     N, P1, P2, K = int(x.shape[0]), int(x.shape[1]), int(y.shape[1]), int(K)
     _check_knn_sizes("sdf_distance", P1, P2, K, not single_directional, min_points=2)
     dev = x.device
-    lib = _lib.load()
-    ws = torch.empty(int(lib.smil_sdf_distance_workspace_bytes(N, P1, P2, K)), dtype=torch.uint8, device=dev)
+    lib = _lib.checked()
+    ws = _workspace(lib.smil_sdf_distance_workspace_bytes(N, P1, P2, K), dev)
     loss = torch.empty(1, device=dev, dtype=torch.float32)
     d_x = torch.empty_like(x) if want_grad else None
     d_y = torch.empty_like(y) if want_grad else None
@@ -891,9 +880,8 @@ def sdf_distance(x: torch.Tensor, y: torch.Tensor, x_sdf: torch.Tensor, y_sdf: t
                   None if single_directional else torch.empty(N, P2, K, device=dev, dtype=torch.float32),
                   None if single_directional else torch.empty(N, P2, K, device=dev, dtype=torch.int32))
     t = tables or (None,) * 4
-    _lib.check(lib.smil_sdf_distance(_ptr(x), _ptr(y), _ptr(x_sdf), _ptr(y_sdf), N, P1, P2, K, int(bool(single_directional)),
-                                     int(bool(point_sum)), int(bool(batch_sum)), _ptr(loss), _ptr(d_x), _ptr(d_y), _ptr(t[0]), _ptr(t[1]),
-                                     _ptr(t[2]), _ptr(t[3]), _ptr(ws), _stream()), "smil_sdf_distance")
+    lib.smil_sdf_distance(_ptr(x), _ptr(y), _ptr(x_sdf), _ptr(y_sdf), N, P1, P2, K, int(bool(single_directional)), int(bool(point_sum)),
+                          int(bool(batch_sum)), _ptr(loss), _ptr(d_x), _ptr(d_y), _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), _ptr(t[3]), _ptr(ws), _stream())
     return loss, d_x, d_y, tables, _insertions(ws)
 
 
@@ -905,20 +893,18 @@ def sample_vertices(verts_packed: torch.Tensor, values_packed: torch.Tensor, ver
     out = torch.empty(n_meshes, num_samples, 3, device=dev, dtype=torch.float32)
     val = torch.empty(n_meshes, num_samples, device=dev, dtype=torch.float32)
     idx = torch.empty(n_meshes, num_samples, device=dev, dtype=torch.int32)
-    _lib.check(_lib.load().smil_sample_vertices(_ptr(verts_packed), _ptr(values_packed), _ptr(vert_off), int(n_meshes), int(num_samples),
-                                                int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out), _ptr(val), _ptr(idx), _stream()),
-               "smil_sample_vertices")
+    _lib.checked().smil_sample_vertices(_ptr(verts_packed), _ptr(values_packed), _ptr(vert_off), int(n_meshes), int(num_samples),
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out), _ptr(val), _ptr(idx), _stream())
     return out, val, idx
 
 
 def sample_vertices_backward(d_pts: torch.Tensor, idx: torch.Tensor, vert_off: torch.Tensor, n_verts: int, max_verts: int):
     """d_verts (n_verts,3): d_pts (N,S,3) summed over the samples that drew each vertex (order-independent)."""
     N, S = int(idx.shape[0]), int(idx.shape[1])
-    lib = _lib.load()
-    ws = torch.empty(int(lib.smil_sample_vertices_backward_workspace_bytes(int(n_verts), N)), dtype=torch.uint8, device=d_pts.device)
+    lib = _lib.checked()
+    ws = _workspace(lib.smil_sample_vertices_backward_workspace_bytes(int(n_verts), N), d_pts.device)
     d_verts = torch.empty(int(n_verts), 3, device=d_pts.device, dtype=torch.float32)
-    _lib.check(lib.smil_sample_vertices_backward(_ptr(d_pts), _ptr(idx), _ptr(vert_off), int(n_verts), int(max_verts), N, S, _ptr(d_verts),
-                                                 _ptr(ws), _stream()), "smil_sample_vertices_backward")
+    lib.smil_sample_vertices_backward(_ptr(d_pts), _ptr(idx), _ptr(vert_off), int(n_verts), int(max_verts), N, S, _ptr(d_verts), _ptr(ws), _stream())
     return d_verts
 
 
@@ -942,12 +928,12 @@ class DeviceTopology:
 def mesh_regularisers(topo: DeviceTopology, verts: torch.Tensor, terms: int, want_grad=True):
     """verts (B,V,3) on ``topo`` -> (out3 (3,) = edge, normal, laplacian losses, d_edge, d_normal, d_lap (B,V,3) or None)."""
     B = int(verts.shape[0])
-    lib = _lib.load()
-    ws = torch.empty(int(lib.smil_mesh_reg_workspace_bytes(ctypes.byref(topo.struct), B)), dtype=torch.uint8, device=verts.device)
+    lib = _lib.checked()
+    ws = _workspace(lib.smil_mesh_reg_workspace_bytes(ctypes.byref(topo.struct), B), verts.device)
     out = torch.empty(3, device=verts.device, dtype=torch.float32)
     g = [torch.empty_like(verts) if (want_grad and terms & bit) else None for bit in (_lib.REG_EDGE, _lib.REG_NORMAL, _lib.REG_LAPLACIAN)]
-    _lib.check(lib.smil_mesh_regularisers(ctypes.byref(topo.struct), _ptr(verts), B, int(terms), _ptr(out), _ptr(g[0]), _ptr(g[1]),
-                                          _ptr(g[2]), _ptr(ws), _stream()), "smil_mesh_regularisers")
+    lib.smil_mesh_regularisers(ctypes.byref(topo.struct), _ptr(verts), B, int(terms), _ptr(out), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(ws),
+                               _stream())
     return out, g[0], g[1], g[2]
 
 
@@ -967,12 +953,12 @@ def ray_diameters(verts: torch.Tensor, faces: torch.Tensor, origins: torch.Tenso
         raise ValueError("ray_diameters: verts (V,3), faces (F,3), origins (S,3), own_face (S), dirs (S,R,3)")
     dev = verts.device
     verts, faces, origins, own_face, dirs = (t.contiguous() for t in (verts, faces, origins, own_face, dirs))
-    lib = _lib.load()
-    ws = torch.empty(int(lib.smil_ray_diameters_workspace_bytes(F, S, R)), dtype=torch.uint8, device=dev)
+    lib = _lib.checked()
+    ws = _workspace(lib.smil_ray_diameters_workspace_bytes(F, S, R), dev)
     diam = torch.empty(S, device=dev, dtype=torch.float32)
     ray_t = torch.empty(S, R, device=dev, dtype=torch.float32) if want_ray_t else None
-    _lib.check(lib.smil_ray_diameters(_ptr(verts), V, _ptr(faces), F, _ptr(origins), _ptr(own_face), _ptr(dirs), S, R, float(t_min), float(d_lo),
-                                      float(d_hi), int(cap), _ptr(ray_t), _ptr(diam), _ptr(ws), _stream()), "smil_ray_diameters")
+    lib.smil_ray_diameters(_ptr(verts), V, _ptr(faces), F, _ptr(origins), _ptr(own_face), _ptr(dirs), S, R, float(t_min), float(d_lo), float(d_hi),
+                           int(cap), _ptr(ray_t), _ptr(diam), _ptr(ws), _stream())
     return diam, ray_t
 
 
@@ -1002,11 +988,11 @@ def _point_mesh_inputs(who: str, verts: torch.Tensor, mt: MeshTables, points: to
         if tuple(lengths.shape) != (mt.n_meshes,):
             raise ValueError(f"{who}: lengths ({mt.n_meshes},), got {tuple(lengths.shape)}")
         lengths = lengths.to(device=verts.device, dtype=torch.int32).contiguous()
-    lib = _lib.load()
+    lib = _lib.checked()
     nbytes = int(lib.smil_point_mesh_workspace_bytes(mt.n_meshes, mt.n_faces, int(points.shape[1]), mt.n_verts))
     if nbytes == 0:
         raise _lib.SmilError(f"{who}: sizes N={mt.n_meshes} F={mt.n_faces} P={int(points.shape[1])} V={mt.n_verts} are not supported")
-    return lib, verts.contiguous(), points.contiguous(), lengths, torch.empty(nbytes, dtype=torch.uint8, device=verts.device)
+    return lib, verts.contiguous(), points.contiguous(), lengths, _workspace(nbytes, verts.device)
 
 
 def point_mesh_distance(verts: torch.Tensor, mt: MeshTables, points: torch.Tensor, lengths: Optional[torch.Tensor] = None,
@@ -1021,8 +1007,8 @@ def point_mesh_distance(verts: torch.Tensor, mt: MeshTables, points: torch.Tenso
     idx = torch.empty(rows, device=verts.device, dtype=torch.int32)
     bary = torch.empty(rows + (3,), device=verts.device, dtype=torch.float32)
     fn = lib.smil_face_point_distance if by_face else lib.smil_point_face_distance
-    _lib.check(fn(_ptr(verts), mt.n_verts, _ptr(mt.faces), _ptr(mt.face_off), mt.n_meshes, mt.n_faces, mt.max_faces, _ptr(points),
-                  int(points.shape[1]), _ptr(lengths), int(splits), _ptr(dist2), _ptr(idx), _ptr(bary), _ptr(ws), _stream()), f"smil_{who}")
+    fn(_ptr(verts), mt.n_verts, _ptr(mt.faces), _ptr(mt.face_off), mt.n_meshes, mt.n_faces, mt.max_faces, _ptr(points), int(points.shape[1]),
+       _ptr(lengths), int(splits), _ptr(dist2), _ptr(idx), _ptr(bary), _ptr(ws), _stream())
     return dist2, idx, bary
 
 
@@ -1035,10 +1021,9 @@ def point_mesh_backward(verts: torch.Tensor, mt: MeshTables, points: torch.Tenso
         raise ValueError(f"point_mesh_backward: idx int32 and g float32 of shape {rows}")
     d_points = torch.empty_like(points)
     d_verts = torch.empty_like(verts)
-    _lib.check(lib.smil_point_mesh_backward(_ptr(verts), mt.n_verts, _ptr(mt.faces), _ptr(mt.face_off), _ptr(mt.vert_off), mt.n_meshes,
-                                            mt.n_faces, mt.max_faces, mt.max_verts, _ptr(points), int(points.shape[1]), _ptr(lengths),
-                                            int(bool(by_face)), _ptr(idx.contiguous()), _ptr(g.contiguous()), _ptr(d_points), _ptr(d_verts),
-                                            _ptr(ws), _stream()), "smil_point_mesh_backward")
+    lib.smil_point_mesh_backward(_ptr(verts), mt.n_verts, _ptr(mt.faces), _ptr(mt.face_off), _ptr(mt.vert_off), mt.n_meshes, mt.n_faces, mt.max_faces,
+                                 mt.max_verts, _ptr(points), int(points.shape[1]), _ptr(lengths), int(bool(by_face)), _ptr(idx.contiguous()),
+                                 _ptr(g.contiguous()), _ptr(d_points), _ptr(d_verts), _ptr(ws), _stream())
     return d_points, d_verts
 
 
@@ -1062,7 +1047,7 @@ def fps(xyz: torch.Tensor, npoint: int, start: torch.Tensor) -> torch.Tensor:
         raise ValueError(f"fps: bad sizes B={B} N={N} npoint={npoint}")
     xyz, start = xyz.contiguous(), start.contiguous()
     out = torch.empty(B, npoint, device=xyz.device, dtype=torch.int32)
-    _lib.check(_lib.load().smil_fps(_ptr(xyz), _ptr(start), B, N, npoint, _ptr(out), _stream()), "smil_fps")
+    _lib.checked().smil_fps(_ptr(xyz), _ptr(start), B, N, npoint, _ptr(out), _stream())
     return out
 
 
@@ -1082,8 +1067,8 @@ def ball_query(xyz: torch.Tensor, new_xyz: torch.Tensor, radii, nsamples):
         raise ValueError(f"ball_query: bad sizes B={B} N={N} S={S}")
     xyz, new_xyz = xyz.contiguous(), new_xyz.contiguous()
     outs = [torch.empty(B, S, min(k, N), device=xyz.device, dtype=torch.int32) for k in nsamples]
-    _lib.check(_lib.load().smil_ball_query(_ptr(xyz), _ptr(new_xyz), B, N, S, n, (ctypes.c_double * n)(*radii), (ctypes.c_int32 * n)(*nsamples),
-                                           (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), _stream()), "smil_ball_query")
+    _lib.checked().smil_ball_query(_ptr(xyz), _ptr(new_xyz), B, N, S, n, (ctypes.c_double * n)(*radii), (ctypes.c_int32 * n)(*nsamples),
+                                   (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), _stream())
     return outs
 
 
@@ -1114,8 +1099,8 @@ def group_points(xyz: Optional[torch.Tensor], centres: Optional[torch.Tensor], f
         raise ValueError(f"group_points: bad sizes B={B} N={N} S={S} K={K} D={D}")
     xyz, centres, features, idx = (None if t is None else t.contiguous() for t in (xyz, centres, features, idx))
     out = torch.empty(B, (0 if xyz is None else 3) + D, K, S, device=idx.device, dtype=torch.float32)
-    _lib.check(_lib.load().smil_group_points(_ptr(xyz), _ptr(centres), _ptr(features if D else None), _ptr(idx), B, N, S, K, D,
-                                             int(bool(xyz_last)), _ptr(out), _stream()), "smil_group_points")
+    _lib.checked().smil_group_points(_ptr(xyz), _ptr(centres), _ptr(features if D else None), _ptr(idx), B, N, S, K, D, int(bool(xyz_last)),
+                                     _ptr(out), _stream())
     return out
 
 
@@ -1126,11 +1111,10 @@ def group_points_backward(d_out: torch.Tensor, idx: torch.Tensor, N: int, D: int
     if idx.dtype != torch.int32 or d_out.dtype != torch.float32 or tuple(d_out.shape) != (B, (3 if has_xyz else 0) + D, K, S) or D < 1:
         raise ValueError("group_points_backward: d_out (B, C, K, S) float32 and idx (B, S, K) int32 with C = 3 + D or D >= 1")
     d_out, idx = d_out.contiguous(), idx.contiguous()
-    lib = _lib.load()
-    ws = torch.empty(int(lib.smil_group_points_backward_workspace_bytes(B, N, D)), dtype=torch.uint8, device=d_out.device)
+    lib = _lib.checked()
+    ws = _workspace(lib.smil_group_points_backward_workspace_bytes(B, N, D), d_out.device)
     d_feat = torch.empty(B, N, D, device=d_out.device, dtype=torch.float32)
-    _lib.check(lib.smil_group_points_backward(_ptr(d_out), _ptr(idx), B, N, S, K, D, int(bool(has_xyz)), int(bool(xyz_last)), _ptr(d_feat),
-                                              _ptr(ws), _stream()), "smil_group_points_backward")
+    lib.smil_group_points_backward(_ptr(d_out), _ptr(idx), B, N, S, K, D, int(bool(has_xyz)), int(bool(xyz_last)), _ptr(d_feat), _ptr(ws), _stream())
     return d_feat
 
 
@@ -1182,10 +1166,9 @@ def triangulate(P: torch.Tensor, obs: torch.Tensor, scores: Optional[torch.Tenso
     view_err = torch.empty(N, Kp, C, device=dev, dtype=torch.float64) if want_view_err else None
     mask = torch.empty(N, Kp, device=dev, dtype=torch.int32) if want_inlier_mask else None
     undist = torch.full((N, Kp, C, 2), float("nan"), device=dev, dtype=torch.float64) if want_undistorted else None
-    _lib.check(_lib.load().smil_triangulate(_ptr(P), _ptr(K), _ptr(dist), _ptr(obs), _ptr(scores), _ptr(pairs), N, Kp, C,
-                                            float(confidence_threshold), int(min_views), float(reproj_threshold), int(mode), _ptr(xyz),
-                                            _ptr(status), _ptr(used), _ptr(mean_err), _ptr(view_err), _ptr(mask), _ptr(undist), _stream()),
-               "smil_triangulate")
+    _lib.checked().smil_triangulate(_ptr(P), _ptr(K), _ptr(dist), _ptr(obs), _ptr(scores), _ptr(pairs), N, Kp, C, float(confidence_threshold),
+                                    int(min_views), float(reproj_threshold), int(mode), _ptr(xyz), _ptr(status), _ptr(used), _ptr(mean_err),
+                                    _ptr(view_err), _ptr(mask), _ptr(undist), _stream())
     return xyz, status, used, mean_err, view_err, mask, undist
 
 
@@ -1201,8 +1184,8 @@ def _refine_inputs(who, pts_3d, pts_2d, offsets, params, n_params, f_scale):
                               (("pts_3d", pts_3d, (total, 3)), ("pts_2d", pts_2d, (total, 2)), ("params", params, (C, 10))))
     if int(n_params) not in (6, 10) or not float(f_scale) > 0.0:
         raise ValueError(f"{who}: n_params={n_params} must be 6 or 10 and f_scale={f_scale} positive")
-    lib = _lib.load()
-    ws = torch.empty(int(lib.smil_refine_workspace_bytes(C, int(np.diff(offsets).max()))), dtype=torch.uint8, device=params.device)
+    lib = _lib.checked()
+    ws = _workspace(lib.smil_refine_workspace_bytes(C, int(np.diff(offsets).max())), params.device)
     return pts_3d, pts_2d, params, offsets, torch.from_numpy(offsets).to(params.device), C, ws
 
 
@@ -1215,8 +1198,8 @@ def refine_evaluate(pts_3d: torch.Tensor, pts_2d: torch.Tensor, offsets, params:
     cost = torch.empty(C, device=dev, dtype=torch.float64)
     g = torch.empty(C, 10, device=dev, dtype=torch.float64)
     H = torch.empty(C, 10, 10, device=dev, dtype=torch.float64)
-    _lib.check(_lib.load().smil_refine_evaluate(_ptr(pts_3d), _ptr(pts_2d), offsets.ctypes.data, _ptr(off_dev), C, _ptr(params), int(n_params),
-                                                float(f_scale), _ptr(cost), _ptr(g), _ptr(H), _ptr(ws), _stream()), "smil_refine_evaluate")
+    _lib.checked().smil_refine_evaluate(_ptr(pts_3d), _ptr(pts_2d), offsets.ctypes.data, _ptr(off_dev), C, _ptr(params), int(n_params),
+                                        float(f_scale), _ptr(cost), _ptr(g), _ptr(H), _ptr(ws), _stream())
     return cost, g, H
 
 
@@ -1232,9 +1215,9 @@ def refine_cameras(pts_3d: torch.Tensor, pts_2d: torch.Tensor, offsets, params0:
     status, n_acc, n_trial = (torch.empty(C, device=dev, dtype=torch.int32) for _ in range(3))
     cost0, cost = (torch.empty(C, device=dev, dtype=torch.float64) for _ in range(2))
     g = torch.empty(C, 10, device=dev, dtype=torch.float64)
-    _lib.check(_lib.load().smil_refine_cameras(_ptr(pts_3d), _ptr(pts_2d), offsets.ctypes.data, _ptr(off_dev), C, _ptr(params0), int(n_params),
-                                               float(f_scale), int(max_steps), _ptr(params), _ptr(status), _ptr(n_acc), _ptr(n_trial),
-                                               _ptr(cost0), _ptr(cost), _ptr(g), _ptr(ws), _stream()), "smil_refine_cameras")
+    _lib.checked().smil_refine_cameras(_ptr(pts_3d), _ptr(pts_2d), offsets.ctypes.data, _ptr(off_dev), C, _ptr(params0), int(n_params),
+                                       float(f_scale), int(max_steps), _ptr(params), _ptr(status), _ptr(n_acc), _ptr(n_trial), _ptr(cost0),
+                                       _ptr(cost), _ptr(g), _ptr(ws), _stream())
     return params, status, n_acc, n_trial, cost0, cost, g
 
 
@@ -1262,8 +1245,8 @@ def refine_points_evaluate(P: torch.Tensor, obs: torch.Tensor, view_mask: torch.
     cost = torch.empty(N, Kp, device=dev, dtype=torch.float64)
     g = torch.empty(N, Kp, 3, device=dev, dtype=torch.float64)
     H = torch.empty(N, Kp, 3, 3, device=dev, dtype=torch.float64)
-    _lib.check(_lib.load().smil_refine_points_evaluate(_ptr(P), _ptr(obs), _ptr(view_mask), _ptr(xyz), N, Kp, C, float(f_scale), _ptr(cost),
-                                                       _ptr(g), _ptr(H), _stream()), "smil_refine_points_evaluate")
+    _lib.checked().smil_refine_points_evaluate(_ptr(P), _ptr(obs), _ptr(view_mask), _ptr(xyz), N, Kp, C, float(f_scale), _ptr(cost), _ptr(g), _ptr(H),
+                                               _stream())
     return cost, g, H
 
 
@@ -1279,9 +1262,8 @@ def refine_points(P: torch.Tensor, obs: torch.Tensor, view_mask: torch.Tensor, x
     status, n_acc, n_trial = (torch.empty(N, Kp, device=dev, dtype=torch.int32) for _ in range(3))
     cost0, cost = (torch.empty(N, Kp, device=dev, dtype=torch.float64) for _ in range(2))
     view_err = torch.empty(N, Kp, C, device=dev, dtype=torch.float64) if want_view_err else None
-    _lib.check(_lib.load().smil_refine_points(_ptr(P), _ptr(obs), _ptr(view_mask), _ptr(xyz0), N, Kp, C, float(f_scale), int(max_steps),
-                                              _ptr(xyz), _ptr(status), _ptr(n_acc), _ptr(n_trial), _ptr(cost0), _ptr(cost), _ptr(view_err),
-                                              _stream()), "smil_refine_points")
+    _lib.checked().smil_refine_points(_ptr(P), _ptr(obs), _ptr(view_mask), _ptr(xyz0), N, Kp, C, float(f_scale), int(max_steps), _ptr(xyz),
+                                      _ptr(status), _ptr(n_acc), _ptr(n_trial), _ptr(cost0), _ptr(cost), _ptr(view_err), _stream())
     return xyz, status, n_acc, n_trial, cost0, cost, view_err
 
 
@@ -1301,7 +1283,7 @@ def image_bounds(sil: torch.Tensor) -> torch.Tensor:
     dev = require_gpu(sil.device)
     sil = sil.contiguous()
     bounds = torch.empty(N, 5, dtype=torch.int32, device=dev)
-    _lib.check(_lib.load().smil_image_bounds(_ptr(sil), int(sil.dtype == torch.uint8), N, H, W, _ptr(bounds), _stream()), "smil_image_bounds")
+    _lib.checked().smil_image_bounds(_ptr(sil), int(sil.dtype == torch.uint8), N, H, W, _ptr(bounds), _stream())
     return bounds
 
 
@@ -1390,7 +1372,7 @@ def warp_images(src: torch.Tensor, size, affine: torch.Tensor, *, coord_mode: st
     if clamp is not None:
         w.clamp, w.n_clamp = clamp.data_ptr(), int(clamp.shape[0])
     w.border, w.n_border, w.scale = border.data_ptr(), int(border.shape[0]), float(scale)
-    _lib.check(_lib.load().smil_warp_images(ctypes.byref(w), _stream()), "smil_warp_images")
+    _lib.checked().smil_warp_images(ctypes.byref(w), _stream())
     return out
 
 
@@ -1400,7 +1382,7 @@ ROT_DTYPES = {torch.float32: _lib.ROT_F32, torch.float64: _lib.ROT_F64}
 
 def rot_call(name: str, n: int, dtype: torch.dtype, *tensors: Optional[torch.Tensor]) -> None:
     """One ``smil_*`` rotation entry point over ``n`` rotations: the tensors in the order of its pointer arguments (None: NULL)."""
-    _lib.check(getattr(_lib.load(), name)(*(_ptr(t) for t in tensors), int(n), ROT_DTYPES[dtype], _stream()), name)
+    getattr(_lib.checked(), name)(*(_ptr(t) for t in tensors), int(n), ROT_DTYPES[dtype], _stream())
 
 
 def rot_forward(name: str, x: torch.Tensor, width: int) -> torch.Tensor:
@@ -1450,9 +1432,8 @@ def kp_se_forward(pred: torch.Tensor, target: torch.Tensor, vis, mask, weights, 
     N, J, D = pred.shape
     loss = torch.empty((), dtype=pred.dtype, device=pred.device)
     factor = _kp_f64(N, device=pred.device)
-    _lib.check(_lib.load().smil_kp_se_forward(_ptr(pred), _ptr(target), _ptr(vis), _ptr(mask), _ptr(weights), N, J, D, flags, rule,
-                                              ROT_DTYPES[pred.dtype], _ptr(_kp_f64(N, 4, device=pred.device)), _ptr(factor), _ptr(loss),
-                                              _stream()), "smil_kp_se_forward")
+    _lib.checked().smil_kp_se_forward(_ptr(pred), _ptr(target), _ptr(vis), _ptr(mask), _ptr(weights), N, J, D, flags, rule, ROT_DTYPES[pred.dtype],
+                                      _ptr(_kp_f64(N, 4, device=pred.device)), _ptr(factor), _ptr(loss), _stream())
     return loss, factor
 
 
@@ -1460,8 +1441,8 @@ def kp_se_backward(pred, target, vis, mask, weights, factor, upstream: torch.Ten
     """The gradient on ``pred`` from the 0-dim device tensor ``upstream``."""
     N, J, D = pred.shape
     dpred = torch.empty_like(pred)
-    _lib.check(_lib.load().smil_kp_se_backward(_ptr(pred), _ptr(target), _ptr(vis), _ptr(mask), _ptr(weights), _ptr(factor), _ptr(upstream),
-                                               _ptr(dpred), N, J, D, flags, ROT_DTYPES[pred.dtype], _stream()), "smil_kp_se_backward")
+    _lib.checked().smil_kp_se_backward(_ptr(pred), _ptr(target), _ptr(vis), _ptr(mask), _ptr(weights), _ptr(factor), _ptr(upstream), _ptr(dpred), N,
+                                       J, D, flags, ROT_DTYPES[pred.dtype], _stream())
     return dpred
 
 
@@ -1473,8 +1454,8 @@ def kp_project(joints, R, T, fov, aspect, S: float) -> torch.Tensor:
     """joints (B,J,3), R (B,V,3,3), T (B,V,3), fov (B,V), aspect (B,V) or None -> (B,V,J,2) normalised, clamped (y, x)."""
     B, V, J = _kp_sizes(R, joints.shape[1])
     out = torch.empty(B, V, J, 2, dtype=joints.dtype, device=joints.device)
-    _lib.check(_lib.load().smil_kp_project(_ptr(joints), _ptr(R), _ptr(T), _ptr(fov), _ptr(aspect), B, V, J, float(S),
-                                           ROT_DTYPES[joints.dtype], _ptr(out), _stream()), "smil_kp_project")
+    _lib.checked().smil_kp_project(_ptr(joints), _ptr(R), _ptr(T), _ptr(fov), _ptr(aspect), B, V, J, float(S), ROT_DTYPES[joints.dtype], _ptr(out),
+                                   _stream())
     return out
 
 
@@ -1487,9 +1468,8 @@ def kp_project_backward(joints, R, T, fov, aspect, dout, S: float, need=(True, T
     B, V, J = _kp_sizes(R, joints.shape[1])
     grads = _kp_camera_grads(joints, R, T, fov, need)
     if any(need):
-        _lib.check(_lib.load().smil_kp_project_backward(_ptr(joints), _ptr(R), _ptr(T), _ptr(fov), _ptr(aspect), _ptr(dout), B, V, J, float(S),
-                                                        ROT_DTYPES[joints.dtype], *(_ptr(g) for g in grads), _stream()),
-                   "smil_kp_project_backward")
+        _lib.checked().smil_kp_project_backward(_ptr(joints), _ptr(R), _ptr(T), _ptr(fov), _ptr(aspect), _ptr(dout), B, V, J, float(S),
+                                                ROT_DTYPES[joints.dtype], *(_ptr(g) for g in grads), _stream())
     return grads
 
 
@@ -1498,10 +1478,9 @@ def kp_project_loss(joints, R, T, fov, aspect, target, vis, view_mask, weights, 
     B, V, J = _kp_sizes(R, joints.shape[1])
     loss = torch.empty((), dtype=joints.dtype, device=joints.device)
     factor = _kp_f64(B * V, device=joints.device)
-    _lib.check(_lib.load().smil_kp_project_loss(_ptr(joints), _ptr(R), _ptr(T), _ptr(fov), _ptr(aspect), _ptr(target), _ptr(vis),
-                                                _ptr(view_mask), _ptr(weights), B, V, J, float(S), ROT_DTYPES[joints.dtype],
-                                                _ptr(_kp_f64(B * V, 4, device=joints.device)), _ptr(factor), _ptr(loss), _stream()),
-               "smil_kp_project_loss")
+    _lib.checked().smil_kp_project_loss(_ptr(joints), _ptr(R), _ptr(T), _ptr(fov), _ptr(aspect), _ptr(target), _ptr(vis), _ptr(view_mask),
+                                        _ptr(weights), B, V, J, float(S), ROT_DTYPES[joints.dtype], _ptr(_kp_f64(B * V, 4, device=joints.device)),
+                                        _ptr(factor), _ptr(loss), _stream())
     return loss, factor
 
 
@@ -1510,10 +1489,9 @@ def kp_project_loss_backward(joints, R, T, fov, aspect, target, vis, view_mask, 
     B, V, J = _kp_sizes(R, joints.shape[1])
     grads = _kp_camera_grads(joints, R, T, fov, need)
     if any(need):
-        _lib.check(_lib.load().smil_kp_project_loss_backward(_ptr(joints), _ptr(R), _ptr(T), _ptr(fov), _ptr(aspect), _ptr(target), _ptr(vis),
-                                                             _ptr(view_mask), _ptr(weights), _ptr(factor), _ptr(upstream), B, V, J, float(S),
-                                                             ROT_DTYPES[joints.dtype], *(_ptr(g) for g in grads), _stream()),
-                   "smil_kp_project_loss_backward")
+        _lib.checked().smil_kp_project_loss_backward(_ptr(joints), _ptr(R), _ptr(T), _ptr(fov), _ptr(aspect), _ptr(target), _ptr(vis),
+                                                     _ptr(view_mask), _ptr(weights), _ptr(factor), _ptr(upstream), B, V, J, float(S),
+                                                     ROT_DTYPES[joints.dtype], *(_ptr(g) for g in grads), _stream())
     return grads
 
 
@@ -1523,9 +1501,8 @@ def kp_triangulate(kp, vis, view_mask, R, T, fov, aspect, S: float, damping: flo
     points = torch.empty(B, J, 3, dtype=kp.dtype, device=kp.device)
     valid = torch.empty(B, J, dtype=torch.uint8, device=kp.device)
     sane = torch.empty_like(valid) if max_norm is not None else None
-    _lib.check(_lib.load().smil_kp_triangulate(_ptr(kp), _ptr(vis), _ptr(view_mask), _ptr(R), _ptr(T), _ptr(fov), _ptr(aspect), B, V, J, float(S),
-                                               float(damping), float(max_norm or 0.0), ROT_DTYPES[kp.dtype], _ptr(points), _ptr(valid),
-                                               _ptr(sane), _stream()), "smil_kp_triangulate")
+    _lib.checked().smil_kp_triangulate(_ptr(kp), _ptr(vis), _ptr(view_mask), _ptr(R), _ptr(T), _ptr(fov), _ptr(aspect), B, V, J, float(S),
+                                       float(damping), float(max_norm or 0.0), ROT_DTYPES[kp.dtype], _ptr(points), _ptr(valid), _ptr(sane), _stream())
     return points, valid, sane
 
 
@@ -1534,10 +1511,9 @@ def kp_triangulate_backward(kp, vis, view_mask, R, T, fov, aspect, dpoints, S: f
     B, V, J = _kp_sizes(R, kp.shape[2])
     grads = tuple(torch.empty_like(t) if n else None for t, n in zip((R, T, fov), need))
     if any(need):
-        _lib.check(_lib.load().smil_kp_triangulate_backward(_ptr(kp), _ptr(vis), _ptr(view_mask), _ptr(R), _ptr(T), _ptr(fov), _ptr(aspect),
-                                                            _ptr(dpoints), B, V, J, float(S), float(damping), ROT_DTYPES[kp.dtype],
-                                                            _ptr(_kp_f64(B, J, 6, device=kp.device)), *(_ptr(g) for g in grads), _stream()),
-                   "smil_kp_triangulate_backward")
+        _lib.checked().smil_kp_triangulate_backward(_ptr(kp), _ptr(vis), _ptr(view_mask), _ptr(R), _ptr(T), _ptr(fov), _ptr(aspect), _ptr(dpoints), B,
+                                                    V, J, float(S), float(damping), ROT_DTYPES[kp.dtype], _ptr(_kp_f64(B, J, 6, device=kp.device)),
+                                                    *(_ptr(g) for g in grads), _stream())
     return grads
 
 
@@ -1556,10 +1532,9 @@ def align_forward(src: torch.Tensor, dst: torch.Tensor, weights, mask, with_scal
     R, t, s, gap, rms = new(B, 3, 3), new(B, 3), new(B), new(B), new(B)
     status = new(B, dtype=torch.int32)
     w_final, saved = new(B, J, dtype=torch.float64), new(B, _lib.ALIGN_SAVED, dtype=torch.float64)
-    _lib.check(_lib.load().smil_align_forward(_ptr(src), _ptr(dst), _ptr(weights), int(weights is not None and weights.dim() == 2), _ptr(mask),
-                                              B, J, int(bool(with_scale)), float(min_gap), int(robust_iters), float(robust_scale),
-                                              ROT_DTYPES[src.dtype], _ptr(R), _ptr(t), _ptr(s), _ptr(status), _ptr(gap), _ptr(rms),
-                                              _ptr(w_final), _ptr(saved), _stream()), "smil_align_forward")
+    _lib.checked().smil_align_forward(_ptr(src), _ptr(dst), _ptr(weights), int(weights is not None and weights.dim() == 2), _ptr(mask), B, J,
+                                      int(bool(with_scale)), float(min_gap), int(robust_iters), float(robust_scale), ROT_DTYPES[src.dtype], _ptr(R),
+                                      _ptr(t), _ptr(s), _ptr(status), _ptr(gap), _ptr(rms), _ptr(w_final), _ptr(saved), _stream())
     return R, t, s, status, gap, rms, w_final, saved
 
 
@@ -1569,9 +1544,8 @@ def align_backward(src, dst, w_final, saved, status, gR, gt, gs, with_scale: boo
     dsrc = torch.empty_like(src) if need[0] else None
     ddst = torch.empty_like(dst) if need[1] else None
     if any(need):
-        _lib.check(_lib.load().smil_align_backward(_ptr(src), _ptr(dst), _ptr(w_final), _ptr(saved), _ptr(status), _ptr(gR), _ptr(gt), _ptr(gs),
-                                                   B, J, int(bool(with_scale)), ROT_DTYPES[src.dtype], _ptr(dsrc), _ptr(ddst), _stream()),
-                   "smil_align_backward")
+        _lib.checked().smil_align_backward(_ptr(src), _ptr(dst), _ptr(w_final), _ptr(saved), _ptr(status), _ptr(gR), _ptr(gt), _ptr(gs), B, J,
+                                           int(bool(with_scale)), ROT_DTYPES[src.dtype], _ptr(dsrc), _ptr(ddst), _stream())
     return dsrc, ddst
 
 
@@ -1581,9 +1555,8 @@ def align_errors(pred, target, mask, mode: int, sentinel: bool, scale: float, mi
     dist = torch.empty(B, J, dtype=pred.dtype, device=pred.device)
     valid = torch.empty(B, J, dtype=torch.uint8, device=pred.device)
     status = torch.empty(B, dtype=torch.int32, device=pred.device)
-    _lib.check(_lib.load().smil_align_errors(_ptr(pred), _ptr(target), _ptr(mask), B, J, int(mode), int(bool(sentinel)), float(scale),
-                                             float(min_gap), ROT_DTYPES[pred.dtype], _ptr(dist), _ptr(valid), _ptr(status), _stream()),
-               "smil_align_errors")
+    _lib.checked().smil_align_errors(_ptr(pred), _ptr(target), _ptr(mask), B, J, int(mode), int(bool(sentinel)), float(scale), float(min_gap),
+                                     ROT_DTYPES[pred.dtype], _ptr(dist), _ptr(valid), _ptr(status), _stream())
     return dist, valid, status
 
 
@@ -1651,8 +1624,7 @@ def joints_forward(jt: DeviceJointTables, beta, theta, trans=None, logscale=None
     i = _joints_inputs(jt, beta, theta, trans, logscale, btrans, theta_mask, fl)
     joints = torch.empty(i.B, jt.J, 3, dtype=torch.float32, device=jt.device)
     new_J = torch.empty_like(joints) if want_new_J else None
-    _lib.check(_lib.load().smil_joints_forward(ctypes.byref(jt.struct), ctypes.byref(i), _ptr(joints), _ptr(new_J), _stream()),
-               "smil_joints_forward")
+    _lib.checked().smil_joints_forward(ctypes.byref(jt.struct), ctypes.byref(i), _ptr(joints), _ptr(new_J), _stream())
     return joints, new_J
 
 
@@ -1679,10 +1651,10 @@ def joints_backward(jt: DeviceJointTables, d_joints, beta, theta, trans=None, lo
     g.d_joints = _ptr(d_joints)
     for k, v in out.items():
         setattr(g, k, _ptr(v))
-    lib = _lib.load()
+    lib = _lib.checked()
     ws = jt.workspace(int(lib.smil_joints_backward_workspace_bytes(ctypes.byref(jt.struct), ctypes.byref(i), ctypes.byref(g))))
     g.workspace = _ptr(ws)
-    _lib.check(lib.smil_joints_backward(ctypes.byref(jt.struct), ctypes.byref(i), ctypes.byref(g), _stream()), "smil_joints_backward")
+    lib.smil_joints_backward(ctypes.byref(jt.struct), ctypes.byref(i), ctypes.byref(g), _stream())
     return out
 
 
@@ -1702,13 +1674,12 @@ def kp3d_fit_eval(cfg: _lib.FitConfig, jt: DeviceJointTables, w_k3d: float, robu
         raise ValueError(f"visibility must be a contiguous uint8 ({N},{Jc}) tensor")
     if joint_weights is not None and (joint_weights.dtype != torch.float64 or tuple(joint_weights.shape) != (Jc,)):
         raise ValueError(f"joint_weights must be float64 ({Jc},)")
-    lib = _lib.load()
+    lib = _lib.checked()
     ws = jt.workspace(int(lib.smil_kp3d_fit_eval_workspace_bytes(ctypes.byref(jt.struct), ctypes.byref(i), int(d_betas is not None),
                                                                  int(d_logscale is not None), int(d_btrans is not None))))
-    _lib.check(lib.smil_kp3d_fit_eval(ctypes.byref(cfg), float(w_k3d), float(robust_scale), ctypes.byref(jt.struct), ctypes.byref(i), Jc,
-                                      _ptr(canon), _ptr(target), _ptr(visibility), _ptr(joint_weights), _ptr(objs), _ptr(d_pose),
-                                      _ptr(d_trans), _ptr(d_betas), _ptr(d_logscale), _ptr(d_btrans), _ptr(joints_out), _ptr(ws),
-                                      _stream()), "smil_kp3d_fit_eval")
+    lib.smil_kp3d_fit_eval(ctypes.byref(cfg), float(w_k3d), float(robust_scale), ctypes.byref(jt.struct), ctypes.byref(i), Jc, _ptr(canon),
+                           _ptr(target), _ptr(visibility), _ptr(joint_weights), _ptr(objs), _ptr(d_pose), _ptr(d_trans), _ptr(d_betas),
+                           _ptr(d_logscale), _ptr(d_btrans), _ptr(joints_out), _ptr(ws), _stream())
 
 
 def kp2d_fit_eval(cfg: _lib.FitConfig, jt: DeviceJointTables, cams: CameraSet, w_k2d: float, robust_scale_px: float, canon, target2d,
@@ -1743,15 +1714,14 @@ def kp2d_fit_eval(cfg: _lib.FitConfig, jt: DeviceJointTables, cams: CameraSet, w
     if canon is None and Jc > jt.J:
         raise ValueError(f"Jc={Jc} above J={jt.J} without a canon list")
     cam = cams.struct(N * Nv)
-    lib = _lib.load()
+    lib = _lib.checked()
     ws = jt.workspace(int(lib.smil_kp2d_fit_eval_workspace_bytes(ctypes.byref(jt.struct), ctypes.byref(i), ctypes.byref(cam),
                                                                  int(d_betas is not None), int(d_logscale is not None),
                                                                  int(d_btrans is not None))))
-    _lib.check(lib.smil_kp2d_fit_eval(ctypes.byref(cfg), float(w_k2d), float(robust_scale_px), ctypes.byref(jt.struct), ctypes.byref(i),
-                                      ctypes.byref(cam), Jc, _ptr(canon), _ptr(target2d), _ptr(visibility2d), _ptr(confidence),
-                                      _ptr(joint_weights), float(w_k3d), float(robust_scale), _ptr(target3d), _ptr(visibility3d), _ptr(objs),
-                                      _ptr(d_pose), _ptr(d_trans), _ptr(d_betas), _ptr(d_logscale), _ptr(d_btrans), _ptr(joints_out),
-                                      _ptr(yx_out), _ptr(ws), _stream()), "smil_kp2d_fit_eval")
+    lib.smil_kp2d_fit_eval(ctypes.byref(cfg), float(w_k2d), float(robust_scale_px), ctypes.byref(jt.struct), ctypes.byref(i), ctypes.byref(cam), Jc,
+                           _ptr(canon), _ptr(target2d), _ptr(visibility2d), _ptr(confidence), _ptr(joint_weights), float(w_k3d), float(robust_scale),
+                           _ptr(target3d), _ptr(visibility3d), _ptr(objs), _ptr(d_pose), _ptr(d_trans), _ptr(d_betas), _ptr(d_logscale),
+                           _ptr(d_btrans), _ptr(joints_out), _ptr(yx_out), _ptr(ws), _stream())
 
 
 def adam_step_multi_bc64(items, beta1=0.5, beta2=0.999, eps=1e-8):
@@ -1803,15 +1773,14 @@ def hull_carve(spec: HullGridSpec, masks: torch.Tensor, cams: CameraSet, min_vie
     N, Nv = spec.N, int(cams.views)
     masks = _hull_masks(masks, N, Nv)
     H, W = int(masks.shape[2]), int(masks.shape[3])
-    lib = _lib.load()
+    lib = _lib.checked()
     cam = cams.struct(N * Nv)
     occ = torch.empty(spec.shape(), dtype=torch.uint8, device=dev)
     fg = torch.empty_like(occ) if want_counts else None
     seen = torch.empty_like(occ) if want_counts else None
-    ws = torch.empty(max(1, int(lib.smil_hull_carve_workspace_bytes(ctypes.byref(spec.struct)))), dtype=torch.uint8, device=dev)
-    _lib.check(lib.smil_hull_carve(ctypes.byref(spec.struct), _ptr(masks), int(masks.dtype == torch.float32), H, W, float(threshold),
-                                   ctypes.byref(cam), int(min_views), int(max_misses), int(bool(outside_carves)), _ptr(occ), _ptr(fg),
-                                   _ptr(seen), _ptr(ws), _stream()), "smil_hull_carve")
+    ws = _workspace(max(1, lib.smil_hull_carve_workspace_bytes(ctypes.byref(spec.struct))), dev)
+    lib.smil_hull_carve(ctypes.byref(spec.struct), _ptr(masks), int(masks.dtype == torch.float32), H, W, float(threshold), ctypes.byref(cam),
+                        int(min_views), int(max_misses), int(bool(outside_carves)), _ptr(occ), _ptr(fg), _ptr(seen), _ptr(ws), _stream())
     return occ, fg, seen
 
 
@@ -1826,9 +1795,8 @@ def hull_query(points: torch.Tensor, masks: torch.Tensor, cams: CameraSet, outsi
     cam = cams.struct(N * Nv)
     fg = torch.empty(N, P, dtype=torch.uint8, device=dev)
     seen = torch.empty_like(fg)
-    _lib.check(_lib.load().smil_hull_query(_ptr(points), N, P, _ptr(masks), int(masks.dtype == torch.float32), int(masks.shape[2]),
-                                           int(masks.shape[3]), float(threshold), ctypes.byref(cam), int(bool(outside_carves)), _ptr(fg),
-                                           _ptr(seen), _stream()), "smil_hull_query")
+    _lib.checked().smil_hull_query(_ptr(points), N, P, _ptr(masks), int(masks.dtype == torch.float32), int(masks.shape[2]), int(masks.shape[3]),
+                                   float(threshold), ctypes.byref(cam), int(bool(outside_carves)), _ptr(fg), _ptr(seen), _stream())
     return fg, seen
 
 
@@ -1844,7 +1812,7 @@ def hull_stats(spec: HullGridSpec, occ: torch.Tensor) -> torch.Tensor:
     the occupied voxels."""
     occ = _hull_occ(spec, occ)
     stats = torch.empty(spec.N, _lib.HULL_STATS, dtype=torch.int64, device=occ.device)
-    _lib.check(_lib.load().smil_hull_stats(ctypes.byref(spec.struct), _ptr(occ), _ptr(stats), _stream()), "smil_hull_stats")
+    _lib.checked().smil_hull_stats(ctypes.byref(spec.struct), _ptr(occ), _ptr(stats), _stream())
     return stats
 
 
@@ -1853,16 +1821,15 @@ def hull_surface(spec: HullGridSpec, occ: torch.Tensor, want_index: bool = False
     waits ONCE, for ``offsets[N]``, to size the outputs."""
     occ = _hull_occ(spec, occ)
     dev = occ.device
-    lib = _lib.load()
-    ws = torch.empty(max(1, int(lib.smil_hull_surface_workspace_bytes(ctypes.byref(spec.struct)))), dtype=torch.uint8, device=dev)
+    lib = _lib.checked()
+    ws = _workspace(max(1, lib.smil_hull_surface_workspace_bytes(ctypes.byref(spec.struct))), dev)
     offsets = torch.empty(spec.N + 1, dtype=torch.int64, device=dev)
-    _lib.check(lib.smil_hull_surface_count(ctypes.byref(spec.struct), _ptr(occ), _ptr(offsets), _ptr(ws), _stream()), "smil_hull_surface_count")
+    lib.smil_hull_surface_count(ctypes.byref(spec.struct), _ptr(occ), _ptr(offsets), _ptr(ws), _stream())
     total = int(offsets[-1].item())
     points = torch.empty(total, 3, dtype=torch.float32, device=dev)
     index = torch.empty(total, dtype=torch.int64, device=dev) if want_index else None
     if total:
-        _lib.check(lib.smil_hull_surface_write(ctypes.byref(spec.struct), _ptr(occ), _ptr(ws), _ptr(points), _ptr(index), _stream()),
-                   "smil_hull_surface_write")
+        lib.smil_hull_surface_write(ctypes.byref(spec.struct), _ptr(occ), _ptr(ws), _ptr(points), _ptr(index), _stream())
     return points, index, offsets
 
 
@@ -1874,19 +1841,19 @@ def hull_mesh(spec: HullGridSpec, occ: torch.Tensor, weights=(), want_normals: b
     occ = _hull_occ(spec, occ)
     dev = occ.device
     w = np.ascontiguousarray(np.asarray(tuple(weights), np.float64).reshape(-1))
-    lib = _lib.load()
+    lib = _lib.checked()
     grid = ctypes.byref(spec.struct)
-    ws = torch.empty(max(1, int(lib.smil_hull_mesh_workspace_bytes(grid))), dtype=torch.uint8, device=dev)
+    ws = _workspace(max(1, lib.smil_hull_mesh_workspace_bytes(grid)), dev)
     offsets = torch.empty(2, spec.N + 1, dtype=torch.int64, device=dev)
-    _lib.check(lib.smil_hull_mesh_count(grid, _ptr(occ), _ptr(offsets[0]), _ptr(offsets[1]), _ptr(ws), _stream()), "smil_hull_mesh_count")
+    lib.smil_hull_mesh_count(grid, _ptr(occ), _ptr(offsets[0]), _ptr(offsets[1]), _ptr(ws), _stream())
     n_verts, n_faces = (int(t) for t in offsets[:, -1].tolist())
     verts = torch.empty(n_verts, 3, dtype=torch.float32, device=dev)
     normals = torch.empty(n_verts, 3, dtype=torch.float32, device=dev) if want_normals else None
     faces = torch.empty(n_faces, 3, dtype=torch.int64, device=dev)
     # (both totals 0: the call validates its arguments and launches nothing)
-    scratch = torch.empty(max(1, int(lib.smil_hull_mesh_scratch_bytes(n_verts, len(w)))), dtype=torch.uint8, device=dev)
-    _lib.check(lib.smil_hull_mesh_write(grid, _ptr(occ), _ptr(ws), _ptr(scratch), n_verts, n_faces, w.ctypes.data if len(w) else None, len(w),
-                                        _ptr(verts), _ptr(normals), _ptr(faces), _stream()), "smil_hull_mesh_write")
+    scratch = _workspace(max(1, lib.smil_hull_mesh_scratch_bytes(n_verts, len(w))), dev)
+    lib.smil_hull_mesh_write(grid, _ptr(occ), _ptr(ws), _ptr(scratch), n_verts, n_faces, w.ctypes.data if len(w) else None, len(w), _ptr(verts),
+                             _ptr(normals), _ptr(faces), _stream())
     return verts, normals, faces, offsets[0], offsets[1]
 
 
@@ -1895,11 +1862,10 @@ def hull_edt(spec: HullGridSpec, occ: torch.Tensor, invert: bool = False, border
     """smil_hull_edt: occ (N,Gz,Gy,Gx) uint8 -> d2 (N,Gz,Gy,Gx) int32, the squared voxel distance of every voxel to the nearest one with
     ``occ != 0`` (``invert``: ``== 0``; ``border``: the one-voxel layer around the grid counts too); ``_lib.EDT_NONE`` where there is none."""
     occ = _hull_occ(spec, occ)
-    lib = _lib.load()
+    lib = _lib.checked()
     d2 = torch.empty(spec.shape(), dtype=torch.int32, device=occ.device)
-    ws = torch.empty(max(1, int(lib.smil_hull_edt_workspace_bytes(ctypes.byref(spec.struct)))), dtype=torch.uint8, device=occ.device)
-    _lib.check(lib.smil_hull_edt(ctypes.byref(spec.struct), _ptr(occ), int(bool(invert)), int(bool(border)), _ptr(d2), _ptr(ws), _stream()),
-               "smil_hull_edt")
+    ws = _workspace(max(1, lib.smil_hull_edt_workspace_bytes(ctypes.byref(spec.struct))), occ.device)
+    lib.smil_hull_edt(ctypes.byref(spec.struct), _ptr(occ), int(bool(invert)), int(bool(border)), _ptr(d2), _ptr(ws), _stream())
     return d2
 
 
@@ -1919,12 +1885,11 @@ def field_sample(spec: HullGridSpec, d2_out: torch.Tensor, d2_in: Optional[torch
         raise ValueError(f"points must be ({spec.N},P,2 or 3), got {tuple(points.shape)}")
     P, dim = int(points.shape[1]), int(points.shape[2])
     points = _f32(points, dev)
-    lib = _lib.load()
+    lib = _lib.checked()
     value = torch.empty(spec.N, P, dtype=torch.float32, device=dev)
     grad = torch.empty(spec.N, P, dim, dtype=torch.float32, device=dev) if want_grad else None
     if P == 0:  # (an empty tensor has no address to pass)
         return value, grad
-    ws = torch.empty(max(1, int(lib.smil_hull_carve_workspace_bytes(ctypes.byref(spec.struct)))), dtype=torch.uint8, device=dev)
-    _lib.check(lib.smil_field_sample(ctypes.byref(spec.struct), _ptr(d2_out), _ptr(d2_in), _ptr(points), dim, P, _ptr(value), _ptr(grad),
-                                     _ptr(ws), _stream()), "smil_field_sample")
+    ws = _workspace(max(1, lib.smil_hull_carve_workspace_bytes(ctypes.byref(spec.struct))), dev)
+    lib.smil_field_sample(ctypes.byref(spec.struct), _ptr(d2_out), _ptr(d2_in), _ptr(points), dim, P, _ptr(value), _ptr(grad), _ptr(ws), _stream())
     return value, grad

@@ -24,9 +24,8 @@ from typing import Optional
 
 import numpy as np
 
+from ._lib import MAX_JOINTS  # the skin table's 8-bit bone ids
 from .model_io import MAX_BONES_PER_VERTEX, SmilModelTables
-
-MAX_JOINTS = 256  # SMIL_MAX_JOINTS: the skin table's 8-bit bone ids
 
 
 @dataclass

@@ -27,7 +27,7 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-MAX_BONES_PER_VERTEX = 4
+from ._lib import MAX_BONES as MAX_BONES_PER_VERTEX
 
 # Only these globals may be resolved while unpickling a model file.  The SMIL
 # pickles reference numpy array reconstruction only; legacy SMAL/SMPL pickles
