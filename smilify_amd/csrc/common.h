@@ -187,24 +187,36 @@ __device__ __forceinline__ float row_sum16(float v) {
     return v;
 }
 
-__device__ __forceinline__ float wave_max(float v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+// Every other fold over the 64 lanes is ONE xor butterfly: op(own value, the partner's).  Both partners of an exchange combine the
+// same two numbers, so every lane ends with the same bits and the result depends on nothing but the values (the float64 sum of
+// triangulate.hip relies on it).  wave_sum(float) above is not one of them: its DPP order defines its bits.
+template <class T, class Op> __device__ __forceinline__ T wave_fold(T v, Op op) {
+    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ int wave_sum(int v) { return wave_fold(v, [](int a, int b) { return a + b; }); }
+__device__ __forceinline__ long long wave_sum(long long v) { return wave_fold(v, [](long long a, long long b) { return a + b; }); }
+__device__ __forceinline__ double wave_sum(double v) { return wave_fold(v, [](double a, double b) { return a + b; }); }
+__device__ __forceinline__ int wave_min(int v) { return wave_fold(v, [](int a, int b) { return min(a, b); }); }
+__device__ __forceinline__ long long wave_min(long long v) { return wave_fold(v, [](long long a, long long b) { return b < a ? b : a; }); }
+__device__ __forceinline__ float wave_max(float v) { return wave_fold(v, [](float a, float b) { return fmaxf(a, b); }); }
+__device__ __forceinline__ int wave_max(int v) { return wave_fold(v, [](int a, int b) { return max(a, b); }); }
+__device__ __forceinline__ long long wave_max(long long v) { return wave_fold(v, [](long long a, long long b) { return b > a ? b : a; }); }
+__device__ __forceinline__ double wave_max(double v) { return wave_fold(v, [](double a, double b) { return fmax(a, b); }); }
+
+// inclusive sum over the lanes up to and including this one
+template <class T> __device__ __forceinline__ T wave_scan_inclusive(T v) {
+    const int lane = threadIdx.x & 63;
+    for (int o = 1; o < 64; o <<= 1) {
+        const T w = __shfl_up(v, o, 64);
+        if (lane >= o) v += w;
+    }
     return v;
 }
 
-__device__ __forceinline__ int wave_max(int v) {
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-// float64 (triangulate.hip): the value of a lane, and the sum over the 64 lanes as a butterfly.  Both partners of an exchange add
-// the same two numbers, so every lane ends with the same bits and the result depends on nothing but the values.
+// the value of a lane, float64 (triangulate.hip)
 __device__ __forceinline__ double read_lane(double v, int lane) {
     return __builtin_bit_cast(double, read_lane(__builtin_bit_cast(unsigned long long, v), lane));
-}
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // Block-wide sum for blocks of up to 1024 threads; result valid in thread 0 (and all threads of wave 0).

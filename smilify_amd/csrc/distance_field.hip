@@ -262,11 +262,7 @@ __global__ void __launch_bounds__(HULL_THREADS) k_field_sample(FieldArgs a) {
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
 static int check_edt_grid(const char *who, const SmilHullGrid *g, long long *vox) {
-    SMIL_REQUIRE(g, "%s: null grid argument", who);
-    SMIL_REQUIRE(g->N >= 1, "%s: N=%d frames", who, g->N);
-    SMIL_REQUIRE(g->Gx >= 1 && g->Gy >= 1 && g->Gz >= 1, "%s: grid extent %d x %d x %d below 1", who, g->Gx, g->Gy, g->Gz);
-    SMIL_REQUIRE((long long)g->Gx * g->Gy <= HULL_MAX_VOXELS / g->Gz, "%s: grid %d x %d x %d exceeds 2^40 voxels a frame", who, g->Gx, g->Gy, g->Gz);
-    *vox = (long long)g->Gx * g->Gy * g->Gz;
+    if (int rc = check_hull_extent(who, g, vox)) return rc;
     const long long sx = (long long)g->Gx + 1, sy = (long long)g->Gy + 1, sz = (long long)g->Gz + 1;
     SMIL_REQUIRE(sx <= 46341 && sy <= 46341 && sz <= 46341 && sx * sx + sy * sy + sz * sz < (1LL << 31),
                  "%s: grid %d x %d x %d: squared distances exceed an int32", who, g->Gx, g->Gy, g->Gz);
@@ -279,8 +275,7 @@ static bool edt_fused(const SmilHullGrid *g) { return (long long)g->Gx * g->Gy <
 static bool edt_needs_second(const SmilHullGrid *g) { return (!edt_fused(g) && g->Gy > EDT_MAX_LINE) || g->Gz > EDT_MAX_LINE; }
 
 extern "C" size_t smil_hull_edt_workspace_bytes(const SmilHullGrid *g) {
-    if (!g || g->N < 1 || g->Gx < 1 || g->Gy < 1 || g->Gz < 1) return 0;
-    if ((long long)g->Gx * g->Gy > HULL_MAX_VOXELS / g->Gz) return 0;
+    if (!hull_extent_ok(g)) return 0;
     Workspace ws{nullptr};
     ws.take<int>(edt_needs_second(g) ? (size_t)g->N * (size_t)g->Gx * (size_t)g->Gy * (size_t)g->Gz : 1);
     return ws.used;

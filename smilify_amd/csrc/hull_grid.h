@@ -1,5 +1,6 @@
 // What the translation units that work on a SmilHullGrid share (visual_hull.hip, distance_field.hip, hull_mesh.hip): the launch constants the
-// grid's checks depend on, the device view of a grid, its validation, and the workspace layout that carries the caller's host tables.
+// grid's checks depend on, the device view of a grid, the workgroup scan and the scan of per-workgroup counts that the surface and the
+// mesh share, the grid's validation, and the workspace layout that carries the caller's host tables.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -21,14 +22,51 @@ struct HullGridDev {
 
 static inline long long hull_chunks(long long vox, int per_block) { return (vox + per_block - 1) / per_block; }
 
-// the grid's sizes; `tables`: origin and voxel_size are read too
-static inline int check_hull_grid(const char *who, const SmilHullGrid *g, bool tables, long long *vox_out) {
+// The exclusive prefix of `mine` over the THREADS threads of the workgroup, and their sum in `total`: an inclusive scan of every
+// wave, lane 63 stores its wave's sum, every thread adds the waves before it.  s_wave: THREADS / 64 entries of LDS, which a caller
+// that comes back (the scan's rounds) may rewrite only behind a barrier of its own.
+template <class T, int THREADS> __device__ __forceinline__ T block_scan_exclusive(T mine, T *s_wave, T &total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const T incl = wave_scan_inclusive(mine);
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    T before = 0;
+    total = 0;
+    for (int w = 0; w < THREADS / 64; ++w) {
+        before += w < wave ? s_wave[w] : 0;
+        total += s_wave[w];
+    }
+    return before + incl - mine;
+}
+
+// (visual_hull.hip) Per-workgroup counts -> their exclusive prefixes, in place, for one or two jobs over the same n = N x chunks
+// counts: offsets[f] = scale x the prefix of frame f's first workgroup, offsets[N] = scale x the total, which write_total_at_n
+// also leaves in counts[n].  One workgroup of HULL_SCAN_THREADS per job.
+#define HULL_SCAN_THREADS 1024
+struct HullScanJob {
+    long long *counts, *offsets;
+    long long scale;
+    int write_total_at_n;
+};
+int hull_scan(const HullScanJob *jobs, int n_jobs, long long n, long long chunks, int N, hipStream_t stream);
+
+// what every check of a grid starts with: the grid is there, holds frames and voxels, at most 2^40 a frame (their number out)
+static inline int check_hull_extent(const char *who, const SmilHullGrid *g, long long *vox) {
     SMIL_REQUIRE(g, "%s: null grid argument", who);
     SMIL_REQUIRE(g->N >= 1, "%s: N=%d frames", who, g->N);
     SMIL_REQUIRE(g->Gx >= 1 && g->Gy >= 1 && g->Gz >= 1, "%s: grid extent %d x %d x %d below 1", who, g->Gx, g->Gy, g->Gz);
-    const long long vox = (long long)g->Gx * g->Gy;  // < 2^62
-    SMIL_REQUIRE(vox <= HULL_MAX_VOXELS / g->Gz, "%s: grid %d x %d x %d exceeds 2^40 voxels a frame", who, g->Gx, g->Gy, g->Gz);
-    *vox_out = vox * g->Gz;
+    SMIL_REQUIRE((long long)g->Gx * g->Gy <= HULL_MAX_VOXELS / g->Gz, "%s: grid %d x %d x %d exceeds 2^40 voxels a frame", who, g->Gx, g->Gy, g->Gz);
+    *vox = (long long)g->Gx * g->Gy * g->Gz;
+    return SMIL_OK;
+}
+// the same conditions without a word (the *_workspace_bytes functions answer 0)
+static inline bool hull_extent_ok(const SmilHullGrid *g) {
+    return g && g->N >= 1 && g->Gx >= 1 && g->Gy >= 1 && g->Gz >= 1 && (long long)g->Gx * g->Gy <= HULL_MAX_VOXELS / g->Gz;
+}
+
+// the grid's sizes; `tables`: origin and voxel_size are read too
+static inline int check_hull_grid(const char *who, const SmilHullGrid *g, bool tables, long long *vox_out) {
+    if (int rc = check_hull_extent(who, g, vox_out)) return rc;
     // the grid of the launch with the fewest voxels per workgroup (HULL_VOX = HULL_SURF_VOX per thread)
     SMIL_REQUIRE(hull_chunks(*vox_out, HULL_VOX * HULL_THREADS) <= 0x7FFFFFFFLL / g->N, "%s: N=%d frames of %lld voxels exceed the grid", who, g->N,
                  *vox_out);

@@ -10,7 +10,8 @@
 //                      sample share them through the caches), __ballot of "active" -> the word's 64-bit mask, ballots of the three owned
 //                      sign-changing edges -> its quad count.  A workgroup of 4 waves takes MESH_BLOCK_WORDS = 32 words, leaves the
 //                      words' exclusive prefixes inside the workgroup packed in 32 bits (vertices low, quads high) and its two totals.
-//  * k_mesh_scan       one block: the workgroups' totals -> exclusive prefixes (the totals behind the last), the frames' offsets out.
+//  * hull_scan         (hull_grid.h; the kernel is visual_hull.hip's k_hull_scan) the workgroups' totals -> exclusive prefixes (the
+//                      totals behind the last), the frames' offsets out: one workgroup for the vertices, one for the quads.
 //  * mesh_vertex_id    the only lookup the later kernels need: prefix[workgroup] + prefix[word] + popcount(mask[word] & lower lanes) -
 //                      12 bytes per 64 cubes of workspace instead of a dense index grid; its three loads do not depend on each other.
 //  * k_mesh_emit       the same walk, a word whose mask is 0 skipped (a wave-uniform test): the corners again, the start position
@@ -31,7 +32,6 @@
 #define MESH_BLOCK_WORDS 32                                // words of 64 cubes per workgroup
 #define MESH_WAVE_WORDS (MESH_BLOCK_WORDS / (HULL_THREADS / 64))
 #define MESH_BLOCK_CUBES (MESH_BLOCK_WORDS * 64)
-#define MESH_SCAN_THREADS 1024
 #define MESH_MAX_BLOCKS (1LL << 28)                        // N x workgroups of a frame: the per-vertex launches stay below 2^31 blocks
 
 struct MeshGrid {
@@ -115,50 +115,6 @@ __global__ void __launch_bounds__(HULL_THREADS) k_mesh_classify(const unsigned c
     }
     vcount[blockIdx.x] = v;
     qcount[blockIdx.x] = qd;
-}
-
-// ---- scan -------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ long long mesh_wave_scan(long long v) {  // inclusive
-    const int lane = threadIdx.x & 63;
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long w = __shfl_up(v, o, 64);
-        if (lane >= o) v += w;
-    }
-    return v;
-}
-
-// counts (n, then one more entry) -> exclusive prefixes in place, the total in entry n; offsets[f] = scale x the prefix of frame f's
-// first workgroup, offsets[N] = scale x the total.  blockIdx.x 0: vertices, 1: quads (two triangles each).
-__global__ void __launch_bounds__(MESH_SCAN_THREADS) k_mesh_scan(long long *vcount, long long *qcount, long long n, long long blocks, int N,
-                                                                 long long *vert_offsets, long long *face_offsets) {
-    __shared__ long long s_wave[MESH_SCAN_THREADS / 64];
-    long long *counts = blockIdx.x ? qcount : vcount, *offsets = blockIdx.x ? face_offsets : vert_offsets;
-    const long long scale = blockIdx.x ? 2 : 1;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long carry = 0;
-    for (long long base = 0; base < n; base += MESH_SCAN_THREADS) {
-        const long long e = base + threadIdx.x;
-        const long long c = e < n ? counts[e] : 0;
-        const long long incl = mesh_wave_scan(c);
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        long long before = 0, total = 0;
-        for (int w = 0; w < MESH_SCAN_THREADS / 64; ++w) {
-            before += w < wave ? s_wave[w] : 0;
-            total += s_wave[w];
-        }
-        __syncthreads();  // (the next round rewrites s_wave)
-        const long long excl = carry + before + incl - c;
-        if (e < n) {
-            counts[e] = excl;
-            if (e % blocks == 0) offsets[e / blocks] = scale * excl;
-        }
-        carry += total;
-    }
-    if (threadIdx.x == 0) {
-        counts[n] = carry;
-        offsets[N] = scale * carry;
-    }
 }
 
 // ---- emit -------------------------------------------------------------------------------------------------------------------
@@ -432,10 +388,9 @@ extern "C" int smil_hull_mesh_count(const SmilHullGrid *g, const uint8_t *occ, i
     hipLaunchKernelGGL(k_mesh_classify, dim3((unsigned)d.all_blocks), dim3(HULL_THREADS), 0, stream, (const unsigned char *)occ, d, w.mask, w.wpre,
                        w.vpre, w.qpre);
     SMIL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_mesh_scan, dim3(2), dim3(MESH_SCAN_THREADS), 0, stream, w.vpre, w.qpre, d.all_blocks, (long long)d.blocks, g->N,
-                       (long long *)vert_offsets, (long long *)face_offsets);
-    SMIL_LAUNCH_CHECK();
-    return SMIL_OK;
+    // vertices, and quads of two triangles each; the totals stay behind the prefixes (mesh_counts_agree)
+    const HullScanJob jobs[2] = {{w.vpre, (long long *)vert_offsets, 1, 1}, {w.qpre, (long long *)face_offsets, 2, 1}};
+    return hull_scan(jobs, 2, d.all_blocks, (long long)d.blocks, g->N, stream);
 }
 
 struct MeshScratch { double *pos[2]; long long *vcube; unsigned char *cfg; size_t bytes; };

@@ -5,7 +5,7 @@
 // crop_to_silhouette (smal_fitter/utils.py:7-49), host loops over single frames.  The semantics are stated at include/smilfit.h.
 //
 //  * k_image_bounds   exact integer reduction of one image (or one slab of rows of it): lanes stride over the pixels, wave minima /
-//                     maxima / count by butterfly, the waves meet in LDS, one lane stores.  An image of more than BOUNDS_SPLIT
+//                     maxima / count by butterfly (common.h), the waves meet in LDS, one lane stores.  An image of more than BOUNDS_SPLIT
 //                     pixels is cut into slabs whose results meet with integer atomics in a row that k_bounds_init has preset:
 //                     minima, maxima and integer sums do not depend on the order, so the result is bit-reproducible either way.
 //  * k_warp<T, C>     one output pixel (all C channels) per thread, consecutive threads on consecutive pixels of a row-major image:
@@ -27,15 +27,6 @@
 #define WARP_THREADS 256
 
 // ---- bounds -----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int wave_min_i(int v) {
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_sum_i(int v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __global__ void k_bounds_init(int *bounds, long long N, int H, int W) {
     const long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
@@ -69,9 +60,9 @@ __global__ void __launch_bounds__(BOUNDS_THREADS) k_image_bounds(const T *sil, i
             }
         }
     }
-    y_min = wave_min_i(y_min); y_max = wave_max(y_max);
-    x_min = wave_min_i(x_min); x_max = wave_max(x_max);
-    count = wave_sum_i(count);
+    y_min = wave_min(y_min); y_max = wave_max(y_max);
+    x_min = wave_min(x_min); x_max = wave_max(x_max);
+    count = wave_sum(count);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) {
         s_red[wave][0] = y_min; s_red[wave][1] = y_max; s_red[wave][2] = x_min; s_red[wave][3] = x_max; s_red[wave][4] = count;

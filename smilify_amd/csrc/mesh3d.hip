@@ -710,11 +710,6 @@ __global__ void __launch_bounds__(256) k_sdf_stats(SdfArgs a) {
     for (int i = threadIdx.x; i < P; i += 256) z[i] = ((double)v[i] - mean) / sd;
 }
 
-__device__ __forceinline__ double wave_max_f64(double v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, WAVE));
-    return v;
-}
-
 // wave = one query i of direction d, lane k = its k-th neighbour j: w_k = softmax_k(-|z_q[i] - z_c[j]| / 0.1), r_i = sum_k w_k d_k,
 // the owned gradient 2 w sum_k w_k (q - c_j), and -w_k (q - c_j) added to candidate j's fixed-point sums.
 __global__ void __launch_bounds__(256) k_sdf_term(SdfArgs a) {
@@ -731,7 +726,7 @@ __global__ void __launch_bounds__(256) k_sdf_term(SdfArgs a) {
     j = min(max(j, 0), Pc - 1);
     const double zd = fabs(a.z[row] - a.z[ch_row(a.c, n, 1 - d) + j]) * SDF_INV_TEMPERATURE;
     const double lo = on ? -zd : -__builtin_inf();
-    const double top = wave_max_f64(lo);
+    const double top = wave_max(lo);
     const float e = on ? expf((float)(lo - top)) : 0.f;
     const float w = e / wave_sum(e);
     const float r = wave_sum(w * dd);

@@ -523,7 +523,3 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 #undef MAX_STEP
     return (uint32_t)__builtin_amdgcn_readlane(x, WAVE - 1);
 }
-__device__ __forceinline__ double wave_sum_f64(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-    return v;
-}

@@ -296,7 +296,7 @@ __global__ void __launch_bounds__(64, TIE_WAVES_PER_SIMD) k_raster_tie_replay(Ra
             const bool ok0 = lane < qsize, ok1 = lane + WAVE < qsize;
             const float lf0 = ok0 ? __log2f(1.0f - face_prob(qs0, a.inv_sigma_log2e)) : 0.f;
             const float lf1 = ok1 ? __log2f(1.0f - face_prob(qs1, a.inv_sigma_log2e)) : 0.f;
-            const double plog_px = wave_sum_f64((double)lf0 + (double)lf1);
+            const double plog_px = wave_sum((double)lf0 + (double)lf1);
             const float alpha = exp2f((float)plog_px);
             const float silv = 1.0f - alpha;
             const size_t pix = ((size_t)n * a.S + yo) * a.S + xo;

@@ -18,14 +18,17 @@
 //                      contraction off (origin + (i + 0.5) voxel_size: three roundings, specified to the bit - the surface points
 //                      are these numbers rounded once).  A pure gather: no atomics, bit-reproducible by construction.
 //  * k_hull_query      the same for arbitrary float32 points.
-//  * k_hull_stats      exact int64 sums, minima and maxima of the occupied voxel indices: per-thread, wave butterfly, LDS across the
+//  * k_hull_stats      exact int64 sums, minima and maxima of the occupied voxel indices: per-thread, wave butterfly (common.h), LDS across the
 //                      waves, then one set of integer atomics per block into a row that k_hull_stats_init has preset.  Integer sums,
 //                      minima and maxima do not depend on the order.
 //  * k_hull_surface<WRITE>  a block looks at HULL_SURF_VOX consecutive voxels per thread.  WRITE false: its count of surface voxels
-//                      into the workspace; k_hull_scan (one block) turns the counts into exclusive prefixes and the frames' offsets.
-//                      WRITE true: the same flags again, a block-wide exclusive scan of the threads' counts, and every surface voxel
-//                      stored at prefix of its block + prefix of its thread + its rank in the thread: ascending linear voxel index,
-//                      whatever the scheduling.
+//                      into the workspace; k_hull_scan turns the counts into exclusive prefixes and the frames' offsets.
+//                      WRITE true: the same flags again, a block-wide exclusive scan of the threads' counts (block_scan_exclusive,
+//                      hull_grid.h), and every surface voxel stored at prefix of its block + prefix of its thread + its rank in the
+//                      thread: ascending linear voxel index, whatever the scheduling.
+//  * k_hull_scan       the ONE scan of per-workgroup counts, launched through hull_scan (hull_grid.h) by the surface count here (one
+//                      job) and by the mesh count of hull_mesh.hip (two jobs: vertices, and quads scaled to triangles).  A workgroup
+//                      per job scans 1 024 counts a round with block_scan_exclusive and carries the rounds' totals.
 // Every voxel index is 64-bit (N Gx Gy Gz may exceed 2^31; a frame whose own count stays below 2^31 decodes (i, j, k) with 32-bit
 // divisions, a wave-uniform choice).
 #include <algorithm>
@@ -35,7 +38,6 @@
 #include "hull_grid.h"
 
 #define HULL_STAT_VOX 16  // voxels per thread of the statistics, HULL_THREADS apart
-#define HULL_SCAN_THREADS 1024
 #define HULL_CAM 16       // doubles of a staged camera
 
 // (joints.hip, stage_camera64, restated: that file's kernels are pinned to their instructions and share no header with this one)
@@ -163,19 +165,6 @@ __global__ void __launch_bounds__(HULL_THREADS) k_hull_query(QueryArgs a) {
 }
 
 // ---- statistics -------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ long long wave_sum_ll(long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ long long wave_min_ll(long long v) {
-    for (int o = 32; o > 0; o >>= 1) { const long long w = __shfl_xor(v, o, 64); v = w < v ? w : v; }
-    return v;
-}
-__device__ __forceinline__ long long wave_max_ll(long long v) {
-    for (int o = 32; o > 0; o >>= 1) { const long long w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
-    return v;
-}
-
 __global__ void k_hull_stats_init(long long *stats, int N, int Gx, int Gy, int Gz) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
@@ -216,11 +205,11 @@ __global__ void __launch_bounds__(HULL_THREADS) k_hull_stats(const unsigned char
         a[13] = li > a[13] ? li : a[13]; a[14] = lj > a[14] ? lj : a[14]; a[15] = lk > a[15] ? lk : a[15];
     }
 #pragma unroll
-    for (int c = 0; c < 10; ++c) a[c] = wave_sum_ll(a[c]);
+    for (int c = 0; c < 10; ++c) a[c] = wave_sum(a[c]);
 #pragma unroll
-    for (int c = 10; c < 13; ++c) a[c] = wave_min_ll(a[c]);
+    for (int c = 10; c < 13; ++c) a[c] = wave_min(a[c]);
 #pragma unroll
-    for (int c = 13; c < 16; ++c) a[c] = wave_max_ll(a[c]);
+    for (int c = 13; c < 16; ++c) a[c] = wave_max(a[c]);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0)
 #pragma unroll
@@ -251,16 +240,6 @@ __device__ __forceinline__ bool hull_is_surface(const unsigned char *o, long lon
     return !(xm && xp && ym && yp && zm && zp);
 }
 
-// inclusive sum over the lanes up to and including this one
-__device__ __forceinline__ long long wave_scan_ll(long long v) {
-    const int lane = threadIdx.x & 63;
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long w = __shfl_up(v, o, 64);
-        if (lane >= o) v += w;
-    }
-    return v;
-}
-
 template <bool WRITE>
 __global__ void __launch_bounds__(HULL_THREADS) k_hull_surface(const unsigned char *occ, HullGridDev g, long long *counts, float *points,
                                                                long long *index) {
@@ -276,20 +255,13 @@ __global__ void __launch_bounds__(HULL_THREADS) k_hull_surface(const unsigned ch
         flag[q] = v0 + q < g.vox && hull_is_surface(o, v0 + q, g, small);
         mine += flag[q] ? 1 : 0;
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int incl = (int)wave_scan_ll(mine);
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-    for (int w = 0; w < HULL_THREADS / 64; ++w) {
-        before += w < wave ? s_wave[w] : 0;
-        total += s_wave[w];
-    }
+    int total;
+    const int before = block_scan_exclusive<int, HULL_THREADS>(mine, s_wave, total);
     if (!WRITE) {
         if (threadIdx.x == 0) counts[blockIdx.x] = total;
         return;
     }
-    long long pos = counts[blockIdx.x] + before + incl - mine;  // (counts: the exclusive prefixes k_hull_scan left)
+    long long pos = counts[blockIdx.x] + before;  // (counts: the exclusive prefixes k_hull_scan left)
     const double *org = g.origin + 3 * (frame % g.n_origin);
     const double voxel = g.voxel[frame % g.n_voxel];
 #pragma unroll
@@ -305,31 +277,38 @@ __global__ void __launch_bounds__(HULL_THREADS) k_hull_surface(const unsigned ch
     }
 }
 
-// counts (n) -> their exclusive prefixes, in place; offsets[f] = the prefix of frame f's first block, offsets[N] = the total.  One block.
-__global__ void __launch_bounds__(HULL_SCAN_THREADS) k_hull_scan(long long *counts, long long n, long long chunks, int N, long long *offsets) {
+// The scan of hull_grid.h: workgroup blockIdx.x takes job blockIdx.x, HULL_SCAN_THREADS counts a round, the rounds before it in `carry`.
+struct HullScanArgs {  // (the sizes first: the kernel reads n before anything else, and with the first job they fill 56 bytes)
+    long long n, chunks;
+    int N;
+    HullScanJob job[2];
+};
+
+__global__ void __launch_bounds__(HULL_SCAN_THREADS) k_hull_scan(HullScanArgs a) {
     __shared__ long long s_wave[HULL_SCAN_THREADS / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const HullScanJob &j = blockIdx.x ? a.job[1] : a.job[0];
     long long carry = 0;
-    for (long long base = 0; base < n; base += HULL_SCAN_THREADS) {
+    for (long long base = 0; base < a.n; base += HULL_SCAN_THREADS) {
         const long long e = base + threadIdx.x;
-        const long long c = e < n ? counts[e] : 0;
-        const long long incl = wave_scan_ll(c);
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        long long before = 0, total = 0;
-        for (int w = 0; w < HULL_SCAN_THREADS / 64; ++w) {
-            before += w < wave ? s_wave[w] : 0;
-            total += s_wave[w];
-        }
+        long long total;
+        const long long excl = carry + block_scan_exclusive<long long, HULL_SCAN_THREADS>(e < a.n ? j.counts[e] : 0, s_wave, total);
         __syncthreads();  // (the next round rewrites s_wave)
-        const long long excl = carry + before + incl - c;
-        if (e < n) {
-            counts[e] = excl;
-            if (e % chunks == 0) offsets[e / chunks] = excl;
+        if (e < a.n) {
+            j.counts[e] = excl;
+            if (e % a.chunks == 0) j.offsets[e / a.chunks] = j.scale * excl;
         }
         carry += total;
     }
-    if (threadIdx.x == 0) offsets[N] = carry;
+    if (threadIdx.x != 0) return;
+    if (j.write_total_at_n) j.counts[a.n] = carry;
+    j.offsets[a.N] = j.scale * carry;
+}
+
+int hull_scan(const HullScanJob *jobs, int n_jobs, long long n, long long chunks, int N, hipStream_t stream) {
+    const HullScanArgs a{n, chunks, N, {jobs[0], jobs[n_jobs - 1]}};
+    hipLaunchKernelGGL(k_hull_scan, dim3((unsigned)n_jobs), dim3(HULL_SCAN_THREADS), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    return SMIL_OK;
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
@@ -410,8 +389,7 @@ extern "C" int smil_hull_stats(const SmilHullGrid *g, const uint8_t *occ, int64_
 }
 
 extern "C" size_t smil_hull_surface_workspace_bytes(const SmilHullGrid *g) {
-    if (!g || g->N < 1 || g->Gx < 1 || g->Gy < 1 || g->Gz < 1 || g->n_origin < 1 || g->n_voxel_size < 1) return 0;
-    if ((long long)g->Gx * g->Gy > HULL_MAX_VOXELS / g->Gz) return 0;
+    if (!hull_extent_ok(g) || g->n_origin < 1 || g->n_voxel_size < 1) return 0;
     return hull_layout(nullptr, g, hull_chunks((long long)g->Gx * g->Gy * g->Gz, HULL_SURF_VOX * HULL_THREADS) * g->N).bytes;
 }
 
@@ -427,9 +405,8 @@ extern "C" int smil_hull_surface_count(const SmilHullGrid *g, const uint8_t *occ
     hipLaunchKernelGGL(k_hull_surface<false>, dim3((unsigned)(d.chunks * g->N)), dim3(HULL_THREADS), 0, stream, (const unsigned char *)occ, d, w.counts,
                        (float *)nullptr, (long long *)nullptr);
     SMIL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_hull_scan, dim3(1), dim3(HULL_SCAN_THREADS), 0, stream, w.counts, d.chunks * g->N, d.chunks, g->N, (long long *)offsets);
-    SMIL_LAUNCH_CHECK();
-    return SMIL_OK;
+    const HullScanJob job{w.counts, (long long *)offsets, 1, 0};
+    return hull_scan(&job, 1, d.chunks * g->N, d.chunks, g->N, stream);
 }
 
 extern "C" int smil_hull_surface_write(const SmilHullGrid *g, const uint8_t *occ, void *workspace, float *points, int64_t *index, void *stream_) {

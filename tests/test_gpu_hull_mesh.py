@@ -135,6 +135,24 @@ def test_without_normals_and_an_empty_hull():
     assert nothing.volume().tolist() == [0.0] * 3 and nothing.verts_list()[1].shape[0] == 0
 
 
+def test_offsets_across_scan_rounds():
+    """The scan of the per-workgroup vertex and quad counts takes 1 024 counts a round (a workgroup counts 2 048 cubes).  11 frames of
+    63 x 63 x 51 voxels = 64 x 64 x 52 cubes: 104 counts a frame, 1 144 in all - frame 10 starts at count 1 040, inside the second round,
+    whose prefixes carry the first round's totals.  Occupancy built directly (``scan_occupancy``: frame 2 empty)."""
+    N, G = 11, (63, 63, 51)
+    blocks = -(-(G[0] + 1) * (G[1] + 1) * (G[2] + 1) // 2048)
+    assert N * blocks == 1144 and 10 * blocks == 1040
+    occ = VC.scan_occupancy(N, G)
+    hull = _hull(occ, *DYADIC)
+    tops = MR.topologies(occ)
+    for weights in ((), (0.5,)):
+        ref = MR.extract(occ, *DYADIC, weights, tops=tops)
+        assert ref.vert_offsets[2] == ref.vert_offsets[3] and (np.diff(ref.vert_offsets)[[0, 1, *range(3, N)]] > 100).all()
+        v, n = _check(hull.extract_mesh(weights), ref, weights)
+        print(f"weights {weights}: max error {v:.3g} ulp (vertices), {n:.3g} ulp (normals)")
+        assert max(v, n) <= MESH_ULPS
+
+
 def test_beyond_2_31_cubes():
     """N = 33 600 frames of 40^3 voxels = 41^3 cubes (2.15e9 voxels, 2.32e9 cubes; 2.2 GB of occupancy): all empty but the first, the
     last and the two around cube 2^31 and around voxel 2^31, which hold a seeded blob each and are compared with the restatement."""

@@ -176,6 +176,27 @@ def test_stats_and_sample_surface():
         assert len({r.tobytes() for r in sample[n]}) > 3
 
 
+@pytest.mark.parametrize("N, grid", [(6, (64, 64, 52)), (4, (64, 64, 64))])
+def test_surface_offsets_across_scan_rounds(N, grid):
+    """The scan of the per-workgroup surface counts takes 1 024 counts a round (a workgroup counts 1 024 voxels).  6 frames of 64 x 64 x 52:
+    208 counts a frame, 1 248 in all - frame 5 starts at count 1 040, inside the second round, whose prefixes carry the first round's
+    total.  4 frames of 64^3: exactly 1 024 counts, one full round.  Occupancy built directly (``scan_occupancy``: frame 2 empty)."""
+    from smilify_amd import engine
+    from smilify_amd import visual_hull as VH
+
+    Gx, Gy, Gz = grid
+    counts = N * -(-Gx * Gy * Gz // 1024)
+    assert counts == (1248 if N == 6 else 1024)
+    occ = VC.scan_occupancy(N, grid)
+    origin, voxel = np.array([[-1.5, 0.25, -0.75]]), np.array([0.125])
+    hull = VH.VisualHull(torch.from_numpy(occ).to(DEV), None, None, engine.HullGridSpec(N, grid, origin, voxel))
+    pts, idx, off = hull.surface_points(True)
+    r_pts, r_idx, r_off = VR.surface(occ, origin, voxel)
+    assert r_off[2] == r_off[3] and (np.diff(r_off)[[0, 1, *range(3, N)]] > 100).all()
+    assert np.array_equal(off.cpu().numpy(), r_off) and np.array_equal(idx.cpu().numpy(), r_idx)
+    assert tuple(pts.shape) == (len(r_idx), 3) and np.array_equal(_bits(pts.cpu().numpy()), _bits(r_pts))
+
+
 def test_tight_bounds_second_pass():
     """Coarse to fine: the grid of ``tight_bounds`` holds the voxel of every coarse occupied centre, is finer, and the second carve agrees
     with the restatement on it."""

@@ -161,3 +161,21 @@ def reference(name):
 def ambiguous_fraction(name):
     occ, v = reference(name)
     return 1.0 - float(v.exact.mean())
+
+
+def scan_occupancy(N, grid, seed=0):
+    """(N,Gz,Gy,Gx) uint8 built directly, for the scans of the per-workgroup counts (surface and mesh): frame 2 empty, every other frame six
+    seeded balls of radius 2 to 5 voxels, and the first and the last voxel of the frame set - the counts of a frame's first and last
+    workgroup are not zero, so a prefix that loses a round's carry shows in the very next frame."""
+    Gx, Gy, Gz = grid
+    rng = np.random.default_rng(4100 + seed)
+    k, j, i = np.meshgrid(np.arange(Gz), np.arange(Gy), np.arange(Gx), indexing="ij")
+    occ = np.zeros((N, Gz, Gy, Gx), np.uint8)
+    for n in range(N):
+        if n == 2:
+            continue
+        for _ in range(6):
+            c, r = rng.uniform(0.0, (Gx, Gy, Gz)), rng.uniform(2.0, 5.0)
+            occ[n] |= ((i - c[0]) ** 2 + (j - c[1]) ** 2 + (k - c[2]) ** 2 <= r * r).astype(np.uint8)
+        occ[n, 0, 0, 0] = occ[n, -1, -1, -1] = 1
+    return occ
