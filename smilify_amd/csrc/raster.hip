@@ -52,7 +52,8 @@
 //    select_mode(1) and the faithful queue within the documented tolerance).
 //
 // Map (one translation unit; the headers are included below in this order and by nothing else):
-//   raster_common.h  constants, RasterArgs / SetupArgs, clip tables, `at`, wave helpers, the pair arithmetic, pack_fx2
+//   raster_common.h  constants, RasterArgs / SetupArgs, clip tables, `at`, wave helpers, the pair arithmetic, pack_fx2; it includes
+//   raster_reach.h   the rounded blur box (corner-tile flags, row / column trim): plain C++, also compiled on the host by a test
 //   raster_setup.h   k_raster_setup, k_clip_backward, k_unpack_dndc
 //   raster_tile.h    DenseLds, the list phase, stage_faces, the select sweeps, k_raster_dense
 //   raster_replay.h  k_raster_tie_replay

@@ -3,6 +3,10 @@
 // kernel and k_raster_tie_replay must evaluate to the same bits.  Included by raster.hip only, behind common.h and raster_hooks.h.
 #pragma once
 
+// the rounded blur box: which tiles, rows and columns of a face's pixel box can hold a record (k_raster_setup, stage_faces)
+#define REACH_FN __host__ __device__ __forceinline__
+#include "raster_reach.h"
+
 #define DCHUNK 32           // faces staged per chunk
 #define FREC 28             // floats per staged face record
 #define FSTR 28             // its stride in LDS: 112 bytes = 28 banks, so the 16-byte rows of 16 consecutive faces start in 16 different

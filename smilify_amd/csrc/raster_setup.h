@@ -54,6 +54,14 @@ __global__ void __launch_bounds__(SETUP_THREADS, 8) k_raster_setup(SetupArgs q) 
     const bool in_regs = FP <= SETUP_REG_ROUNDS * (int)blockDim.x;
     const bool store = q.store_tables != 0 || !in_regs;
     uint32_t rbox[SETUP_REG_ROUNDS], rzn[SETUP_REG_ROUNDS];
+    // Corner tiles of a face's tile box that cannot hold a record of it (raster_reach.h) get neither a count nor an entry.  The four
+    // flags of a face are worked out ONCE, in pass 1, and ride beside its box - four bits a round in one register - to pass 2, which
+    // fills exactly the list space pass 1 counted.  Faces whose rows go through memory (the front parts of cut faces, every face of
+    // a mesh of more than SETUP_REG_ROUNDS rounds) are not culled: the tables have no room for the flags.  Nor is anything culled
+    // where the reach exceeds a tile (edge tiles could then fail too, and four flags would not say so) or the tiles are not counted.
+    static_assert(4 * SETUP_REG_ROUNDS <= 32, "four corner flags a round in one register");
+    uint32_t rcull = 0u;
+    const bool cull_ok = counted && in_regs && q.sqrt_blur * fS * 0.5f + REACH_SLACK_PX <= (float)TILE;
 #pragma unroll
     for (int r = 0; r < SETUP_REG_ROUNDS; ++r) { rbox[r] = 0x0000FFFFu; rzn[r] = 0u; }
     if (store)
@@ -62,9 +70,11 @@ __global__ void __launch_bounds__(SETUP_THREADS, 8) k_raster_setup(SetupArgs q) 
     TSETUP(1)
     float *const xv_n = q.clip.xv + (size_t)n * CLIP_VX * 3;
     int *const xf_n = q.clip.xf + (size_t)n * CLIP_FX * 3;
-    // one face (an original one or the front part of a cut one): validity, blurred pixel box -> tile box, cost / entry per tile
-    auto emit = [&](int fid, float x0, float y0, float z0, float x1, float y1, float z1, float x2, float y2, float z2, float &znear) -> uint32_t {
+    // one face (an original one or the front part of a cut one): validity, blurred pixel box -> tile box, cost / entry per tile;
+    // `carried` (a literal at every call): the face's corner flags can ride to pass 2, so its corner tiles may be culled
+    auto emit = [&](int fid, float x0, float y0, float z0, float x1, float y1, float z1, float x2, float y2, float z2, float &znear, const bool carried, uint32_t &cull) -> uint32_t {
         uint32_t box = 0x0000FFFFu;  // empty: tx0 = ty0 = 255 > tx1 = ty1 = 0
+        cull = 0u;
         const float zmin = fminf(fminf(z0, z1), z2), zmax = fmaxf(fmaxf(z0, z1), z2);
         znear = zmin;
         if (store || fid >= FP) q.fzr[(size_t)n * FT + fid] = make_float2(zmin, zmax);
@@ -73,8 +83,9 @@ __global__ void __launch_bounds__(SETUP_THREADS, 8) k_raster_setup(SetupArgs q) 
         // zmin < 1e-8: the rasteriser's own rule; zmax < z_clip: the face lies entirely nearer than MeshRasterizer's
         // z_clip_value (znear / 2) and clip_faces() removes it
         if (finite && !(zmin < K_EPS) && !(zmax < q.z_clip) && !(area <= K_EPS && area >= -K_EPS)) {
-            const float xlo = fminf(fminf(x0, x1), x2) - q.sqrt_blur, xhi = fmaxf(fmaxf(x0, x1), x2) + q.sqrt_blur;
-            const float ylo = fminf(fminf(y0, y1), y2) - q.sqrt_blur, yhi = fmaxf(fmaxf(y0, y1), y2) + q.sqrt_blur;
+            const float fx0 = fminf(fminf(x0, x1), x2), fx1 = fmaxf(fmaxf(x0, x1), x2), fy0 = fminf(fminf(y0, y1), y2), fy1 = fmaxf(fmaxf(y0, y1), y2);
+            const float xlo = fx0 - q.sqrt_blur, xhi = fx1 + q.sqrt_blur;
+            const float ylo = fy0 - q.sqrt_blur, yhi = fy1 + q.sqrt_blur;
             // pixel index i (flipped axis) has centre -1 + (2i+1)/S: centres inside [lo,hi] are ceil(v_lo)..floor(v_hi)
             // with v = ((x+1) S - 1)/2; 0.01 px of slack covers the float rounding of both sides (clamped in float first: the
             // front part of a cut face can reach far outside the image)
@@ -91,8 +102,12 @@ __global__ void __launch_bounds__(SETUP_THREADS, 8) k_raster_setup(SetupArgs q) 
                 box = (uint32_t)tx0 | ((uint32_t)ty0 << 8) | ((uint32_t)tx1 << 16) | ((uint32_t)ty1 << 24);
                 if (store || fid >= FP) q.tbox[(size_t)n * FT + fid] = box;  // (ahead of the tile loop: the address does not live through it)
                 const int xo0 = S - 1 - xi_hi, xo1 = S - 1 - xi_lo, yo0 = S - 1 - yi_hi, yo1 = S - 1 - yi_lo;
+                if (carried && cull_ok)  // (the limit worked out here: a value kept across the rounds would cost a register the kernel does not have)
+                    cull = reach_corner_flags(reach_px_of(fx0, fS), reach_px_of(fx1, fS), reach_px_of(fy0, fS), reach_px_of(fy1, fS),
+                                              xo0, xo1, yo0, yo1, tx0, tx1, ty0, ty1, S, TILE, reach_limit2(q.sqrt_blur, fS));
                 for (int ty = ty0; ty <= ty1; ++ty)
                     for (int tx = tx0; tx <= tx1; ++tx) {
+                        if (reach_corner_culled(cull, tx, ty, tx0, tx1, ty0, ty1)) continue;
                         const int t = ty * tiles_x + tx;
                         if (counted) {  // cost of this face in this tile: its (face, pixel) pairs plus a bit for staging it; one list entry
                             const int wx = min(xo1, tx * TILE + TILE - 1) - max(xo0, tx * TILE) + 1;
@@ -126,7 +141,7 @@ __global__ void __launch_bounds__(SETUP_THREADS, 8) k_raster_setup(SetupArgs q) 
     if ((int)threadIdx.x < F) { nx0 = q.faces[3 * threadIdx.x]; nx1 = q.faces[3 * threadIdx.x + 1]; nx2 = q.faces[3 * threadIdx.x + 2]; }
     for (int f0 = 0; f0 < FP; f0 += blockDim.x) {  // every wave handles 64 consecutive faces per round
         const int f = f0 + threadIdx.x;
-        uint32_t box = 0x0000FFFFu;
+        uint32_t box = 0x0000FFFFu, cull = 0u;
         float znear = 0.f;
         const int ii[3] = {nx0, nx1, nx2};
         {
@@ -155,7 +170,7 @@ __global__ void __launch_bounds__(SETUP_THREADS, 8) k_raster_setup(SetupArgs q) 
                     atomicAdd(&s_unclipped, 1u);  // beyond the tables: rendered whole, or dropped when a vertex is nearer than 1e-8 (counted)
                 }
             }
-            if (!cut) box = emit(f, X[0], Y[0], Z[0], X[1], Y[1], Z[1], X[2], Y[2], Z[2], znear);
+            if (!cut) box = emit(f, X[0], Y[0], Z[0], X[1], Y[1], Z[1], X[2], Y[2], Z[2], znear, true, cull);
         }
         if (in_regs) {  // (the round number is uniform: a select per register, no indexed access)
 #pragma unroll
@@ -163,6 +178,7 @@ __global__ void __launch_bounds__(SETUP_THREADS, 8) k_raster_setup(SetupArgs q) 
                 const bool here = f0 == r * (int)blockDim.x;
                 rbox[r] = here ? box : rbox[r];
                 rzn[r] = here ? __float_as_uint(znear) : rzn[r];
+                rcull |= here ? cull << (4 * r) : 0u;
             }
         }
         if (store) group_box(box, (f0 + (int)threadIdx.x) / WAVE);
@@ -190,6 +206,7 @@ __global__ void __launch_bounds__(SETUP_THREADS, 8) k_raster_setup(SetupArgs q) 
         const int o1 = k1, o2 = (k1 + 1) % 3, o3 = (k1 + 2) % 3;
         const uint32_t jv = 2u * c;
         float nx[2], ny[2], zn_;
+        uint32_t cull_;  // (front parts go through the tables: never culled)
         {  // the front parts' vertex ids (ahead of the arithmetic: the face's own ids do not live through it)
             const int v4 = V + (int)jv, v5 = v4 + 1;
             int *xf = xf_n + 3 * (2 * c);
@@ -207,10 +224,10 @@ __global__ void __launch_bounds__(SETUP_THREADS, 8) k_raster_setup(SetupArgs q) 
             q.clip.xcoef[(size_t)n * CLIP_VX + jv + e] = make_float2(ca, cb);
         }
         if (nb == 1) {  // quadrilateral (p4, p2, p3, p5) as (p4, p2, p3) + (p4, p3, p5)
-            emit(FP + 2 * (int)c, nx[0], ny[0], q.z_clip, X[o2], Y[o2], Z[o2], X[o3], Y[o3], Z[o3], zn_);
-            emit(FP + 2 * (int)c + 1, nx[0], ny[0], q.z_clip, X[o3], Y[o3], Z[o3], nx[1], ny[1], q.z_clip, zn_);
+            emit(FP + 2 * (int)c, nx[0], ny[0], q.z_clip, X[o2], Y[o2], Z[o2], X[o3], Y[o3], Z[o3], zn_, false, cull_);
+            emit(FP + 2 * (int)c + 1, nx[0], ny[0], q.z_clip, X[o3], Y[o3], Z[o3], nx[1], ny[1], q.z_clip, zn_, false, cull_);
         } else {        // triangle (p1, p4, p5)
-            emit(FP + 2 * (int)c, X[o1], Y[o1], Z[o1], nx[0], ny[0], q.z_clip, nx[1], ny[1], q.z_clip, zn_);
+            emit(FP + 2 * (int)c, X[o1], Y[o1], Z[o1], nx[0], ny[0], q.z_clip, nx[1], ny[1], q.z_clip, zn_, false, cull_);
             q.tbox[(size_t)n * FT + FP + 2 * (int)c + 1] = 0x0000FFFFu;  // (the cut's second slot: empty - nothing else fills the rows from FP on when the tables are not stored)
         }
     }
@@ -352,7 +369,7 @@ __global__ void __launch_bounds__(SETUP_THREADS, 8) k_raster_setup(SetupArgs q) 
     // (consecutive faces cover the same tiles: their entries take consecutive slots, so a wave's stores land in few cache lines;
     // spreading the lanes over distant faces to thin out the same-address atomics was measured slower, 601 -> 658 us)
     const int f_end = FP + 2 * (int)n_cut;  // (the rows behind the last cut face's front parts are empty)
-    auto bin_face = [&](int f, uint32_t box, uint32_t znear_bits) {
+    auto bin_face = [&](int f, uint32_t box, uint32_t znear_bits, uint32_t cull) {
         const uint2 ent = make_uint2((uint32_t)f, znear_bits);
         const int tx0 = box & 0xFF, ty0 = (box >> 8) & 0xFF, tx1 = (box >> 16) & 0xFF, ty1 = box >> 24;
         if (tx0 > tx1) return;
@@ -360,15 +377,16 @@ __global__ void __launch_bounds__(SETUP_THREADS, 8) k_raster_setup(SetupArgs q) 
         // (a fast path for boxes of at most 2 x 2 tiles - the four returning atomics issued before the four stores - measured no
         // different, profiles/r5_experiments.md)
         for (int ty = ty0; ty <= ty1; ++ty)
-            for (int tx = tx0; tx <= tx1; ++tx) at(lists, atomicAdd(&cur[ty * tiles_x + tx], 1u)) = ent;
+            for (int tx = tx0; tx <= tx1; ++tx)
+                if (!reach_corner_culled(cull, tx, ty, tx0, tx1, ty0, ty1)) at(lists, atomicAdd(&cur[ty * tiles_x + tx], 1u)) = ent;  // (pass 1's flags: its count)
     };
     if (in_regs) {
 #pragma unroll
         for (int r = 0; r < SETUP_REG_ROUNDS; ++r)
-            if (r * (int)blockDim.x < FP) bin_face(r * (int)blockDim.x + (int)threadIdx.x, rbox[r], rzn[r]);  // (rows from FP on: empty boxes)
+            if (r * (int)blockDim.x < FP) bin_face(r * (int)blockDim.x + (int)threadIdx.x, rbox[r], rzn[r], (rcull >> (4 * r)) & 15u);  // (rows from FP on: empty boxes)
     }
     for (int f = (in_regs ? FP : 0) + (int)threadIdx.x; f < f_end; f += blockDim.x)
-        bin_face(f, q.tbox[(size_t)n * FT + f], __float_as_uint(q.fzr[(size_t)n * FT + f].x));  // (one round trip: both requested together)
+        bin_face(f, q.tbox[(size_t)n * FT + f], __float_as_uint(q.fzr[(size_t)n * FT + f].x), 0u);  // (one round trip: both requested together)
     TSETUP(8)
     TSETUP_REPORT
 }

@@ -148,8 +148,9 @@ __device__ __forceinline__ void sort_list_near_to_far(const uint2 *list, uint32_
 
 // Staging of a chunk of DCHUNK = 32 faces by all 64 lanes: lanes l and l + 32 share face l.  The LOW lane builds the affine
 // forms (rows 1-3 of the record) and the pixel ROWS the face's blurred box covers inside the open part of the tile; the
-// HIGH lane the bounding box (row 0), the edge data (rows 4-7) and the pixel COLUMNS; the columns then cross over (one
-// ds_bpermute each) and the low lane leaves with the face's pair count `cf` and the word pairs decode their pixel from.
+// HIGH lane the bounding box (row 0), the edge data (rows 4-7) and the pixel COLUMNS; rows and columns are cut to what the blur
+// disc of the face's bounding box reaches (the lanes swap their gaps: one ds_bpermute), the columns then cross over (one more,
+// both ends in one word) and the low lane leaves with the face's pair count `cf` and the word pairs decode their pixel from.
 // Both lanes load the same nine vertex floats (one transaction); the face's vertex indices (i0, i1, i2) come from the
 // caller, which fetched them while the previous chunk was being evaluated.  Pixel index i (flipped axis) has centre -1 + (2i+1)/S:
 // centres inside [lo, hi] are ceil(v_lo) .. floor(v_hi) with v = ((x+1) S - 1)/2; 0.01 px of slack covers the float rounding
@@ -162,6 +163,7 @@ __device__ __forceinline__ void stage_faces(const RasterArgs &a, const Tri9 &tv,
     const int slot = lane & (DCHUNK - 1);
     const bool hi = lane >= DCHUNK;
     int b0 = 0, b1 = -1;  // low lane: box rows by0 .. by1; high lane: box columns bx0 .. bx1
+    float c_lo = 0.f, c_hi = 0.f;  // the face's unblurred extent on the lane's axis (NDC)
     if (slot < m) {
         const float x0 = tv.x0, y0 = tv.y0, x1 = tv.x1, y1 = tv.y1, x2 = tv.x2, y2 = tv.y2;
         float4 *r = reinterpret_cast<float4 *>(rec + slot * FSTR);
@@ -176,6 +178,7 @@ __device__ __forceinline__ void stage_faces(const RasterArgs &a, const Tri9 &tv,
             const int yi_lo = (int)ceilf(((ymin + 1.0f) * fS - 1.0f) * 0.5f - 0.01f), yi_hi = (int)floorf(((ymax + 1.0f) * fS - 1.0f) * 0.5f + 0.01f);
             b0 = max(a.S - 1 - yi_hi - ty * TILE, oy0);
             b1 = min(a.S - 1 - yi_lo - ty * TILE, oy1);
+            c_lo = fminf(fminf(y0, y1), y2); c_hi = fmaxf(fmaxf(y0, y1), y2);
         } else {
             const float xmin = fminf(fminf(x0, x1), x2) - a.sqrt_blur, xmax = fmaxf(fmaxf(x0, x1), x2) + a.sqrt_blur;
             float rl12;
@@ -185,9 +188,30 @@ __device__ __forceinline__ void stage_faces(const RasterArgs &a, const Tri9 &tv,
             const int xi_lo = (int)ceilf(((xmin + 1.0f) * fS - 1.0f) * 0.5f - 0.01f), xi_hi = (int)floorf(((xmax + 1.0f) * fS - 1.0f) * 0.5f + 0.01f);
             b0 = max(a.S - 1 - xi_hi - tx * TILE, ox0);
             b1 = min(a.S - 1 - xi_lo - tx * TILE, ox1);
+            c_lo = fminf(fminf(x0, x1), x2); c_hi = fmaxf(fmaxf(x0, x1), x2);
         }
     }
-    int bx0 = __shfl(b0, slot + DCHUNK, WAVE), bx1 = __shfl(b1, slot + DCHUNK, WAVE);  // (all lanes: no divergent ds_bpermute)
+    // The rectangle above is the blurred SQUARE cut to the tile and its open pixels; a record needs dx^2 + dy^2 < blur (raster_reach.h).
+    // Each lane works out how far its run of rows / columns stays from the face's extent on its axis, the two lanes of a face swap
+    // these gaps, and each cuts its run to what the other's gap leaves of the reach: the rounded box.  (Both lanes run the same
+    // code on their own axis; one round - a run cut here could shorten the other's again, which was not worth a second exchange.)
+    {
+        const int edge = a.S - 1 - (hi ? tx : ty) * TILE;  // pixel index (flipped axis) of the tile's first row / column
+        const bool any = b0 <= b1;
+        const float vlo = reach_px_of(c_lo, fS), vhi = reach_px_of(c_hi, fS);
+        const float gap = any ? reach_gap(vlo, vhi, edge - b1, edge - b0) : 0.f;
+        const float gap_other = __shfl(gap, lane ^ DCHUNK, WAVE);  // (all lanes: no divergent ds_bpermute)
+        if (any) {
+            int i_lo = edge - b1, i_hi = edge - b0;
+            float sb = a.sqrt_blur;
+            asm volatile("" : "+v"(sb));  // (the limit is worked out per chunk, three instructions, and not kept in a register across the chunks)
+            reach_trim(vlo, vhi, gap_other, reach_limit2(sb, fS), i_lo, i_hi);
+            b0 = edge - i_hi;
+            b1 = edge - i_lo;
+        }
+    }
+    const int bxx = __shfl(b0 <= b1 ? (b0 | (b1 << 4)) : 1, slot + DCHUNK, WAVE);  // the columns cross over: bx0 | bx1 << 4 (empty: 1 | 0)
+    int bx0 = bxx & 15, bx1 = bxx >> 4;
     cf = 0;
     packed2 = 0;
     if (!hi && slot < m && bx0 <= bx1 && b0 <= b1) {
