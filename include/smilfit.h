@@ -53,7 +53,8 @@ int smil_model_create(const SmilModelDesc *desc, SmilModel **out);
 void smil_model_destroy(SmilModel *m);
 int smil_model_dims(const SmilModel *m, int32_t dims[4]); /* V,F,J,nB */
 const char *smil_last_error(void);
-const char *smil_version(void);   /* "smilfit 0.11 (gfx950; 0.3 + SmilCameras.principal (0.4) + fragments, depth visibility (0.5) + mesh-free joints, kp3d fit (0.6) + kp2d fit (0.7) + visual hull (0.8) + distance fields (0.9) + hull meshes + point-mesh distances)".  0.11 adds
+const char *smil_version(void);   /* "smilfit 0.12 (gfx950; 0.3 + SmilCameras.principal (0.4) + fragments, depth visibility (0.5) + mesh-free joints, kp3d fit (0.6) + kp2d fit (0.7) + visual hull (0.8) + distance fields (0.9) + hull meshes (0.10) + point-mesh distances (0.11) + winding numbers)".  0.12 adds
+                                    * smil_point_mesh_winding and changes no layout.  0.11 adds
                                     * smil_point_face_distance / smil_face_point_distance / smil_point_mesh_backward and their
                                     * workspace query and changes no layout.  0.10 adds
                                     * the smil_hull_mesh_* entry points and changes no layout.  0.9 adds
@@ -1211,7 +1212,7 @@ int smil_hull_mesh_write(const SmilHullGrid *g, const uint8_t *occ, void *worksp
  * face_off, max_faces (and vert_off, max_verts) are the caller's statement about the meshes and are trusted: they size the launches,
  * and a max_faces / max_verts below a mesh's true count leaves that mesh's last rows of the outputs unwritten, without an error.
  * splits: over how many workgroups the candidates of one query are divided, 0 = chosen from the sizes.
- * workspace: smil_point_mesh_workspace_bytes(N, F_total, P, n_verts) bytes (0: bad sizes), one layout for the three calls.
+ * workspace: smil_point_mesh_workspace_bytes(N, F_total, P, n_verts) bytes (0: bad sizes), one layout for the four calls.
  *
  * smil_point_face_distance: for every point the nearest face of its mesh: dist2 (N,P), face (N,P) int32 within the mesh, bary (N,P,3)
  * of the closest point (b >= 0, sum 1).  A non-finite point, a point at or beyond its cloud's length and a mesh in which no face
@@ -1226,6 +1227,19 @@ int smil_hull_mesh_write(const SmilHullGrid *g, const uint8_t *occ, void *worksp
  * written in full.  vert_off (N+1) int32: the first vertex of every mesh; max_verts: the most vertices of one mesh.  Shared sums
  * are int64 fixed point with a unit that follows the mesh's largest addend: scaling every input by a power of two scales the
  * gradients exactly, and a permutation of the points leaves d_verts bit-identical.
+ *
+ * smil_point_mesh_winding: the generalised winding number winding (N,P) of every point with respect to its mesh: the sum over ALL
+ * faces of the signed solid angle Omega / (4 pi) the face subtends at the point.  1 inside a closed mesh whose faces are oriented
+ * outwards, 0 outside, -1 inside one oriented inwards, k inside k nested shells; on a mesh with holes or self-intersections a
+ * smooth function that stays near those integers away from the defects (tests/winding_ref.py restates the rules).  Per pair, in
+ * float32 in the mesh's power-of-two frame, with a = v0 - p, b = a + e1, c = a + e2 (e1 = v1 - v0, e2 = v2 - v0):
+ *   det = a . (e1 x e2),  den = |a||b||c| + (a.b)|c| + (a.c)|b| + (b.c)|a|,  Omega / 2 = atan2(det, den).
+ * A pair with det == 0 (either sign of zero) adds exactly 0: a degenerate face, a point in a face's plane, a point on a vertex; the
+ * result never hangs on the sign of a zero.  A face that is not usable (above) adds 0.  A point with an unusable coordinate, or at
+ * or beyond its cloud's length, gets NaN.  A mesh without faces gives 0.  Every pair's Omega / (4 pi) (|.| <= 0.5) is converted to
+ * int64 fixed point with the unit 2^-(61 - bits(F_n)) and summed as an integer, the splits merged with integer atomics and the sum
+ * converted once to float32: two calls, every `splits`, every order of the faces and a scaling of all inputs by a power of two
+ * give the same bits.  Errors as smil_point_face_distance.
  * ---------------------------------------------------------------------------------------- */
 size_t smil_point_mesh_workspace_bytes(int32_t N, int32_t F_total, int32_t P, int32_t n_verts);
 int smil_point_face_distance(const float *verts, int32_t n_verts, const int32_t *faces, const int32_t *face_off, int32_t N,
@@ -1238,6 +1252,9 @@ int smil_point_mesh_backward(const float *verts, int32_t n_verts, const int32_t 
                              int32_t N, int32_t F_total, int32_t max_faces, int32_t max_verts, const float *points, int32_t P,
                              const int32_t *lengths, int32_t by_face, const int32_t *idx, const float *g, float *d_points,
                              float *d_verts, void *workspace, void *stream);
+int smil_point_mesh_winding(const float *verts, int32_t n_verts, const int32_t *faces, const int32_t *face_off, int32_t N,
+                            int32_t F_total, int32_t max_faces, const float *points, int32_t P, const int32_t *lengths, int32_t splits,
+                            float *winding /* (N,P) */, void *workspace, void *stream);
 
 #ifdef __cplusplus
 }

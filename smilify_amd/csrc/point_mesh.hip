@@ -19,6 +19,13 @@
 //                   and a tie goes to the smaller face index, as one sequential scan gives (k_chamfer_nn's merge, mesh3d.hip).
 //  * k_pm_faces     faces -> points: the same device function with the roles swapped.  lane = one face (its table entry in registers),
 //                   the cloud's points stream through LDS in the frame, the point range may be split, the same merge.
+//  * k_pm_winding   the generalised winding number of every point (Jacobson et al. 2013): the sum over ALL faces of the signed solid
+//                   angle Omega_f / (4 pi), by van Oosterom & Strackee's formula in float32 in the frame.  The loop of k_pm_points:
+//                   lane = point, face tiles broadcast from LDS.  A pair whose det is +-0 adds exactly 0 (a degenerate face, a point
+//                   in the face's plane or on a vertex).  Every pair's value (|.| <= 0.5) goes to int64 fixed point whose unit follows
+//                   the mesh's face count and is added as an integer, in the lane and, when the faces are split, with one 64-bit
+//                   atomicAdd per point and split: two calls, every split count and every order of the faces give the same bits.
+//                   k_pm_winding_finish converts once to float32; a padded or unusable point gets NaN.
 //  * k_pm_finish    thread per query (point or face): the winner's closest point once more in float64 from the float32 inputs (the
 //                   float32 search decides WHICH, the value is the float64 formula's, rounded once), the barycentrics and the index.
 //                   No winner (a non-finite or padded point, a mesh without a face that can win, an empty cloud): +inf, -1, 0.
@@ -53,7 +60,8 @@ struct PmArgs {
     float *bary;              // (N, P, 3) or (F_total, 3)
     const float *g;           // upstream gradient per record
     long long *acc_v;         // (n_verts, 3)
-    long long *acc_p;         // (N, P, 3)
+    long long *acc_p;         // (N, P, 3); the winding numbers' integer sums are its first (N, P)
+    float *winding;           // (N, P)
     unsigned int *dmax;       // (N) bits of the largest |2 g e| component of mesh n's records
     float *d_points;          // (N, P, 3)
     float *d_verts;           // (n_verts, 3)
@@ -119,10 +127,11 @@ __global__ void __launch_bounds__(256) k_pm_table(PmArgs a) {
             finite &= fabsf(x) <= 3.0e38f;
             c[k] = ldexpf(x, sh);
         }
-        if (finite) {
-            v0 = make_float4(c[0], c[1], c[2], 0.f);
-            e1 = make_float4(c[3] - c[0], c[4] - c[1], c[5] - c[2], 0.f);
-            e2 = make_float4(c[6] - c[0], c[7] - c[1], c[8] - c[2], 0.f);
+        if (finite) {  // (the .w slots: n = e1 x e2 for k_pm_winding; the distance kernels do not read them)
+            const float ux = c[3] - c[0], uy = c[4] - c[1], uz = c[5] - c[2], vx = c[6] - c[0], vy = c[7] - c[1], vz = c[8] - c[2];
+            v0 = make_float4(c[0], c[1], c[2], uy * vz - uz * vy);
+            e1 = make_float4(ux, uy, uz, uz * vx - ux * vz);
+            e2 = make_float4(vx, vy, vz, ux * vy - uy * vx);
         }
     }
     a.table[3 * j] = v0;
@@ -265,6 +274,61 @@ __global__ void __launch_bounds__(256) k_pm_finish(PmArgs a) {
     a.bary[3 * at + 2] = none ? 0.f : (float)r.w;
 }
 
+// ---- winding numbers ------------------------------------------------------------------------------------------------------------
+// Omega / (4 pi) of one face seen from p, everything in the frame: with a = v0 - p, b = a + e1, c = a + e2,
+// tan(Omega / 2) = a . (e1 x e2) / (|a||b||c| + (a.b)|c| + (a.c)|b| + (b.c)|a|) (van Oosterom & Strackee 1983).  Positive when the
+// face's normal e1 x e2 points away from p.  det == +-0 (and a NaN: an unusable face or point): exactly 0, so nothing hangs on the
+// sign of a zero.
+__device__ __forceinline__ float pm_face_angle(float px, float py, float pz, const float4 &v0, const float4 &e1, const float4 &e2) {
+    const float ax = v0.x - px, ay = v0.y - py, az = v0.z - pz;
+    const float bx = ax + e1.x, by = ay + e1.y, bz = az + e1.z;
+    const float cx = ax + e2.x, cy = ay + e2.y, cz = az + e2.z;
+    const float det = ax * v0.w + ay * e1.w + az * e2.w;
+    const float la = sqrtf(ax * ax + ay * ay + az * az), lb = sqrtf(bx * bx + by * by + bz * bz), lc = sqrtf(cx * cx + cy * cy + cz * cz);
+    const float ab = ax * bx + ay * by + az * bz, ac = ax * cx + ay * cy + az * cz, bc = bx * cx + by * cy + bz * cz;
+    const float den = la * lb * lc + ab * lc + ac * lb + bc * la;
+    return fabsf(det) > 0.f ? atan2f(det, den) * 0.15915494309189535f : 0.f;  // 1 / (2 pi)
+}
+
+// Unit exponent of mesh n's winding sums: |addend| <= 0.5 < 2^0, one addend per face.
+__device__ __forceinline__ int pm_winding_fix(const PmMesh &m) { return fix_unit_exp(0, max(m.F, 1)); }
+
+__global__ void __launch_bounds__(PM_BLOCK) k_pm_winding(PmArgs a) {
+    __shared__ float4 tile[3 * PM_TILE];
+    const int n = blockIdx.z;
+    const PmMesh m = pm_mesh(a, n);
+    const int q = blockIdx.x * PM_BLOCK + threadIdx.x;
+    if ((int)(blockIdx.x * PM_BLOCK) >= m.len) return;  // (block-uniform, as the next)
+    int f_begin, f_end;
+    pm_split_range(a, m.F, f_begin, f_end);
+    if (f_begin >= f_end) return;
+    const int sh = pm_frame(a, n), fix = pm_winding_fix(m);
+    const float *Q = a.points + (size_t)n * a.P * 3;
+    float px, py, pz;  // (a lane behind the cloud's end repeats its last point and writes nothing)
+    pm_load_point(Q + 3 * (size_t)min(q, m.len - 1), sh, px, py, pz);
+    long long sum = 0;
+    const float4 *table = a.table + 3 * (size_t)m.f0;
+    for (int f0 = f_begin; f0 < f_end; f0 += PM_TILE) {
+        const int cnt = min(PM_TILE, f_end - f0);
+        __syncthreads();
+        for (int i = threadIdx.x; i < 3 * cnt; i += PM_BLOCK) tile[i] = table[3 * (size_t)f0 + i];
+        __syncthreads();
+        for (int j = 0; j < cnt; ++j)
+            sum += __double2ll_rn(ldexp((double)pm_face_angle(px, py, pz, tile[3 * j], tile[3 * j + 1], tile[3 * j + 2]), fix));
+    }
+    if (q < m.len) atomicAdd((unsigned long long *)&a.acc_p[(size_t)n * a.P + q], (unsigned long long)sum);
+}
+
+__global__ void __launch_bounds__(256) k_pm_winding_finish(PmArgs a) {
+    const int n = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= a.P) return;
+    const PmMesh m = pm_mesh(a, n);
+    const size_t at = (size_t)n * a.P + t;
+    const float *p = a.points + 3 * at;
+    const bool usable = t < m.len && fabsf(p[0]) <= 3.0e38f && fabsf(p[1]) <= 3.0e38f && fabsf(p[2]) <= 3.0e38f;
+    a.winding[at] = usable ? fix_read(a.acc_p[at], pm_winding_fix(m)) : __builtin_nanf("");
+}
+
 // ---- backward -----------------------------------------------------------------------------------------------------------------
 // record t of mesh n: the pair, its barycentrics and the point's gradient 2 g e (float64); false: the record contributes nothing
 __device__ __forceinline__ bool pm_record(const PmArgs &a, int n, const PmMesh &m, int t, size_t &at, int &point, double (&b)[3], double (&ge)[3],
@@ -379,14 +443,19 @@ static int pm_fill(PmArgs &a, const char *who, const float *verts, int32_t n_ver
     return SMIL_OK;
 }
 
+// splits of `cols` candidates for `qblocks` workgroups of queries per mesh: the caller's, or enough workgroups for the whole GPU
+// (>= 2048) while every split still streams >= 2 tiles
+static int pm_splits(int32_t splits, int qblocks, int cols, int N) {
+    const int max_split = std::max(1, cols / (2 * PM_TILE));
+    return splits > 0 ? splits : std::max(1, std::min(std::min(max_split, 65535), ceil_div(2048, qblocks * N)));
+}
+
 // the forward of either direction: `rows` queries and `cols` candidates per mesh at most
 static int pm_forward(PmArgs &a, int max_faces, int32_t splits, hipStream_t stream) {
     const int rows = a.by_face ? max_faces : a.P, cols = a.by_face ? a.P : max_faces;
     const size_t n_keys = a.by_face ? (size_t)a.F_total : (size_t)a.N * a.P;
     const int qblocks = ceil_div(rows, PM_BLOCK);
-    // splits: enough workgroups for the whole GPU (>= 2048) while every split still streams >= 2 tiles
-    const int max_split = std::max(1, cols / (2 * PM_TILE));
-    a.splits = splits > 0 ? splits : std::max(1, std::min(std::min(max_split, 65535), ceil_div(2048, qblocks * a.N)));
+    a.splits = pm_splits(splits, qblocks, cols, a.N);
     SMIL_HIP(hipMemsetAsync(a.key, 0xFF, n_keys * sizeof(unsigned long long), stream));
     SMIL_HIP(hipMemsetAsync(a.ext, 0, (size_t)a.N * sizeof(unsigned int), stream));
     hipLaunchKernelGGL(k_pm_extent, dim3(ceil_div(std::max(max_faces, a.P), 256), a.N), dim3(256), 0, stream, a);
@@ -424,6 +493,31 @@ extern "C" int smil_face_point_distance(const float *verts, int32_t n_verts, con
     SMIL_REQUIRE(splits >= 0 && splits <= 65535, "smil_face_point_distance: splits=%d outside 0 .. 65535", splits);
     a.dist2 = dist2; a.idx = (int *)point; a.bary = bary; a.by_face = 1;
     return pm_forward(a, max_faces, splits, (hipStream_t)stream);
+}
+
+extern "C" int smil_point_mesh_winding(const float *verts, int32_t n_verts, const int32_t *faces, const int32_t *face_off, int32_t N,
+                                       int32_t F_total, int32_t max_faces, const float *points, int32_t P, const int32_t *lengths,
+                                       int32_t splits, float *winding, void *workspace, void *stream_) {
+    PmArgs a;
+    const int rc = pm_fill(a, "smil_point_mesh_winding", verts, n_verts, faces, face_off, N, F_total, max_faces, points, P, lengths, workspace);
+    if (rc != SMIL_OK) return rc;
+    SMIL_REQUIRE(winding, "smil_point_mesh_winding: null output");
+    SMIL_REQUIRE(splits >= 0 && splits <= 65535, "smil_point_mesh_winding: splits=%d outside 0 .. 65535", splits);
+    hipStream_t stream = (hipStream_t)stream_;
+    a.winding = winding;
+    const int qblocks = ceil_div(P, PM_BLOCK);
+    a.splits = pm_splits(splits, qblocks, max_faces, N);
+    SMIL_HIP(hipMemsetAsync(a.ext, 0, (size_t)N * sizeof(unsigned int), stream));
+    SMIL_HIP(hipMemsetAsync(a.acc_p, 0, (size_t)N * P * sizeof(long long), stream));
+    hipLaunchKernelGGL(k_pm_extent, dim3(ceil_div(std::max(max_faces, P), 256), N), dim3(256), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_pm_table, dim3(ceil_div(max_faces, 256), N), dim3(256), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_pm_winding, dim3(qblocks, a.splits, N), dim3(PM_BLOCK), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_pm_winding_finish, dim3(ceil_div(P, 256), N), dim3(256), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    return SMIL_OK;
 }
 
 extern "C" int smil_point_mesh_backward(const float *verts, int32_t n_verts, const int32_t *faces, const int32_t *face_off,

@@ -1027,6 +1027,18 @@ def point_mesh_backward(verts: torch.Tensor, mt: MeshTables, points: torch.Tenso
     return d_points, d_verts
 
 
+def point_mesh_winding(verts: torch.Tensor, mt: MeshTables, points: torch.Tensor, lengths: Optional[torch.Tensor] = None,
+                       splits: int = 0) -> torch.Tensor:
+    """The generalised winding number (N,P) float32 of every point of points (N,P,3) with respect to its mesh: the sum of the faces'
+    signed solid angles / (4 pi) (smil_point_mesh_winding).  NaN for a point at or beyond its cloud's length or with an unusable
+    coordinate.  ``splits``: 0 = automatic; every value gives the same bits.  No host synchronisation."""
+    lib, verts, points, lengths, ws = _point_mesh_inputs("point_mesh_winding", verts, mt, points, lengths)
+    winding = torch.empty((mt.n_meshes, int(points.shape[1])), device=verts.device, dtype=torch.float32)
+    lib.smil_point_mesh_winding(_ptr(verts), mt.n_verts, _ptr(mt.faces), _ptr(mt.face_off), mt.n_meshes, mt.n_faces, mt.max_faces, _ptr(points),
+                                int(points.shape[1]), _ptr(lengths), int(splits), _ptr(winding), _ptr(ws), _stream())
+    return winding
+
+
 # ---- PointNet++ set-abstraction operations (pointnet2.hip) ---------------------------------------------------------------------
 def _check_cloud(what: str, name: str, t: torch.Tensor, B: Optional[int] = None, last: Optional[int] = 3) -> None:
     if not (isinstance(t, torch.Tensor) and t.dim() == 3 and t.dtype == torch.float32 and (last is None or t.shape[2] == last)

@@ -366,6 +366,80 @@ def _masked_mean(dist2: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return torch.where(idx >= 0, dist2, torch.zeros_like(dist2)).mean()
 
 
+# ---- signed distances and containment (the winding numbers of csrc/point_mesh.hip decide the side) -------------------------------
+def _inside(meshes: Meshes, points: torch.Tensor, lengths, oriented: bool) -> torch.Tensor:
+    """(N,P) bool from the winding numbers (``mesh3d.contains``); a constant of every backward."""
+    w = engine.point_mesh_winding(_gpu_f32(meshes.verts_packed()), meshes.face_tables(), _gpu_f32(points), lengths)
+    return (w if oriented else w.abs()) > 0.5
+
+
+class _SignedDistanceFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, verts_packed, points, mt, lengths, inside):
+        v, p = _gpu_f32(verts_packed), _gpu_f32(points)
+        dist2, idx, _ = engine.point_mesh_distance(v, mt, p, lengths, False)
+        sign = torch.where(inside, -torch.ones_like(dist2), torch.ones_like(dist2))
+        ctx.save_for_backward(v, p, idx, dist2, sign)
+        ctx.call = (mt, lengths)
+        idx = idx.long()
+        ctx.mark_non_differentiable(idx)
+        return sign * dist2.sqrt(), idx
+
+    @staticmethod
+    def backward(ctx, g, _):
+        v, p, idx, dist2, sign = ctx.saved_tensors
+        mt, lengths = ctx.call
+        live = (dist2 > 0) & (idx >= 0)  # d sqrt(d2) = d d2 / (2 sqrt(d2)); on the surface and without a face: exactly 0
+        up = torch.where(live, g.to(torch.float32) * sign / (2.0 * torch.where(live, dist2, torch.ones_like(dist2)).sqrt()),
+                         torch.zeros_like(dist2))
+        d_points, d_verts = engine.point_mesh_backward(v, mt, p, lengths, idx, up.contiguous(), False)
+        return d_verts, d_points, None, None, None
+
+
+def _check_cloud_batch(meshes: Meshes, points) -> None:
+    if not (isinstance(points, torch.Tensor) and points.dim() == 3 and points.shape[2] == 3 and points.shape[0] == len(meshes)):
+        raise ValueError(f"points ({len(meshes)},P,3) for {len(meshes)} meshes")
+    engine.require_gpu(meshes.device)
+
+
+def point_mesh_signed_distance(meshes: Meshes, points: torch.Tensor, lengths: Optional[torch.Tensor] = None, oriented: bool = True):
+    """(sdist (N,P), face (N,P) int64): the Euclidean distance of every point to the surface of its mesh, negative inside, and the
+    nearest face.  Inside: the generalised winding number is > 0.5 (``oriented=False``: its magnitude, for scans with inward faces);
+    see ``mesh3d.winding_number`` for what that means on open or self-intersecting meshes.  Differentiable in the points and in the
+    meshes' vertices: the gradient of ``sign * sqrt(dist2)`` at the recorded face, the sign a constant; exactly 0 for a point on the
+    surface (dist2 == 0) and where there is no face (+inf, -1)."""
+    _check_cloud_batch(meshes, points)
+    return _SignedDistanceFn.apply(meshes.verts_packed(), points, meshes.face_tables(), lengths, _inside(meshes, points, lengths, oriented))
+
+
+def _one_sided_loss(meshes: Meshes, points, lengths, weights, oriented: bool, want_inside: bool) -> torch.Tensor:
+    _check_cloud_batch(meshes, points)
+    N, P = len(meshes), int(points.shape[1])
+    dist2, face = point_face_distance(meshes, points, lengths)
+    inside = _inside(meshes, points, lengths, oriented)
+    counted = (face >= 0) & (inside if want_inside else ~inside)
+    valid = torch.ones(N, P, dtype=torch.bool, device=dist2.device) if lengths is None else \
+        torch.arange(P, device=dist2.device)[None] < lengths.to(dist2.device)[:, None]
+    w = valid.to(dist2.dtype) if weights is None else torch.as_tensor(weights, dtype=dist2.dtype, device=dist2.device) * valid
+    norm = w.sum(1)
+    norm = torch.where(norm > 0, norm, torch.ones_like(norm))
+    return ((w * torch.where(counted, dist2, torch.zeros_like(dist2))).sum(1) / norm).sum() / N  # (the masked side: upstream 0)
+
+
+def containment_loss(meshes: Meshes, points: torch.Tensor, lengths: Optional[torch.Tensor] = None, weights=None, oriented: bool = True):
+    """Pulls points INTO their meshes: per cloud the mean over its valid points (``weights`` (N,P): the weighted mean, sum(w x) /
+    sum(w)) of the squared distance to the surface where the point is outside and 0 where it is inside, averaged over the batch.  The
+    mesh counterpart of ``HullDistanceField.containment_loss``, at the mesh's own resolution.  C1 at the surface (no square root);
+    inside points, points without a face and points beyond ``lengths`` receive exactly no gradient."""
+    return _one_sided_loss(meshes, points, lengths, weights, oriented, False)
+
+
+def penetration_loss(meshes: Meshes, points: torch.Tensor, lengths: Optional[torch.Tensor] = None, weights=None, oriented: bool = True):
+    """Pushes points OUT of their meshes: ``containment_loss`` with the roles swapped - the squared distance to the surface where the
+    point is inside, 0 where it is outside."""
+    return _one_sided_loss(meshes, points, lengths, weights, oriented, True)
+
+
 # ---- model ----------------------------------------------------------------------------------------------------------------------
 def get_meshes(verts, faces, device="cuda"):
     return Meshes(verts=verts, faces=faces).to(device)
@@ -454,7 +528,9 @@ class Stage:
     """trainer.py:294-509: one optimisation stage (Adam over a scheme's parameters, chamfer to 3000 fresh target samples per
     iteration plus the mesh regularisers, and the SDF-guided term when ``w_sdf`` > 0 and both value sets are given).  An extension:
     ``loss_weights["w_surface"]`` > 0 (absent from ``default_weights``: off) adds ``comps["surface"]``, the mean exact squared distance
-    of the iteration's target samples to the source surface plus that of the source vertices to the target surfaces."""
+    of the iteration's target samples to the source surface plus that of the source vertices to the target surfaces;
+    ``loss_weights["w_contain"]`` > 0 (absent as well) adds ``comps["contain"]``, ``containment_loss`` of the source vertices in the
+    target meshes - meant for hull meshes as targets."""
 
     def __init__(self, nits: int, scheme: str, smal_3d_fitter: SMAL3DFitter, target_meshes: Meshes, mesh_names=(), name="optimise",
                  loss_weights=None, lr=1e-3, out_dir="static_fits_output", custom_lrs=None, device="cuda", plot_normals=False,
@@ -520,6 +596,10 @@ class Stage:
             to_target = _masked_mean(*point_face_distance(self.target_meshes, src_mesh.verts_padded()))  # ... through the points
             comps["surface"] = to_source + to_target
             loss = loss + w_surface * comps["surface"]
+        w_contain = self.loss_weights.get("w_contain", 0)
+        if w_contain > 0:  # an extension: the source vertices must lie inside the targets (hull meshes: a posed model inside its hull)
+            comps["contain"] = containment_loss(self.target_meshes, src_mesh.verts_padded())
+            loss = loss + w_contain * comps["contain"]
         return loss, comps
 
     def step(self, epoch):
@@ -655,6 +735,9 @@ def build_parser():
                    help="directory of NAME_sdf.npz / NAME_sdf.pkl files (vertex_sdf) for the source model and the target meshes")
     p.add_argument("--w_surface", type=float, default=0.0,
                    help="weight of the exact point-to-surface term of every stage (an extension; 0: off, nothing changes)")
+    p.add_argument("--w_contain", type=float, default=0.0,
+                   help="weight of the containment term of every stage: the model's vertices inside the target meshes, for hull meshes "
+                        "as targets (an extension; 0: off, nothing changes)")
     return p
 
 
@@ -702,7 +785,7 @@ def main(args):
             tv = check_and_load_sdf_values(names, args.sdf_dir, args.device)
             if all(v is not None for v in tv):  # (the reference hands over the list as it is and fails on a None inside)
                 kw.update(sdf_values=tv, source_sdf_values=source_sdf_values)
-        surface = dict(w_surface=float(args.w_surface)) if getattr(args, "w_surface", 0) > 0 else None
+        surface = {k: float(getattr(args, k)) for k in ("w_surface", "w_contain") if getattr(args, k, 0) > 0} or None
         if stage_options is not None:
             for stage_name, skw in stage_options.items():
                 if surface is not None:  # under the stage's own weights
