@@ -53,7 +53,8 @@ int smil_model_create(const SmilModelDesc *desc, SmilModel **out);
 void smil_model_destroy(SmilModel *m);
 int smil_model_dims(const SmilModel *m, int32_t dims[4]); /* V,F,J,nB */
 const char *smil_last_error(void);
-const char *smil_version(void);   /* "smilfit 0.12 (gfx950; 0.3 + SmilCameras.principal (0.4) + fragments, depth visibility (0.5) + mesh-free joints, kp3d fit (0.6) + kp2d fit (0.7) + visual hull (0.8) + distance fields (0.9) + hull meshes (0.10) + point-mesh distances (0.11) + winding numbers)".  0.12 adds
+const char *smil_version(void);   /* "smilfit 0.13 (gfx950; 0.3 + SmilCameras.principal (0.4) + fragments, depth visibility (0.5) + mesh-free joints, kp3d fit (0.6) + kp2d fit (0.7) + visual hull (0.8) + distance fields (0.9) + hull meshes (0.10) + point-mesh distances (0.11) + winding numbers (0.12) + mesh BVH)".  0.13 adds
+                                    * the smil_bvh_* entry points and changes no layout.  0.12 adds
                                     * smil_point_mesh_winding and changes no layout.  0.11 adds
                                     * smil_point_face_distance / smil_face_point_distance / smil_point_mesh_backward and their
                                     * workspace query and changes no layout.  0.10 adds
@@ -1255,6 +1256,55 @@ int smil_point_mesh_backward(const float *verts, int32_t n_verts, const int32_t 
 int smil_point_mesh_winding(const float *verts, int32_t n_verts, const int32_t *faces, const int32_t *face_off, int32_t N,
                             int32_t F_total, int32_t max_faces, const float *points, int32_t P, const int32_t *lengths, int32_t splits,
                             float *winding /* (N,P) */, void *workspace, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * A bounding-volume hierarchy over the faces of packed meshes (smilify_amd/csrc/mesh_bvh.hip): the answers of
+ * smil_point_face_distance - the same winner, bit for bit, the same float64 finish, the same outputs and rules for padded or
+ * non-finite points and for meshes without a usable face - without the scan over all faces.  An extension.  Built once for meshes
+ * that do not change, refitted when only their vertices move.  tests/mesh_bvh_ref.py restates the rules.
+ *
+ * The tree of mesh n is implicit: its faces stand in Morton order of their centroids (order (F_total) int32: sorted position ->
+ * face within the mesh, the positions of mesh n at face_off[n] ..), SMIL_BVH_LEAF consecutive sorted faces are a leaf, the
+ * L = ceil(F_n / SMIL_BVH_LEAF) leaves are padded to Lp, the next power of two (>= 1), and the nodes are numbered as a heap: root 1,
+ * children of i: 2 i and 2 i + 1, leaf k: Lp + k.  Node i of mesh n is row 4 (face_off[n] / SMIL_BVH_LEAF + n) + i of boxes
+ * (smil_bvh_nodes(N, F_total) rows of 6 floats: lo xyz, hi xyz; 0: bad sizes).  A box is the exact float32 minimum and maximum of
+ * the vertices of the usable faces below it (usable as in the block above: indices inside [0, n_verts), finite coordinates); with
+ * none it is empty (lo = +inf, hi = -inf) and never entered.  No pointers, no atomics in the tree: two builds give the same bits.
+ * workspace: smil_bvh_workspace_bytes(N, F_total, P, n_verts) bytes (0: bad sizes; P = 1 for the calls without points).
+ *
+ * smil_bvh_codes: keys (F_total) int64 = mesh << 32 | the 30-bit Morton code of the face's centroid inside its mesh's bounding box,
+ * SMIL_BVH_SENTINEL for a face that is not usable.  The caller sorts the keys with a STABLE sort (ties keep face order) and passes
+ * the permutation perm (F_total) int64 (sorted position -> packed face) to
+ * smil_bvh_build: writes order and boxes.  An entry of perm outside its mesh gives order -1: a row that never wins.
+ * smil_bvh_refit: boxes once more from new vertices (same faces) in the stored order, without a sort.  Exactness never depends on
+ * the quality of the order: a refitted tree answers exactly like a fresh one, only the number of faces visited differs.
+ * smil_bvh_point_codes: keys (N,P) int64: the Morton code of every point inside its mesh's root box (clamped), SMIL_BVH_SENTINEL for
+ * a point at or beyond its cloud's length or with an unusable coordinate: for callers that present their queries in spatial order.
+ * smil_bvh_point_face_distance: dist2 (N,P), face (N,P) int32, bary (N,P,3) as smil_point_face_distance writes them.  One lane per
+ * point, depth first, the nearer child first, the leaf's faces by the same float32 formula in the same power-of-two frame; the
+ * running best is the key {bits of d^2, face} compared lexicographically, and a node is entered when the squared distance D^2 of the
+ * point to its box satisfies D^2 <= (sqrt(best) + 2^-18)^2 (1 + 2^-19) in the frame (<=, never <: a float32 tie reaches the smaller
+ * face index; 2^-18 covers the leaf formula's evaluation error).  evaluated (N,P) int32 or NULL: the number
+ * of leaf faces evaluated for every point (0 for a padded point).  order and boxes are trusted no further than memory safety: a
+ * tree of other meshes gives wrong answers, never an access outside the arrays.  Errors as smil_point_face_distance.
+ * ---------------------------------------------------------------------------------------- */
+#define SMIL_BVH_LEAF 8
+#define SMIL_BVH_SENTINEL 1073741824 /* 2^30: above every 30-bit code */
+size_t smil_bvh_workspace_bytes(int32_t N, int32_t F_total, int32_t P, int32_t n_verts);
+size_t smil_bvh_nodes(int32_t N, int32_t F_total);
+int smil_bvh_codes(const float *verts, int32_t n_verts, const int32_t *faces, const int32_t *face_off, int32_t N, int32_t F_total,
+                   int32_t max_faces, int64_t *keys, void *workspace, void *stream);
+int smil_bvh_build(const float *verts, int32_t n_verts, const int32_t *faces, const int32_t *face_off, int32_t N, int32_t F_total,
+                   int32_t max_faces, const int64_t *perm, int32_t *order, float *boxes, void *workspace, void *stream);
+int smil_bvh_refit(const float *verts, int32_t n_verts, const int32_t *faces, const int32_t *face_off, int32_t N, int32_t F_total,
+                   int32_t max_faces, const int32_t *order, float *boxes, void *workspace, void *stream);
+int smil_bvh_point_codes(const float *verts, int32_t n_verts, const int32_t *faces, const int32_t *face_off, int32_t N,
+                         int32_t F_total, int32_t max_faces, const float *boxes, const float *points, int32_t P,
+                         const int32_t *lengths, int64_t *keys, void *workspace, void *stream);
+int smil_bvh_point_face_distance(const float *verts, int32_t n_verts, const int32_t *faces, const int32_t *face_off, int32_t N,
+                                 int32_t F_total, int32_t max_faces, const int32_t *order, const float *boxes, const float *points,
+                                 int32_t P, const int32_t *lengths, float *dist2, int32_t *face, float *bary,
+                                 int32_t *evaluated /* (N,P) or NULL */, void *workspace, void *stream);
 
 #ifdef __cplusplus
 }

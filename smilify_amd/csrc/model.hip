@@ -20,9 +20,9 @@ extern "C" const char *smil_last_error(void) { return g_err; }
 // "instrumented" marks a library built by `make variant` for tools/dbg (timers, counters, cut-off experiments - possibly with garbage
 // results by design): tests/test_abi_cpu.py checks that the library the product loads is not one of those.
 #ifdef SMIL_INSTRUMENTED
-extern "C" const char *smil_version(void) { return "smilfit 0.12 (gfx950; 0.3 + SmilCameras.principal (0.4) + fragments, depth visibility (0.5) + mesh-free joints, kp3d fit (0.6) + kp2d fit (0.7) + visual hull (0.8) + distance fields (0.9) + hull meshes (0.10) + point-mesh distances (0.11) + winding numbers) instrumented"; }
+extern "C" const char *smil_version(void) { return "smilfit 0.13 (gfx950; 0.3 + SmilCameras.principal (0.4) + fragments, depth visibility (0.5) + mesh-free joints, kp3d fit (0.6) + kp2d fit (0.7) + visual hull (0.8) + distance fields (0.9) + hull meshes (0.10) + point-mesh distances (0.11) + winding numbers (0.12) + mesh BVH) instrumented"; }
 #else
-extern "C" const char *smil_version(void) { return "smilfit 0.12 (gfx950; 0.3 + SmilCameras.principal (0.4) + fragments, depth visibility (0.5) + mesh-free joints, kp3d fit (0.6) + kp2d fit (0.7) + visual hull (0.8) + distance fields (0.9) + hull meshes (0.10) + point-mesh distances (0.11) + winding numbers)"; }
+extern "C" const char *smil_version(void) { return "smilfit 0.13 (gfx950; 0.3 + SmilCameras.principal (0.4) + fragments, depth visibility (0.5) + mesh-free joints, kp3d fit (0.6) + kp2d fit (0.7) + visual hull (0.8) + distance fields (0.9) + hull meshes (0.10) + point-mesh distances (0.11) + winding numbers (0.12) + mesh BVH)"; }
 #endif
 
 // (common.h) the grids of the persistent kernels of every file; what a workgroup may take of the CU's LDS

@@ -36,55 +36,12 @@
 //                   record count (common.h "order-independent scatter sums"): no float atomics, two calls give equal bits, a
 //                   permutation of the points leaves the vertex gradients bit-identical.
 //
-// There is no BVH, grid or cull: the exact minimum over ALL faces is the contract, as in raycast.hip.
-#include <algorithm>
-
-#include "common.h"
-#include "point_tri.h"
+// These kernels use no BVH, grid or cull: the exact minimum over ALL faces is the contract, as in raycast.hip.
+// mesh_bvh.hip finds the same winner through a hierarchy (section 4.22) between this file's pm_prepare() and pm_finish().
+#include "point_mesh.h"
 
 #define PM_BLOCK 256
 #define PM_TILE 128  // faces (48 B) or points (16 B) staged in LDS per step
-
-struct PmArgs {
-    const float *verts;       // (n_verts, 3) packed
-    const int *faces;         // (F_total, 3) into the packed verts
-    const int *face_off;      // (N + 1)
-    const int *vert_off;      // (N + 1), the backward only
-    const float *points;      // (N, P, 3)
-    const int *lengths;       // (N) or NULL: P
-    float4 *table;            // (F_total, 3) {v0, e1, e2} in the mesh's frame
-    unsigned int *ext;        // (N) bits of the largest finite |coordinate| of mesh n
-    unsigned long long *key;  // (N, P) or (F_total): {bits of d^2 in the frame, index}, all ones: none
-    float *dist2;             // (N, P) or (F_total)
-    int *idx;                 // (N, P) face within its mesh or (F_total) point within its cloud, -1: none
-    float *bary;              // (N, P, 3) or (F_total, 3)
-    const float *g;           // upstream gradient per record
-    long long *acc_v;         // (n_verts, 3)
-    long long *acc_p;         // (N, P, 3); the winding numbers' integer sums are its first (N, P)
-    float *winding;           // (N, P)
-    unsigned int *dmax;       // (N) bits of the largest |2 g e| component of mesh n's records
-    float *d_points;          // (N, P, 3)
-    float *d_verts;           // (n_verts, 3)
-    int N, P, n_verts, F_total, splits, by_face;
-};
-
-struct PmMesh { int f0, F, len; };  // first packed face, faces, points of mesh n
-
-__device__ __forceinline__ PmMesh pm_mesh(const PmArgs &a, int n) {
-    PmMesh m;
-    m.f0 = min(max(a.face_off[n], 0), a.F_total);
-    m.F = min(max(a.face_off[n + 1], m.f0), a.F_total) - m.f0;
-    m.len = a.lengths ? min(max(a.lengths[n], 0), a.P) : a.P;
-    return m;
-}
-
-__device__ __forceinline__ float pm_finite_abs(float x) { return fabsf(x) <= 3.0e38f ? fabsf(x) : 0.f; }  // NaN, inf: 0
-
-// the three vertex ids of packed face j, or false when one is outside [0, n_verts)
-__device__ __forceinline__ bool pm_face_ids(const PmArgs &a, size_t j, int (&id)[3]) {
-    id[0] = a.faces[3 * j]; id[1] = a.faces[3 * j + 1]; id[2] = a.faces[3 * j + 2];
-    return (unsigned)id[0] < (unsigned)a.n_verts && (unsigned)id[1] < (unsigned)a.n_verts && (unsigned)id[2] < (unsigned)a.n_verts;
-}
 
 // (every lane of every wave reaches fix_record_max)
 __global__ void __launch_bounds__(256) k_pm_extent(PmArgs a) {
@@ -105,9 +62,6 @@ __global__ void __launch_bounds__(256) k_pm_extent(PmArgs a) {
     }
     fix_record_max(&a.ext[n], big);
 }
-
-// the frame of mesh n: coordinates are multiplied by 2^pm_frame (exactly)
-__device__ __forceinline__ int pm_frame(const PmArgs &a, int n) { return -fix_max_exp(a.ext[n]); }
 
 __global__ void __launch_bounds__(256) k_pm_table(PmArgs a) {
     const int n = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -137,14 +91,6 @@ __global__ void __launch_bounds__(256) k_pm_table(PmArgs a) {
     a.table[3 * j] = v0;
     a.table[3 * j + 1] = e1;
     a.table[3 * j + 2] = e2;
-}
-
-// A point in the frame; NaN (it never wins and nothing wins for it) when a coordinate is not usable: NaN, inf or above 3e38, as for
-// the vertices of a face, whatever the frame does to it.
-__device__ __forceinline__ void pm_load_point(const float *p, int sh, float &x, float &y, float &z) {
-    const bool usable = fabsf(p[0]) <= 3.0e38f && fabsf(p[1]) <= 3.0e38f && fabsf(p[2]) <= 3.0e38f;
-    const float nan = __builtin_nanf("");
-    x = usable ? ldexpf(p[0], sh) : nan; y = usable ? ldexpf(p[1], sh) : nan; z = usable ? ldexpf(p[2], sh) : nan;
 }
 
 __device__ __forceinline__ void pm_put_key(const PmArgs &a, size_t at, float best, int bi) {
@@ -410,37 +356,9 @@ __global__ void __launch_bounds__(256) k_pm_bwd_out(PmArgs a) {
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-static size_t pm_layout(int N, int F_total, int P, int n_verts, char *base, PmArgs &a) {
-    Workspace w{base};
-    a.table = w.take<float4>((size_t)F_total * 3);
-    a.key = w.take<unsigned long long>(std::max((size_t)N * P, (size_t)F_total));
-    a.ext = w.take<unsigned int>((size_t)N);
-    a.dmax = w.take<unsigned int>((size_t)N);
-    a.acc_v = w.take<long long>((size_t)n_verts * 3);
-    a.acc_p = w.take<long long>((size_t)N * P * 3);
-    return w.used;
-}
-
-static bool pm_sizes_ok(int64_t N, int64_t F_total, int64_t P, int64_t n_verts) {
-    return N > 0 && N <= 65535 && F_total > 0 && P > 0 && n_verts > 0 && N * P <= 0x7FFFFFFF / 4 && F_total <= 0x7FFFFFFF / 4 &&
-           n_verts <= 0x7FFFFFFF / 4;
-}
-
 extern "C" size_t smil_point_mesh_workspace_bytes(int32_t N, int32_t F_total, int32_t P, int32_t n_verts) {
     PmArgs a;
     return pm_sizes_ok(N, F_total, P, n_verts) ? pm_layout(N, F_total, P, n_verts, nullptr, a) : 0;
-}
-
-static int pm_fill(PmArgs &a, const char *who, const float *verts, int32_t n_verts, const int32_t *faces, const int32_t *face_off, int32_t N,
-                   int32_t F_total, int32_t max_faces, const float *points, int32_t P, const int32_t *lengths, void *workspace) {
-    SMIL_REQUIRE(verts && faces && face_off && points && workspace, "%s: null argument", who);
-    SMIL_REQUIRE(pm_sizes_ok(N, F_total, P, n_verts), "%s: bad sizes N=%d F=%d P=%d V=%d", who, N, F_total, P, n_verts);
-    SMIL_REQUIRE(max_faces >= 1 && max_faces <= F_total, "%s: max_faces=%d outside 1 .. F=%d", who, max_faces, F_total);
-    a = PmArgs{};
-    pm_layout(N, F_total, P, n_verts, (char *)workspace, a);
-    a.verts = verts; a.faces = (const int *)faces; a.face_off = (const int *)face_off; a.points = points; a.lengths = (const int *)lengths;
-    a.N = N; a.P = P; a.n_verts = n_verts; a.F_total = F_total;
-    return SMIL_OK;
 }
 
 // splits of `cols` candidates for `qblocks` workgroups of queries per mesh: the caller's, or enough workgroups for the whole GPU
@@ -450,25 +368,35 @@ static int pm_splits(int32_t splits, int qblocks, int cols, int N) {
     return splits > 0 ? splits : std::max(1, std::min(std::min(max_split, 65535), ceil_div(2048, qblocks * N)));
 }
 
-// the forward of either direction: `rows` queries and `cols` candidates per mesh at most
-static int pm_forward(PmArgs &a, int max_faces, int32_t splits, hipStream_t stream) {
-    const int rows = a.by_face ? max_faces : a.P, cols = a.by_face ? a.P : max_faces;
-    const size_t n_keys = a.by_face ? (size_t)a.F_total : (size_t)a.N * a.P;
-    const int qblocks = ceil_div(rows, PM_BLOCK);
-    a.splits = pm_splits(splits, qblocks, cols, a.N);
+int pm_prepare(PmArgs &a, int max_faces, size_t n_keys, hipStream_t stream) {
     SMIL_HIP(hipMemsetAsync(a.key, 0xFF, n_keys * sizeof(unsigned long long), stream));
     SMIL_HIP(hipMemsetAsync(a.ext, 0, (size_t)a.N * sizeof(unsigned int), stream));
     hipLaunchKernelGGL(k_pm_extent, dim3(ceil_div(std::max(max_faces, a.P), 256), a.N), dim3(256), 0, stream, a);
     SMIL_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_pm_table, dim3(ceil_div(max_faces, 256), a.N), dim3(256), 0, stream, a);
     SMIL_LAUNCH_CHECK();
+    return SMIL_OK;
+}
+
+int pm_finish(PmArgs &a, int rows, hipStream_t stream) {
+    hipLaunchKernelGGL(k_pm_finish, dim3(ceil_div(rows, 256), a.N), dim3(256), 0, stream, a);
+    SMIL_LAUNCH_CHECK();
+    return SMIL_OK;
+}
+
+// the forward of either direction: `rows` queries and `cols` candidates per mesh at most
+static int pm_forward(PmArgs &a, int max_faces, int32_t splits, hipStream_t stream) {
+    const int rows = a.by_face ? max_faces : a.P, cols = a.by_face ? a.P : max_faces;
+    const size_t n_keys = a.by_face ? (size_t)a.F_total : (size_t)a.N * a.P;
+    const int qblocks = ceil_div(rows, PM_BLOCK);
+    a.splits = pm_splits(splits, qblocks, cols, a.N);
+    int rc = pm_prepare(a, max_faces, n_keys, stream);
+    if (rc != SMIL_OK) return rc;
     const dim3 grid(qblocks, a.splits, a.N);
     if (a.by_face) hipLaunchKernelGGL(k_pm_faces, grid, dim3(PM_BLOCK), 0, stream, a);
     else hipLaunchKernelGGL(k_pm_points, grid, dim3(PM_BLOCK), 0, stream, a);
     SMIL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_pm_finish, dim3(ceil_div(rows, 256), a.N), dim3(256), 0, stream, a);
-    SMIL_LAUNCH_CHECK();
-    return SMIL_OK;
+    return pm_finish(a, rows, stream);
 }
 
 extern "C" int smil_point_face_distance(const float *verts, int32_t n_verts, const int32_t *faces, const int32_t *face_off, int32_t N,

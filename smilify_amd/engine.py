@@ -1039,6 +1039,76 @@ def point_mesh_winding(verts: torch.Tensor, mt: MeshTables, points: torch.Tensor
     return winding
 
 
+# ---- the face hierarchy of packed meshes (mesh_bvh.hip) ------------------------------------------------------------------------
+def _bvh_inputs(who: str, verts: torch.Tensor, mt: MeshTables, P: int = 1):
+    if verts.dtype != torch.float32 or tuple(verts.shape) != (mt.n_verts, 3):
+        raise ValueError(f"{who}: verts ({mt.n_verts},3) packed float32, got {tuple(verts.shape)} {verts.dtype}")
+    if mt.n_faces < 1:
+        raise ValueError(f"{who}: needs at least one face (F={mt.n_faces})")
+    lib = _lib.checked()
+    nbytes = int(lib.smil_bvh_workspace_bytes(mt.n_meshes, mt.n_faces, P, mt.n_verts))
+    if nbytes == 0:
+        raise _lib.SmilError(f"{who}: sizes N={mt.n_meshes} F={mt.n_faces} P={P} V={mt.n_verts} are not supported")
+    return lib, verts.contiguous(), _workspace(nbytes, verts.device)
+
+
+def bvh_build(verts: torch.Tensor, mt: MeshTables):
+    """(order (F_total) int32, boxes (nodes,6) float32) of the meshes' face hierarchies (smil_bvh_codes, a stable torch.sort of the
+    int64 keys, smil_bvh_build).  No host synchronisation."""
+    lib, verts, ws = _bvh_inputs("bvh_build", verts, mt)
+    keys = torch.empty(mt.n_faces, device=verts.device, dtype=torch.int64)
+    lib.smil_bvh_codes(_ptr(verts), mt.n_verts, _ptr(mt.faces), _ptr(mt.face_off), mt.n_meshes, mt.n_faces, mt.max_faces, _ptr(keys), _ptr(ws),
+                       _stream())
+    perm = torch.sort(keys, stable=True).indices.contiguous()
+    order = torch.empty(mt.n_faces, device=verts.device, dtype=torch.int32)
+    # (zeros: the rows that no node owns - row 0 of every mesh, the padding to the next - are never written)
+    boxes = torch.zeros((int(lib.smil_bvh_nodes(mt.n_meshes, mt.n_faces)), 6), device=verts.device, dtype=torch.float32)
+    lib.smil_bvh_build(_ptr(verts), mt.n_verts, _ptr(mt.faces), _ptr(mt.face_off), mt.n_meshes, mt.n_faces, mt.max_faces, _ptr(perm), _ptr(order),
+                       _ptr(boxes), _ptr(ws), _stream())
+    return order, boxes
+
+
+def bvh_refit(verts: torch.Tensor, mt: MeshTables, order: torch.Tensor, boxes: torch.Tensor) -> None:
+    """The boxes of ``bvh_build`` once more, in place, from new vertices in the stored order (smil_bvh_refit)."""
+    lib, verts, ws = _bvh_inputs("bvh_refit", verts, mt)
+    lib.smil_bvh_refit(_ptr(verts), mt.n_verts, _ptr(mt.faces), _ptr(mt.face_off), mt.n_meshes, mt.n_faces, mt.max_faces, _ptr(order), _ptr(boxes),
+                       _ptr(ws), _stream())
+
+
+def bvh_point_face_distance(verts: torch.Tensor, mt: MeshTables, order: torch.Tensor, boxes: torch.Tensor, points: torch.Tensor,
+                            lengths: Optional[torch.Tensor] = None, sort_queries: bool = False, want_evaluated: bool = False):
+    """``point_mesh_distance`` (points -> faces) through the hierarchy: the same dist2 (N,P), face (N,P) int32 and bary (N,P,3), bit for
+    bit, and with ``want_evaluated`` the number of leaf faces evaluated per point (N,P) int32 (else None).  ``sort_queries``: the
+    lanes of a wave take points that are neighbours in space (smil_bvh_point_codes, a stable sort, the results scattered back): the
+    same answers, other timings."""
+    who = "bvh_point_face_distance"
+    _, verts, points, lengths, _ = _point_mesh_inputs(who, verts, mt, points, lengths)
+    N, P = mt.n_meshes, int(points.shape[1])
+    lib, verts, ws = _bvh_inputs(who, verts, mt, P)
+    if tuple(order.shape) != (mt.n_faces,) or order.dtype != torch.int32 or boxes.dtype != torch.float32 or \
+            tuple(boxes.shape) != (int(lib.smil_bvh_nodes(N, mt.n_faces)), 6):
+        raise ValueError(f"{who}: order and boxes are not a hierarchy of these meshes")
+    mesh = (_ptr(verts), mt.n_verts, _ptr(mt.faces), _ptr(mt.face_off), N, mt.n_faces, mt.max_faces)
+    back = None
+    if sort_queries:
+        keys = torch.empty((N, P), device=verts.device, dtype=torch.int64)
+        lib.smil_bvh_point_codes(*mesh, _ptr(boxes), _ptr(points), P, _ptr(lengths), _ptr(keys), _ptr(ws), _stream())
+        back = torch.sort(keys, dim=1, stable=True).indices  # (padded and unusable points sort behind the cloud, in their order)
+        points = torch.gather(points, 1, back[:, :, None].expand(N, P, 3)).contiguous()
+    dist2 = torch.empty((N, P), device=verts.device, dtype=torch.float32)
+    face = torch.empty((N, P), device=verts.device, dtype=torch.int32)
+    bary = torch.empty((N, P, 3), device=verts.device, dtype=torch.float32)
+    evaluated = torch.empty((N, P), device=verts.device, dtype=torch.int32) if want_evaluated else None
+    lib.smil_bvh_point_face_distance(*mesh, _ptr(order), _ptr(boxes), _ptr(points), P, _ptr(lengths), _ptr(dist2), _ptr(face), _ptr(bary),
+                                     _ptr(evaluated), _ptr(ws), _stream())
+    if back is not None:
+        dist2, face = torch.empty_like(dist2).scatter_(1, back, dist2), torch.empty_like(face).scatter_(1, back, face)
+        bary = torch.empty_like(bary).scatter_(1, back[:, :, None].expand(N, P, 3), bary)
+        if evaluated is not None:
+            evaluated = torch.empty_like(evaluated).scatter_(1, back, evaluated)
+    return dist2, face, bary, evaluated
+
+
 # ---- PointNet++ set-abstraction operations (pointnet2.hip) ---------------------------------------------------------------------
 def _check_cloud(what: str, name: str, t: torch.Tensor, B: Optional[int] = None, last: Optional[int] = 3) -> None:
     if not (isinstance(t, torch.Tensor) and t.dim() == 3 and t.dtype == torch.float32 and (last is None or t.shape[2] == last)

@@ -305,9 +305,9 @@ def mesh_laplacian_smoothing(meshes: Meshes, method: str = "uniform"):
 # ---- exact point <-> mesh distances (csrc/point_mesh.hip; an extension, pytorch3d's loss.point_mesh_face_distance) -----------------
 class _PointMeshFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, verts_packed, points, mt, lengths, by_face):
+    def forward(ctx, verts_packed, points, mt, lengths, by_face, bvh=None):
         v, p = _gpu_f32(verts_packed), _gpu_f32(points)
-        dist2, idx, _ = engine.point_mesh_distance(v, mt, p, lengths, by_face)
+        dist2, idx, _ = _search(v, mt, p, lengths, by_face, bvh)
         ctx.save_for_backward(v, p, idx)
         ctx.call = (mt, lengths, by_face)
         idx = idx.long()
@@ -319,22 +319,34 @@ class _PointMeshFn(torch.autograd.Function):
         v, p, idx = ctx.saved_tensors
         mt, lengths, by_face = ctx.call
         d_points, d_verts = engine.point_mesh_backward(v, mt, p, lengths, idx, g.to(torch.float32).contiguous(), by_face)
-        return d_verts, d_points, None, None, None
+        return d_verts, d_points, None, None, None, None
 
 
-def _point_mesh(meshes: Meshes, points, lengths, by_face: bool):
+def _search(v, mt, p, lengths, by_face: bool, bvh):
+    """The forward search: the brute force, or - points -> faces only - the hierarchy ``bvh`` (``mesh3d.MeshBVH``), which records the
+    same faces, so that the backward is the same call on the same records."""
+    if bvh is None:
+        return engine.point_mesh_distance(v, mt, p, lengths, by_face)
+    return bvh.query(p, lengths, verts=v)[:3]
+
+
+def _point_mesh(meshes: Meshes, points, lengths, by_face: bool, bvh=None):
     if not (isinstance(points, torch.Tensor) and points.dim() == 3 and points.shape[2] == 3 and points.shape[0] == len(meshes)):
         raise ValueError(f"points ({len(meshes)},P,3) for {len(meshes)} meshes")
     engine.require_gpu(meshes.device)
-    return _PointMeshFn.apply(meshes.verts_packed(), points, meshes.face_tables(), lengths, by_face)
+    if bvh is not None:
+        bvh._check(meshes)
+    return _PointMeshFn.apply(meshes.verts_packed(), points, meshes.face_tables(), lengths, by_face, bvh)
 
 
-def point_face_distance(meshes: Meshes, points: torch.Tensor, lengths: Optional[torch.Tensor] = None):
+def point_face_distance(meshes: Meshes, points: torch.Tensor, lengths: Optional[torch.Tensor] = None, *, bvh=None):
     """(dist2 (N,P), face (N,P) int64): for every point of ``points`` (N,P,3) the squared Euclidean distance to the nearest closed
     triangle of its mesh and that face's index within the mesh.  Differentiable in ``points`` and in the meshes' vertices (through
     ``offset_verts`` too); the indices carry no gradient.  Points at or beyond ``lengths`` (N), non-finite points and meshes without a
-    usable face give ``inf`` and -1 and receive no gradient.  Exact: a brute-force search, no acceleration structure."""
-    return _point_mesh(meshes, points, lengths, False)
+    usable face give ``inf`` and -1 and receive no gradient.  Exact: a brute-force search; with ``bvh``, a ``mesh3d.MeshBVH`` built
+    or refitted on these meshes' vertices, the same records and hence the same values and gradients, bit for bit, through the
+    hierarchy."""
+    return _point_mesh(meshes, points, lengths, False, bvh)
 
 
 def face_point_distance(meshes: Meshes, points: torch.Tensor, lengths: Optional[torch.Tensor] = None):
@@ -375,9 +387,9 @@ def _inside(meshes: Meshes, points: torch.Tensor, lengths, oriented: bool) -> to
 
 class _SignedDistanceFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, verts_packed, points, mt, lengths, inside):
+    def forward(ctx, verts_packed, points, mt, lengths, inside, bvh=None):
         v, p = _gpu_f32(verts_packed), _gpu_f32(points)
-        dist2, idx, _ = engine.point_mesh_distance(v, mt, p, lengths, False)
+        dist2, idx, _ = _search(v, mt, p, lengths, False, bvh)
         sign = torch.where(inside, -torch.ones_like(dist2), torch.ones_like(dist2))
         ctx.save_for_backward(v, p, idx, dist2, sign)
         ctx.call = (mt, lengths)
@@ -393,7 +405,7 @@ class _SignedDistanceFn(torch.autograd.Function):
         up = torch.where(live, g.to(torch.float32) * sign / (2.0 * torch.where(live, dist2, torch.ones_like(dist2)).sqrt()),
                          torch.zeros_like(dist2))
         d_points, d_verts = engine.point_mesh_backward(v, mt, p, lengths, idx, up.contiguous(), False)
-        return d_verts, d_points, None, None, None
+        return d_verts, d_points, None, None, None, None
 
 
 def _check_cloud_batch(meshes: Meshes, points) -> None:
@@ -402,20 +414,25 @@ def _check_cloud_batch(meshes: Meshes, points) -> None:
     engine.require_gpu(meshes.device)
 
 
-def point_mesh_signed_distance(meshes: Meshes, points: torch.Tensor, lengths: Optional[torch.Tensor] = None, oriented: bool = True):
+def point_mesh_signed_distance(meshes: Meshes, points: torch.Tensor, lengths: Optional[torch.Tensor] = None, oriented: bool = True, *,
+                               bvh=None):
     """(sdist (N,P), face (N,P) int64): the Euclidean distance of every point to the surface of its mesh, negative inside, and the
     nearest face.  Inside: the generalised winding number is > 0.5 (``oriented=False``: its magnitude, for scans with inward faces);
     see ``mesh3d.winding_number`` for what that means on open or self-intersecting meshes.  Differentiable in the points and in the
     meshes' vertices: the gradient of ``sign * sqrt(dist2)`` at the recorded face, the sign a constant; exactly 0 for a point on the
-    surface (dist2 == 0) and where there is no face (+inf, -1)."""
+    surface (dist2 == 0) and where there is no face (+inf, -1).  ``bvh``: as in ``point_face_distance``, for the distance; the winding
+    numbers stay the brute-force sum."""
     _check_cloud_batch(meshes, points)
-    return _SignedDistanceFn.apply(meshes.verts_packed(), points, meshes.face_tables(), lengths, _inside(meshes, points, lengths, oriented))
+    if bvh is not None:
+        bvh._check(meshes)
+    return _SignedDistanceFn.apply(meshes.verts_packed(), points, meshes.face_tables(), lengths, _inside(meshes, points, lengths, oriented),
+                                   bvh)
 
 
-def _one_sided_loss(meshes: Meshes, points, lengths, weights, oriented: bool, want_inside: bool) -> torch.Tensor:
+def _one_sided_loss(meshes: Meshes, points, lengths, weights, oriented: bool, want_inside: bool, bvh=None) -> torch.Tensor:
     _check_cloud_batch(meshes, points)
     N, P = len(meshes), int(points.shape[1])
-    dist2, face = point_face_distance(meshes, points, lengths)
+    dist2, face = point_face_distance(meshes, points, lengths, bvh=bvh)
     inside = _inside(meshes, points, lengths, oriented)
     counted = (face >= 0) & (inside if want_inside else ~inside)
     valid = torch.ones(N, P, dtype=torch.bool, device=dist2.device) if lengths is None else \
@@ -426,18 +443,21 @@ def _one_sided_loss(meshes: Meshes, points, lengths, weights, oriented: bool, wa
     return ((w * torch.where(counted, dist2, torch.zeros_like(dist2))).sum(1) / norm).sum() / N  # (the masked side: upstream 0)
 
 
-def containment_loss(meshes: Meshes, points: torch.Tensor, lengths: Optional[torch.Tensor] = None, weights=None, oriented: bool = True):
+def containment_loss(meshes: Meshes, points: torch.Tensor, lengths: Optional[torch.Tensor] = None, weights=None, oriented: bool = True, *,
+                     bvh=None):
     """Pulls points INTO their meshes: per cloud the mean over its valid points (``weights`` (N,P): the weighted mean, sum(w x) /
     sum(w)) of the squared distance to the surface where the point is outside and 0 where it is inside, averaged over the batch.  The
     mesh counterpart of ``HullDistanceField.containment_loss``, at the mesh's own resolution.  C1 at the surface (no square root);
-    inside points, points without a face and points beyond ``lengths`` receive exactly no gradient."""
-    return _one_sided_loss(meshes, points, lengths, weights, oriented, False)
+    inside points, points without a face and points beyond ``lengths`` receive exactly no gradient.  ``bvh``: as in
+    ``point_face_distance``."""
+    return _one_sided_loss(meshes, points, lengths, weights, oriented, False, bvh)
 
 
-def penetration_loss(meshes: Meshes, points: torch.Tensor, lengths: Optional[torch.Tensor] = None, weights=None, oriented: bool = True):
+def penetration_loss(meshes: Meshes, points: torch.Tensor, lengths: Optional[torch.Tensor] = None, weights=None, oriented: bool = True, *,
+                     bvh=None):
     """Pushes points OUT of their meshes: ``containment_loss`` with the roles swapped - the squared distance to the surface where the
     point is inside, 0 where it is outside."""
-    return _one_sided_loss(meshes, points, lengths, weights, oriented, True)
+    return _one_sided_loss(meshes, points, lengths, weights, oriented, True, bvh)
 
 
 # ---- model ----------------------------------------------------------------------------------------------------------------------

@@ -11,6 +11,8 @@
   distance, face, barycentrics - on the kernels of csrc/point_mesh.hip: the registration metric.
 * ``winding_number`` / ``contains`` / ``signed_distance`` (an extension): on which side of its mesh's surface a point lies, by the
   generalised winding number (the same file's k_pm_winding).
+* ``MeshBVH(meshes)`` (an extension): a face hierarchy built once for meshes that stay put (csrc/mesh_bvh.hip); ``closest_points(...,
+  bvh=)`` and the distance half of ``signed_distance(..., bvh=)`` then give the brute force's bits without the scan over all faces.
 """
 from __future__ import annotations
 
@@ -269,21 +271,94 @@ class Meshes:
 ClosestPoints = namedtuple("ClosestPoints", "dist2 face bary points")
 
 
-def closest_points(meshes: Meshes, points: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> ClosestPoints:
-    """For every point of ``points`` (N,P,3) the closest point of the surface of its mesh: squared distance (N,P), face within the mesh
-    (N,P) int64, barycentrics (N,P,3) and the closest points themselves (N,P,3).  ``dist2.sqrt()`` is the surface error per point - the
-    registration metric.  Exact (the true Euclidean distance to the closed triangles, a brute-force search over every face, the value
-    in float64); not differentiable (``fit3d.point_face_distance`` is); no host synchronisation.  ``lengths`` (N): points at or beyond
-    a cloud's length, non-finite points and meshes without a usable face give ``inf``, face -1 and zeros."""
-    engine.require_gpu(meshes.device)
-    verts = meshes.verts_packed().detach().to(torch.float32).contiguous()
-    pts = points.detach().to(device=verts.device, dtype=torch.float32).contiguous()
-    mt = meshes.face_tables()
-    dist2, face, bary = engine.point_mesh_distance(verts, mt, pts, lengths)
+class MeshBVH:
+    """A bounding-volume hierarchy over the faces of ``meshes`` (csrc/mesh_bvh.hip), built once on the GPU for
+    meshes that do not change during a run: ``closest_points`` answers exactly as ``mesh3d.closest_points`` does - the same face, the
+    same bits - but visits only the faces near each point.  ``refit(meshes)`` takes new vertices with the same faces and keeps the
+    order; the answers stay exact however far the vertices moved, only the number of faces visited grows.  No host synchronisation at
+    construction or after it.  ``sort_queries``: whether the queries are handed to the kernel in Morton order (the same answers)."""
+
+    SORT_QUERIES = False  # the default of ``sort_queries``: the faster setting of tools/mesh_bvh_probe.py (DESIGN.md section 4.22)
+
+    def __init__(self, meshes: Meshes, sort_queries: Optional[bool] = None):
+        engine.require_gpu(meshes.device)
+        self.sort_queries = self.SORT_QUERIES if sort_queries is None else bool(sort_queries)
+        self._tables = meshes.face_tables()
+        self._verts = meshes.verts_packed().detach().to(torch.float32).contiguous()
+        self._order, self._boxes = engine.bvh_build(self._verts, self._tables)
+        self._face_off_host = np.concatenate([[0], np.cumsum(meshes.num_faces_per_mesh())]).tolist()
+
+    def _check(self, meshes: Meshes) -> "engine.MeshTables":
+        """The tables of ``meshes``, which must have this hierarchy's face arrays (the same object, or the same sizes: the contents
+        are the caller's statement, as ``refit`` documents)."""
+        mt, own = meshes.face_tables(), self._tables
+        if mt is not own and (mt.n_meshes, mt.n_faces, mt.max_faces, mt.n_verts, mt.max_verts) != \
+                (own.n_meshes, own.n_faces, own.max_faces, own.n_verts, own.max_verts):
+            raise ValueError("MeshBVH: these are not the meshes the hierarchy was built for (other face or vertex counts)")
+        return own
+
+    def refit(self, meshes: Meshes) -> "MeshBVH":
+        """New vertices, the same faces (``offset_verts`` of the built meshes, or meshes of equal face arrays - that they are equal is
+        the caller's statement): every box is recomputed in the stored order, without a sort."""
+        self._check(meshes)
+        self._verts = meshes.verts_packed().detach().to(torch.float32).contiguous()
+        engine.bvh_refit(self._verts, self._tables, self._order, self._boxes)
+        return self
+
+    def query(self, points: torch.Tensor, lengths: Optional[torch.Tensor] = None, want_evaluated: bool = False, verts=None):
+        """(dist2, face int32, bary, evaluated or None) of ``engine.bvh_point_face_distance`` on the hierarchy's vertices (``verts``:
+        the same values with another history, for autograd)."""
+        return engine.bvh_point_face_distance(self._verts if verts is None else verts, self._tables, self._order, self._boxes, points, lengths,
+                                              self.sort_queries, want_evaluated)
+
+    def closest_points(self, points: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> "ClosestPoints":
+        """``mesh3d.closest_points`` of the built (or refitted) meshes, bit for bit."""
+        pts = points.detach().to(device=self._verts.device, dtype=torch.float32).contiguous()
+        dist2, face, bary, _ = self.query(pts, lengths)
+        return _closest(self._verts, self._tables, dist2, face, bary)
+
+    def evaluated(self, points: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(N,P) int32: how many leaf faces the search evaluated for every point (the brute force evaluates every face)."""
+        return self.query(points.detach().to(device=self._verts.device, dtype=torch.float32).contiguous(), lengths, True)[3]
+
+    def arrays(self) -> dict:
+        """For inspection: ``order`` (F_total) int32, sorted position -> face within its mesh, mesh n's positions at
+        ``face_off[n]`` ..; ``boxes`` (nodes,6) float32, lo xyz and hi xyz; and per mesh, from the shapes alone (host lists):
+        ``node0`` (row of ``boxes`` that heap index 0 would take: node i is row node0 + i, the root is 1), ``leaves`` (L) and
+        ``padded_leaves`` (Lp, a power of two: leaf k is node Lp + k and holds the sorted positions k * leaf_size ..) and
+        ``leaf_size``."""
+        leaf = int(engine._lib.BVH_LEAF)
+        nf = [int(b) - int(a) for a, b in zip(self._face_off_host[:-1], self._face_off_host[1:])]
+        L = [-(-f // leaf) for f in nf]
+        Lp = [1 << max(l - 1, 0).bit_length() for l in L]
+        node0 = [4 * (int(f0) // leaf + n) for n, f0 in enumerate(self._face_off_host[:-1])]
+        return dict(order=self._order, boxes=self._boxes, node0=node0, leaves=L, padded_leaves=Lp, leaf_size=leaf)
+
+
+def _closest(verts, mt, dist2, face, bary) -> "ClosestPoints":
     face = face.long()
     first = mt.face_off[:-1].long()[:, None]
     tri = verts[mt.faces.long()[(face.clamp(min=0) + first)]]  # (N,P,3,3)
     return ClosestPoints(dist2, face, bary, (bary[..., None] * tri).sum(-2))
+
+
+def closest_points(meshes: Meshes, points: torch.Tensor, lengths: Optional[torch.Tensor] = None, *, bvh: Optional[MeshBVH] = None) -> ClosestPoints:
+    """For every point of ``points`` (N,P,3) the closest point of the surface of its mesh: squared distance (N,P), face within the mesh
+    (N,P) int64, barycentrics (N,P,3) and the closest points themselves (N,P,3).  ``dist2.sqrt()`` is the surface error per point - the
+    registration metric.  Exact (the true Euclidean distance to the closed triangles, a brute-force search over every face, the value
+    in float64); not differentiable (``fit3d.point_face_distance`` is); no host synchronisation.  ``lengths`` (N): points at or beyond
+    a cloud's length, non-finite points and meshes without a usable face give ``inf``, face -1 and zeros.  ``bvh``: a ``MeshBVH`` of
+    these meshes (built or refitted on these vertices): the same result, bit for bit, through the hierarchy."""
+    engine.require_gpu(meshes.device)
+    verts = meshes.verts_packed().detach().to(torch.float32).contiguous()
+    pts = points.detach().to(device=verts.device, dtype=torch.float32).contiguous()
+    mt = meshes.face_tables()
+    if bvh is not None:
+        bvh._check(meshes)
+        dist2, face, bary, _ = bvh.query(pts, lengths, verts=verts)
+    else:
+        dist2, face, bary = engine.point_mesh_distance(verts, mt, pts, lengths)
+    return _closest(verts, mt, dist2, face, bary)
 
 
 SignedDistance = namedtuple("SignedDistance", "sdist dist2 face bary points winding")
@@ -312,11 +387,13 @@ def contains(meshes: Meshes, points: torch.Tensor, lengths: Optional[torch.Tenso
     return _inside(winding_number(meshes, points, lengths), oriented)
 
 
-def signed_distance(meshes: Meshes, points: torch.Tensor, lengths: Optional[torch.Tensor] = None, oriented: bool = True) -> SignedDistance:
+def signed_distance(meshes: Meshes, points: torch.Tensor, lengths: Optional[torch.Tensor] = None, oriented: bool = True, *,
+                    bvh: Optional[MeshBVH] = None) -> SignedDistance:
     """``closest_points`` with a sign: ``sdist`` (N,P) = -sqrt(dist2) where ``contains`` says inside, +sqrt(dist2) elsewhere, +inf where
     ``closest_points`` gives inf; then its dist2, face, bary and points, and the winding number that decided.  Not differentiable
-    (``fit3d.point_mesh_signed_distance`` is)."""
-    cp = closest_points(meshes, points, lengths)
+    (``fit3d.point_mesh_signed_distance`` is).  ``bvh``: as in ``closest_points``, for the distance; the winding number stays the
+    brute-force sum over all faces."""
+    cp = closest_points(meshes, points, lengths, bvh=bvh)
     w = winding_number(meshes, points, lengths)
     d = cp.dist2.sqrt()
     return SignedDistance(torch.where(_inside(w, oriented), -d, d), cp.dist2, cp.face, cp.bary, cp.points, w)
