@@ -8,9 +8,8 @@
 //                        w0 = 1 - sqrt(u), w1 = sqrt(u)(1 - v), w2 = sqrt(u) v (pytorch3d _rand_barycentric_coords).
 //  * k_chamfer_nn        lane = CH_QPT query points, both directions in one launch; candidates stream through LDS as float4 and every
 //                        lane reads the same one (a broadcast).  Direct form sum (q - c)^2, running min with a strict <.  Candidate
-//                        ranges may be split across workgroups; the splits merge through a 64-bit atomicMin of (distance bits, index),
-//                        which is order independent (distances are >= 0, so their bits order like the values; ties go to the
-//                        smaller index, as a sequential scan with < gives).
+//                        ranges may be split across workgroups; the splits merge in the query's key, minimum flavour.  The key, the
+//                        split's range and count and the staging are scan.h's, as for k_knn, raycast.hip and point_mesh.hip.
 //  * k_chamfer_owned     thread per query: argmin out, the owned gradient 2 w (q - c*), and the scattered side (c* - q) added to the
 //                        candidate's int64 fixed-point accumulator, whose unit follows the largest minimum found and the number
 //                        of queries of its (mesh, direction): ch_fix_exp, and "order-independent scatter sums" in common.h.
@@ -23,7 +22,7 @@
 //
 // The SDF-guided term (reference fitter_3d/utils.py:973-1394, trainer.py:398-433), see the section at the end of the file:
 //  * k_knn               wave = KNN_QPW queries, both directions in one launch.  A query's K-list is spread over the wave's lanes as
-//                        64-bit keys {distance bits, candidate index}, ascending; lane l takes candidate c0 + l of every 64, and a
+//                        keys (scan.h), ascending; lane l takes candidate c0 + l of every 64 of a tile (scan_tiles), and a
 //                        candidate enters a list only when its key is below the list's K-th (one compare and a ballot per query).
 //  * k_sdf_stats         per (mesh, side) mean and unbiased std of the values in two float64 passes, then the z-scores.
 //  * k_sdf_term          wave per query, lane per neighbour: softmax weights, r_i, the owned gradient, and the scattered gradient into
@@ -32,7 +31,7 @@
 //                        gathered; k_sv_* scatter a gradient on the samples back to the vertices as int64 fixed point.
 #include <algorithm>
 
-#include "common.h"
+#include "scan.h"
 
 #define CH_BLOCK 256
 #define CH_QPT 4                      // query points per lane of k_chamfer_nn
@@ -135,24 +134,14 @@ __device__ __forceinline__ int ch_fix_exp(const CloudLossArgs &a, int n, int d) 
     return fix_unit_exp(((fix_max_exp(a.dmax[n * 2 + d]) + 1) >> 1) + 1, (long long)a.P[d] * a.K);
 }
 
-// The workgroup's first cnt (<= 256) threads stage candidates c0 .. c0 + cnt - 1 of C into LDS as float4, between two barriers.
-__device__ __forceinline__ void stage_tile(float4 *tile, const float *C, int c0, int cnt) {
-    __syncthreads();
-    if ((int)threadIdx.x < cnt) {
-        const float *p = C + 3 * (size_t)(c0 + threadIdx.x);
-        tile[threadIdx.x] = make_float4(p[0], p[1], p[2], 0.f);
-    }
-    __syncthreads();
-}
-
 __global__ void __launch_bounds__(CH_BLOCK) k_chamfer_nn(ChamferArgs a) {
     __shared__ float4 tile[CH_TILE];
     const int d = blockIdx.z % a.dirs, n = blockIdx.z / a.dirs;
     const int Pq = a.P[d], Pc = a.P[1 - d];
     const int q0 = blockIdx.x * (CH_BLOCK * CH_QPT);
     if (q0 >= Pq) return;  // (block-uniform)
-    const int chunk = ((Pc + a.splits - 1) / a.splits + CH_TILE - 1) / CH_TILE * CH_TILE;
-    const int c_begin = blockIdx.y * chunk, c_end = min(Pc, c_begin + chunk);
+    int c_begin, c_end;
+    scan_split_range(Pc, a.splits, CH_TILE, c_begin, c_end);
     if (c_begin >= c_end) return;
     const float *Q = a.pts[d] + (size_t)n * Pq * 3;
     const float *C = a.pts[1 - d] + (size_t)n * Pc * 3;
@@ -166,9 +155,9 @@ __global__ void __launch_bounds__(CH_BLOCK) k_chamfer_nn(ChamferArgs a) {
         best[k] = __builtin_inff();
         bi[k] = 0x7FFFFFFF;
     }
-    for (int c0 = c_begin; c0 < c_end; c0 += CH_TILE) {
+    for (int c0 = c_begin; c0 < c_end; c0 += CH_TILE) {  // (scan_tiles written out: as a lambda the body costs 19 VGPRs and a wave)
         const int cnt = min(CH_TILE, c_end - c0);
-        stage_tile(tile, C, c0, cnt);
+        scan_stage(tile, ScanStageXyz{C}, c0, cnt);
 #pragma unroll 4
         for (int j = 0; j < cnt; ++j) {
             const float4 c = tile[j];
@@ -186,9 +175,7 @@ __global__ void __launch_bounds__(CH_BLOCK) k_chamfer_nn(ChamferArgs a) {
     for (int k = 0; k < CH_QPT; ++k) {
         const int q = q0 + k * CH_BLOCK + threadIdx.x;
         if (q < Pq) {
-            const unsigned long long kv = ((unsigned long long)__float_as_uint(best[k]) << 32) | (unsigned long long)(uint32_t)bi[k];
-            if (a.splits == 1) key[q] = kv;
-            else atomicMin(&key[q], kv);
+            scan_put_min(&key[q], a.splits, best[k], bi[k]);
             bmax = fmaxf(bmax, best[k]);
         }
     }
@@ -202,8 +189,8 @@ __global__ void __launch_bounds__(256) k_chamfer_owned(ChamferArgs a) {
     if (q >= Pq) return;
     const size_t r = ch_row(a, n, d) + q;
     const unsigned long long kv = a.key[r];
-    const int j = (int)(uint32_t)(kv & 0xFFFFFFFFull);
-    a.dist[r] = __uint_as_float((uint32_t)(kv >> 32));
+    const int j = scan_key_index(kv);
+    a.dist[r] = scan_key_value(kv);
     if (a.idx[d]) a.idx[d][(size_t)n * Pq + q] = j;
     if (!a.grad[0]) return;
     if (j < 0 || j >= Pc) return;  // (every query sees at least one candidate: P >= 1 is checked on the host)
@@ -317,11 +304,9 @@ extern "C" int smil_chamfer(const float *x, const float *y, int32_t N, int32_t P
     cloud_loss_fill(a, x, y, N, P1, P2, single_directional, point_sum, batch_sum, d_x, d_y, loss);
     a.K = 1;
     a.idx[0] = idx_x; a.idx[1] = idx_y;
-    // candidate splits: enough workgroups for the whole GPU (>= 2048) while every split still streams >= 4 tiles
+    // candidate splits: >= 2048 workgroups while every split still streams >= 4 tiles
     const int qblocks = ceil_div(std::max(P1, P2), CH_BLOCK * CH_QPT);
-    const int base = qblocks * N * a.dirs;
-    const int max_split = std::max(1, std::min(P1, P2) / (4 * CH_TILE));
-    a.splits = std::max(1, std::min(max_split, ceil_div(2048, base)));
+    a.splits = scan_splits(0, qblocks * N * a.dirs, std::min(P1, P2), CH_TILE, 4, 2048);
     SMIL_HIP(hipMemsetAsync(a.key, 0xFF, pts * 8, stream));
     if (d_x) {
         SMIL_HIP(hipMemsetAsync(a.acc, 0, pts * 3 * 8, stream));
@@ -540,7 +525,7 @@ extern "C" int smil_mesh_regularisers(const SmilMeshTopology *t, const float *ve
 #define KNN_QPW 4                     // queries per wave of k_knn
 #define KNN_QPB (KNN_QPW * KNN_BLOCK / WAVE)
 #define KNN_TILE 256                  // candidates staged in LDS per step
-#define KNN_EMPTY 0xFFFFFFFFFFFFFFFFull
+#define KNN_EMPTY SCAN_KEY_NONE
 static_assert(SMIL_KNN_MAX_K == WAVE, "k_knn keeps one list entry per lane");
 
 struct KnnArgs {
@@ -577,9 +562,7 @@ __global__ void __launch_bounds__(KNN_BLOCK) k_knn(KnnArgs a) {
         thr[k] = q0 + k < Pq ? KNN_EMPTY : 0ull;  // (a query past the end accepts nothing)
     }
     unsigned int ins = 0;
-    for (int c0 = 0; c0 < Pc; c0 += KNN_TILE) {
-        const int cnt = min(KNN_TILE, Pc - c0);
-        stage_tile(tile, C, c0, cnt);
+    scan_tiles<KNN_TILE>(0, Pc, tile, ScanStageXyz{C}, [&](int c0, int cnt) {
         for (int j0 = 0; j0 < cnt; j0 += WAVE) {
             const int j = j0 + lane;  // (< KNN_TILE: the read stays inside the tile, entries past cnt are not used)
             const float4 c = tile[j];
@@ -587,8 +570,7 @@ __global__ void __launch_bounds__(KNN_BLOCK) k_knn(KnnArgs a) {
             for (int k = 0; k < KNN_QPW; ++k) {
                 const float dx = qx[k] - c.x, dy = qy[k] - c.y, dz = qz[k] - c.z;
                 const float dd = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-                const unsigned long long ck =
-                    j < cnt ? ((unsigned long long)__float_as_uint(dd) << 32) | (unsigned long long)(uint32_t)(c0 + j) : KNN_EMPTY;
+                const unsigned long long ck = j < cnt ? scan_key(dd, c0 + j) : KNN_EMPTY;
                 unsigned long long m = __ballot(ck < thr[k]);
                 while (m) {
                     const int l = __ffsll((long long)m) - 1;
@@ -603,7 +585,7 @@ __global__ void __launch_bounds__(KNN_BLOCK) k_knn(KnnArgs a) {
                 }
             }
         }
-    }
+    });
     float kmax = 0.f;
 #pragma unroll
     for (int k = 0; k < KNN_QPW; ++k) {
@@ -611,10 +593,10 @@ __global__ void __launch_bounds__(KNN_BLOCK) k_knn(KnnArgs a) {
         if (q < Pq) {
             if (lane < a.K) {
                 const size_t o = ((size_t)n * Pq + q) * a.K + lane;
-                a.dists[d][o] = __uint_as_float((uint32_t)(key[k] >> 32));
-                a.idx[d][o] = (int)(uint32_t)key[k];
+                a.dists[d][o] = scan_key_value(key[k]);
+                a.idx[d][o] = scan_key_index(key[k]);
             }
-            kmax = fmaxf(kmax, __uint_as_float((uint32_t)(thr[k] >> 32)));  // (K <= Pc: the K-th entry is a candidate)
+            kmax = fmaxf(kmax, scan_key_value(thr[k]));  // (K <= Pc: the K-th entry is a candidate)
         }
     }
     if (lane == 0) {  // (kmax is wave-uniform already: fix_record_max's wave maximum is not needed; the sum is an integer's)

@@ -22,7 +22,7 @@
 //  * k_bvh_points   lane = one point.  Depth first, nearer child first, WITHOUT a stack: in a heap the node still owed at level l is
 //                   the sibling of the path's node at level l, so one bit per level (`owed`) is the whole traversal state - nothing
 //                   is indexed dynamically and nothing can spill.  At a leaf: closest_on_triangle<float> on the rows of the table,
-//                   the arithmetic of k_pm_points.  The running best is the key {bits of d^2, face} compared lexicographically - what
+//                   the arithmetic of k_pm_points.  The running best is the key of scan.h, {d^2, face} compared lexicographically - what
 //                   a sequential scan with a strict < selects - and a node is entered when its box's squared distance D^2 satisfies
 //                   D^2 <= (sqrt(best) + EPS)^2 (1 + 2^-19): <=, never <, so that a float32 tie still reaches the smaller face
 //                   index, and with the margin EPS for the float32 evaluation error of the leaf formula (bvh_visit_limit).
@@ -65,17 +65,9 @@ __device__ __forceinline__ unsigned int bvh_ordered(float x) {
 }
 __device__ __forceinline__ float bvh_unordered(unsigned int o) { return __uint_as_float((o & 0x80000000u) ? o & 0x7FFFFFFFu : ~o); }
 
-// the vertices of face `t` of mesh m when it is usable (ids in range, nine finite coordinates)
+// the vertices of face `t` of mesh m when there is such a face and it is usable (point_mesh.h)
 __device__ __forceinline__ bool bvh_face(const PmArgs &a, const PmMesh &m, int t, float (&c)[9]) {
-    int id[3];
-    if (t < 0 || t >= m.F || !pm_face_ids(a, (size_t)m.f0 + t, id)) return false;
-    bool finite = true;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        c[k] = a.verts[3 * (size_t)id[k / 3] + k % 3];
-        finite &= fabsf(c[k]) <= 3.0e38f;
-    }
-    return finite;
+    return t >= 0 && t < m.F && pm_face_coords(a, (size_t)m.f0 + t, c);
 }
 
 struct BvhBox { float lo[3], hi[3]; };
@@ -287,7 +279,7 @@ __global__ void __launch_bounds__(BVH_BLOCK) k_bvh_points(BvhArgs b) {
         }
     }
     if (b.evaluated) b.evaluated[(size_t)n * a.P + q] = count;
-    if (best < __builtin_inff()) a.key[(size_t)n * a.P + q] = ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(uint32_t)bi;
+    if (best < __builtin_inff()) scan_put_min(&a.key[(size_t)n * a.P + q], 1, best, bi);  // (one traversal per point: no splits)
 }
 
 // the Morton code of every point inside its mesh's root box, for callers that present the queries in spatial order; a point that is
@@ -299,7 +291,7 @@ __global__ void __launch_bounds__(256) k_bvh_point_codes(BvhArgs b) {
     const PmMesh m = pm_mesh(a, n);
     const float *root = b.boxes + 6 * (bvh_tree(m, n).node0 + 1);
     const float *p = a.points + ((size_t)n * a.P + t) * 3;
-    const bool usable = t < m.len && fabsf(p[0]) <= 3.0e38f && fabsf(p[1]) <= 3.0e38f && fabsf(p[2]) <= 3.0e38f;
+    const bool usable = t < m.len && pm_usable3(p);
     const float x[3] = {p[0], p[1], p[2]}, lo[3] = {root[0], root[1], root[2]}, hi[3] = {root[3], root[4], root[5]};
     b.pkeys[(size_t)n * a.P + t] = usable ? (long long)bvh_morton(x, lo, hi) : (long long)SMIL_BVH_SENTINEL;
 }

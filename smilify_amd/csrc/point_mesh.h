@@ -6,7 +6,7 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "scan.h"
 #include "point_tri.h"
 
 struct PmArgs {
@@ -18,7 +18,7 @@ struct PmArgs {
     const int *lengths;       // (N) or NULL: P
     float4 *table;            // (F_total, 3) {v0, e1, e2} in the mesh's frame
     unsigned int *ext;        // (N) bits of the largest finite |coordinate| of mesh n
-    unsigned long long *key;  // (N, P) or (F_total): {bits of d^2 in the frame, index}, all ones: none
+    unsigned long long *key;  // (N, P) or (F_total): scan.h's key of {d^2 in the frame, index}, minimum flavour
     float *dist2;             // (N, P) or (F_total)
     int *idx;                 // (N, P) face within its mesh or (F_total) point within its cloud, -1: none
     float *bary;              // (N, P, 3) or (F_total, 3)
@@ -50,13 +50,29 @@ __device__ __forceinline__ bool pm_face_ids(const PmArgs &a, size_t j, int (&id)
     return (unsigned)id[0] < (unsigned)a.n_verts && (unsigned)id[1] < (unsigned)a.n_verts && (unsigned)id[2] < (unsigned)a.n_verts;
 }
 
+// three coordinates are usable: none is NaN, inf or above 3e38, whatever a frame does to it
+__device__ __forceinline__ bool pm_usable3(const float *p) { return fabsf(p[0]) <= 3.0e38f && fabsf(p[1]) <= 3.0e38f && fabsf(p[2]) <= 3.0e38f; }
+
+// the nine coordinates of packed face j in the caller's units, or false when the face is not usable (an id out of range, a
+// coordinate that is not usable)
+__device__ __forceinline__ bool pm_face_coords(const PmArgs &a, size_t j, float (&c)[9]) {
+    int id[3];
+    if (!pm_face_ids(a, j, id)) return false;
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        c[k] = a.verts[3 * (size_t)id[k / 3] + k % 3];
+        finite &= fabsf(c[k]) <= 3.0e38f;
+    }
+    return finite;
+}
+
 // the frame of mesh n: coordinates are multiplied by 2^pm_frame (exactly)
 __device__ __forceinline__ int pm_frame(const PmArgs &a, int n) { return -fix_max_exp(a.ext[n]); }
 
-// A point in the frame; NaN (it never wins and nothing wins for it) when a coordinate is not usable: NaN, inf or above 3e38, as for
-// the vertices of a face, whatever the frame does to it.
+// A point in the frame; NaN (it never wins and nothing wins for it) when it is not usable, as for the vertices of a face.
 __device__ __forceinline__ void pm_load_point(const float *p, int sh, float &x, float &y, float &z) {
-    const bool usable = fabsf(p[0]) <= 3.0e38f && fabsf(p[1]) <= 3.0e38f && fabsf(p[2]) <= 3.0e38f;
+    const bool usable = pm_usable3(p);
     const float nan = __builtin_nanf("");
     x = usable ? ldexpf(p[0], sh) : nan; y = usable ? ldexpf(p[1], sh) : nan; z = usable ? ldexpf(p[2], sh) : nan;
 }
@@ -90,8 +106,8 @@ static int pm_fill(PmArgs &a, const char *who, const float *verts, int32_t n_ver
     return SMIL_OK;
 }
 
-// point_mesh.hip: what every forward search stands between.  pm_prepare clears the `n_keys` keys and writes the frame's extent
-// (k_pm_extent) and the face table in the frame (k_pm_table); pm_finish writes the outputs of `rows` queries per mesh from the keys
-// (k_pm_finish, float64).
+// point_mesh.hip: what every forward search stands between.  pm_prepare clears the `n_keys` keys (0: the caller uses none) and
+// writes the frame's extent (k_pm_extent) and the face table in the frame (k_pm_table); pm_finish writes the outputs of `rows`
+// queries per mesh from the keys (k_pm_finish, float64).
 int pm_prepare(PmArgs &a, int max_faces, size_t n_keys, hipStream_t stream);
 int pm_finish(PmArgs &a, int rows, hipStream_t stream);

@@ -14,18 +14,18 @@
 //                   < the running minimum, so it never wins.
 //  * k_pm_points    points -> faces.  lane = one point; face tiles stream through LDS and every lane reads the same face (three
 //                   ds_read_b128 broadcasts against ~110 VALU instructions per point).  Running minimum of the float32 squared
-//                   distance with a strict <.  The face range may be split over blockIdx.y; the splits merge through a 64-bit atomicMin
-//                   of {bits of d^2, face}: d^2 >= 0, so the bits order like the values, the result does not depend on the order
-//                   and a tie goes to the smaller face index, as one sequential scan gives (k_chamfer_nn's merge, mesh3d.hip).
+//                   distance with a strict <.  The face range may be split over blockIdx.y; the splits merge in the point's key,
+//                   minimum flavour: a tie goes to the smaller face index, as one sequential scan gives.  The key, the split's
+//                   range and count and the staging between two barriers are scan.h's, here and in the next two.
 //  * k_pm_faces     faces -> points: the same device function with the roles swapped.  lane = one face (its table entry in registers),
 //                   the cloud's points stream through LDS in the frame, the point range may be split, the same merge.
 //  * k_pm_winding   the generalised winding number of every point (Jacobson et al. 2013): the sum over ALL faces of the signed solid
-//                   angle Omega_f / (4 pi), by van Oosterom & Strackee's formula in float32 in the frame.  The loop of k_pm_points:
-//                   lane = point, face tiles broadcast from LDS.  A pair whose det is +-0 adds exactly 0 (a degenerate face, a point
-//                   in the face's plane or on a vertex).  Every pair's value (|.| <= 0.5) goes to int64 fixed point whose unit follows
-//                   the mesh's face count and is added as an integer, in the lane and, when the faces are split, with one 64-bit
-//                   atomicAdd per point and split: two calls, every split count and every order of the faces give the same bits.
-//                   k_pm_winding_finish converts once to float32; a padded or unusable point gets NaN.
+//                   angle Omega_f / (4 pi), by van Oosterom & Strackee's formula in float32 in the frame.  k_pm_points' prologue and
+//                   loop (pm_points_over_faces) around another per-face body.  A pair whose det is +-0 adds exactly 0 (a degenerate
+//                   face, a point in the face's plane or on a vertex).  Every pair's value (|.| <= 0.5) goes to int64 fixed point
+//                   whose unit follows the mesh's face count and is added as an integer, in the lane and, when the faces are split,
+//                   with one 64-bit atomicAdd per point and split: two calls, every split count and every order of the faces give
+//                   the same bits.  k_pm_winding_finish converts once to float32; a padded or unusable point gets NaN.
 //  * k_pm_finish    thread per query (point or face): the winner's closest point once more in float64 from the float32 inputs (the
 //                   float32 search decides WHICH, the value is the float64 formula's, rounded once), the barycentrics and the index.
 //                   No winner (a non-finite or padded point, a mesh without a face that can win, an empty cloud): +inf, -1, 0.
@@ -71,72 +71,58 @@ __global__ void __launch_bounds__(256) k_pm_table(PmArgs a) {
     const int sh = pm_frame(a, n);
     const float nan = __builtin_nanf("");
     float4 v0 = make_float4(nan, nan, nan, 0.f), e1 = make_float4(0.f, 0.f, 0.f, 0.f), e2 = e1;
-    int id[3];
-    if (pm_face_ids(a, j, id)) {
-        float c[9];
-        bool finite = true;
+    float c[9];
+    if (pm_face_coords(a, j, c)) {  // (the .w slots: n = e1 x e2 for k_pm_winding; the distance kernels do not read them)
 #pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            const float x = a.verts[3 * (size_t)id[k / 3] + k % 3];
-            finite &= fabsf(x) <= 3.0e38f;
-            c[k] = ldexpf(x, sh);
-        }
-        if (finite) {  // (the .w slots: n = e1 x e2 for k_pm_winding; the distance kernels do not read them)
-            const float ux = c[3] - c[0], uy = c[4] - c[1], uz = c[5] - c[2], vx = c[6] - c[0], vy = c[7] - c[1], vz = c[8] - c[2];
-            v0 = make_float4(c[0], c[1], c[2], uy * vz - uz * vy);
-            e1 = make_float4(ux, uy, uz, uz * vx - ux * vz);
-            e2 = make_float4(vx, vy, vz, ux * vy - uy * vx);
-        }
+        for (int k = 0; k < 9; ++k) c[k] = ldexpf(c[k], sh);
+        const float ux = c[3] - c[0], uy = c[4] - c[1], uz = c[5] - c[2], vx = c[6] - c[0], vy = c[7] - c[1], vz = c[8] - c[2];
+        v0 = make_float4(c[0], c[1], c[2], uy * vz - uz * vy);
+        e1 = make_float4(ux, uy, uz, uz * vx - ux * vz);
+        e2 = make_float4(vx, vy, vz, ux * vy - uy * vx);
     }
     a.table[3 * j] = v0;
     a.table[3 * j + 1] = e1;
     a.table[3 * j + 2] = e2;
 }
 
-__device__ __forceinline__ void pm_put_key(const PmArgs &a, size_t at, float best, int bi) {
-    if (!(best < __builtin_inff())) return;  // nothing won in this split
-    const unsigned long long kv = ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(uint32_t)bi;
-    if (a.splits == 1) a.key[at] = kv;
-    else atomicMin(&a.key[at], kv);
-}
-
-// rows [begin, end) of `count` rows that split blockIdx.y of a.splits takes, in whole tiles
-__device__ __forceinline__ void pm_split_range(const PmArgs &a, int count, int &begin, int &end) {
-    const int chunk = ((count + a.splits - 1) / a.splits + PM_TILE - 1) / PM_TILE * PM_TILE;
-    begin = (int)min((long long)blockIdx.y * chunk, (long long)count);
-    end = min(count, begin + chunk);
+// What k_pm_points and k_pm_winding share.  Lane = point q of mesh n's cloud, in the frame; face(px, py, pz, f, v0, e1, e2) for
+// every face f of the split blockIdx.y, from the tile.  `at`: the point's row in the (N, P) arrays; false: the lane has no point
+// (a lane behind the cloud's end repeats its last point and writes nothing), or the workgroup has no points or no faces.
+template <class Face>
+__device__ __forceinline__ bool pm_points_over_faces(const PmArgs &a, int n, const PmMesh &m, float4 *tile, size_t &at, Face face) {
+    const int q = blockIdx.x * PM_BLOCK + threadIdx.x;
+    if ((int)(blockIdx.x * PM_BLOCK) >= m.len) return false;  // (block-uniform, as the next)
+    int f_begin, f_end;
+    scan_split_range(m.F, a.splits, PM_TILE, f_begin, f_end);
+    if (f_begin >= f_end) return false;
+    const int sh = pm_frame(a, n);
+    const float *Q = a.points + (size_t)n * a.P * 3;
+    float px, py, pz;
+    pm_load_point(Q + 3 * (size_t)min(q, m.len - 1), sh, px, py, pz);
+    for (int f0 = f_begin; f0 < f_end; f0 += PM_TILE) {  // (scan_tiles written out: one lambda inside another costs 0.3 % and 3.5 %)
+        const int cnt = min(PM_TILE, f_end - f0);
+        scan_stage(tile, ScanStageRows3<PM_BLOCK>{a.table + 3 * (size_t)m.f0}, f0, cnt);
+        for (int j = 0; j < cnt; ++j) face(px, py, pz, f0 + j, tile[3 * j], tile[3 * j + 1], tile[3 * j + 2]);
+    }
+    at = (size_t)n * a.P + q;
+    return q < m.len;
 }
 
 __global__ void __launch_bounds__(PM_BLOCK) k_pm_points(PmArgs a) {
     __shared__ float4 tile[3 * PM_TILE];
     const int n = blockIdx.z;
     const PmMesh m = pm_mesh(a, n);
-    const int q = blockIdx.x * PM_BLOCK + threadIdx.x;
-    if ((int)(blockIdx.x * PM_BLOCK) >= m.len) return;  // (block-uniform, as the next)
-    int f_begin, f_end;
-    pm_split_range(a, m.F, f_begin, f_end);
-    if (f_begin >= f_end) return;
-    const int sh = pm_frame(a, n);
-    const float *Q = a.points + (size_t)n * a.P * 3;
-    float px, py, pz;  // (a lane behind the cloud's end repeats its last point and writes nothing)
-    pm_load_point(Q + 3 * (size_t)min(q, m.len - 1), sh, px, py, pz);
     float best = __builtin_inff();
     int bi = 0x7FFFFFFF;
-    const float4 *table = a.table + 3 * (size_t)m.f0;
-    for (int f0 = f_begin; f0 < f_end; f0 += PM_TILE) {
-        const int cnt = min(PM_TILE, f_end - f0);
-        __syncthreads();
-        for (int i = threadIdx.x; i < 3 * cnt; i += PM_BLOCK) tile[i] = table[3 * (size_t)f0 + i];
-        __syncthreads();
-        for (int j = 0; j < cnt; ++j) {
-            const float4 v0 = tile[3 * j], e1 = tile[3 * j + 1], e2 = tile[3 * j + 2];
-            const TriPoint<float> r = closest_on_triangle<float>(px - v0.x, py - v0.y, pz - v0.z, e1.x, e1.y, e1.z, e2.x, e2.y, e2.z);
-            const bool take = r.dist2 < best;
-            best = take ? r.dist2 : best;
-            bi = take ? f0 + j : bi;
-        }
-    }
-    if (q < m.len) pm_put_key(a, (size_t)n * a.P + q, best, bi);
+    size_t at;
+    const auto face = [&](float px, float py, float pz, int f, const float4 &v0, const float4 &e1, const float4 &e2) {
+        const TriPoint<float> r = closest_on_triangle<float>(px - v0.x, py - v0.y, pz - v0.z, e1.x, e1.y, e1.z, e2.x, e2.y, e2.z);
+        const bool take = r.dist2 < best;
+        best = take ? r.dist2 : best;
+        bi = take ? f : bi;
+    };
+    // (+inf: nothing won in this split)
+    if (pm_points_over_faces(a, n, m, tile, at, face) && best < __builtin_inff()) scan_put_min(&a.key[at], a.splits, best, bi);
 }
 
 __global__ void __launch_bounds__(PM_BLOCK) k_pm_faces(PmArgs a) {
@@ -146,7 +132,7 @@ __global__ void __launch_bounds__(PM_BLOCK) k_pm_faces(PmArgs a) {
     const int t = blockIdx.x * PM_BLOCK + threadIdx.x;
     if ((int)(blockIdx.x * PM_BLOCK) >= m.F) return;  // (block-uniform, as the next)
     int p_begin, p_end;
-    pm_split_range(a, m.len, p_begin, p_end);
+    scan_split_range(m.len, a.splits, PM_TILE, p_begin, p_end);
     if (p_begin >= p_end) return;
     const int sh = pm_frame(a, n);
     const size_t j = (size_t)m.f0 + min(t, m.F - 1);
@@ -154,15 +140,16 @@ __global__ void __launch_bounds__(PM_BLOCK) k_pm_faces(PmArgs a) {
     const float *Q = a.points + (size_t)n * a.P * 3;
     float best = __builtin_inff();
     int bi = 0x7FFFFFFF;
-    for (int p0 = p_begin; p0 < p_end; p0 += PM_TILE) {
-        const int cnt = min(PM_TILE, p_end - p0);
-        __syncthreads();
+    const auto stage = [&](float4 *tile, int p0, int cnt) {  // ScanStageXyz through pm_load_point: the points in the frame
         if ((int)threadIdx.x < cnt) {
             float x, y, z;
             pm_load_point(Q + 3 * (size_t)(p0 + threadIdx.x), sh, x, y, z);
             tile[threadIdx.x] = make_float4(x, y, z, 0.f);
         }
-        __syncthreads();
+    };
+    for (int p0 = p_begin; p0 < p_end; p0 += PM_TILE) {  // (scan_tiles written out: as a lambda the body costs 11 % of the time)
+        const int cnt = min(PM_TILE, p_end - p0);
+        scan_stage(tile, stage, p0, cnt);
 #pragma unroll 2
         for (int i = 0; i < cnt; ++i) {
             const float4 p = tile[i];
@@ -172,7 +159,7 @@ __global__ void __launch_bounds__(PM_BLOCK) k_pm_faces(PmArgs a) {
             bi = take ? p0 + i : bi;
         }
     }
-    if (t < m.F) pm_put_key(a, (size_t)m.f0 + t, best, bi);
+    if (t < m.F && best < __builtin_inff()) scan_put_min(&a.key[(size_t)m.f0 + t], a.splits, best, bi);  // (+inf: as in k_pm_points)
 }
 
 // The closest point of packed face j to point p of mesh n's cloud in float64, from the float32 inputs.  false: the pair does not
@@ -183,9 +170,8 @@ __device__ __forceinline__ bool pm_pair64(const PmArgs &a, int n, const PmMesh &
     if (!pm_face_ids(a, (size_t)m.f0 + face, id)) return false;
     const float *p = a.points + ((size_t)n * a.P + point) * 3;
     const float *v0 = a.verts + 3 * (size_t)id[0], *v1 = a.verts + 3 * (size_t)id[1], *v2 = a.verts + 3 * (size_t)id[2];
-    bool usable = true;  // (the search never pairs these, a hand-made record of the backward may)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) usable &= fabsf(p[k]) <= 3.0e38f && fabsf(v0[k]) <= 3.0e38f && fabsf(v1[k]) <= 3.0e38f && fabsf(v2[k]) <= 3.0e38f;
+    bool usable = pm_usable3(p);  // (the search never pairs these, a hand-made record of the backward may)
+    usable &= pm_usable3(v0); usable &= pm_usable3(v1); usable &= pm_usable3(v2);
     if (!usable) return false;
     const double e1[3] = {(double)v1[0] - v0[0], (double)v1[1] - v0[1], (double)v1[2] - v0[2]};
     const double e2[3] = {(double)v2[0] - v0[0], (double)v2[1] - v0[1], (double)v2[2] - v0[2]};
@@ -208,11 +194,11 @@ __global__ void __launch_bounds__(256) k_pm_finish(PmArgs a) {
     size_t at;
     if (!pm_query(a, n, m, t, at)) return;
     const unsigned long long kv = a.key[at];
-    const int other = (int)(uint32_t)(kv & 0xFFFFFFFFull);
+    const int other = scan_key_index(kv);
     TriPoint<double> r;
     double e[3];
     int id[3];
-    const bool none = kv == ~0ull || !pm_pair64(a, n, m, a.by_face ? t : other, a.by_face ? other : t, r, e, id);
+    const bool none = kv == SCAN_KEY_NONE || !pm_pair64(a, n, m, a.by_face ? t : other, a.by_face ? other : t, r, e, id);
     a.dist2[at] = none ? __builtin_inff() : (float)r.dist2;
     a.idx[at] = none ? -1 : other;
     a.bary[3 * at] = none ? 0.f : (float)r.b0;
@@ -243,26 +229,13 @@ __global__ void __launch_bounds__(PM_BLOCK) k_pm_winding(PmArgs a) {
     __shared__ float4 tile[3 * PM_TILE];
     const int n = blockIdx.z;
     const PmMesh m = pm_mesh(a, n);
-    const int q = blockIdx.x * PM_BLOCK + threadIdx.x;
-    if ((int)(blockIdx.x * PM_BLOCK) >= m.len) return;  // (block-uniform, as the next)
-    int f_begin, f_end;
-    pm_split_range(a, m.F, f_begin, f_end);
-    if (f_begin >= f_end) return;
-    const int sh = pm_frame(a, n), fix = pm_winding_fix(m);
-    const float *Q = a.points + (size_t)n * a.P * 3;
-    float px, py, pz;  // (a lane behind the cloud's end repeats its last point and writes nothing)
-    pm_load_point(Q + 3 * (size_t)min(q, m.len - 1), sh, px, py, pz);
+    const int fix = pm_winding_fix(m);
     long long sum = 0;
-    const float4 *table = a.table + 3 * (size_t)m.f0;
-    for (int f0 = f_begin; f0 < f_end; f0 += PM_TILE) {
-        const int cnt = min(PM_TILE, f_end - f0);
-        __syncthreads();
-        for (int i = threadIdx.x; i < 3 * cnt; i += PM_BLOCK) tile[i] = table[3 * (size_t)f0 + i];
-        __syncthreads();
-        for (int j = 0; j < cnt; ++j)
-            sum += __double2ll_rn(ldexp((double)pm_face_angle(px, py, pz, tile[3 * j], tile[3 * j + 1], tile[3 * j + 2]), fix));
-    }
-    if (q < m.len) atomicAdd((unsigned long long *)&a.acc_p[(size_t)n * a.P + q], (unsigned long long)sum);
+    size_t at;
+    const auto face = [&](float px, float py, float pz, int, const float4 &v0, const float4 &e1, const float4 &e2) {
+        sum += __double2ll_rn(ldexp((double)pm_face_angle(px, py, pz, v0, e1, e2), fix));
+    };
+    if (pm_points_over_faces(a, n, m, tile, at, face)) atomicAdd((unsigned long long *)&a.acc_p[at], (unsigned long long)sum);
 }
 
 __global__ void __launch_bounds__(256) k_pm_winding_finish(PmArgs a) {
@@ -270,8 +243,7 @@ __global__ void __launch_bounds__(256) k_pm_winding_finish(PmArgs a) {
     if (t >= a.P) return;
     const PmMesh m = pm_mesh(a, n);
     const size_t at = (size_t)n * a.P + t;
-    const float *p = a.points + 3 * at;
-    const bool usable = t < m.len && fabsf(p[0]) <= 3.0e38f && fabsf(p[1]) <= 3.0e38f && fabsf(p[2]) <= 3.0e38f;
+    const bool usable = t < m.len && pm_usable3(a.points + 3 * at);
     a.winding[at] = usable ? fix_read(a.acc_p[at], pm_winding_fix(m)) : __builtin_nanf("");
 }
 
@@ -361,15 +333,12 @@ extern "C" size_t smil_point_mesh_workspace_bytes(int32_t N, int32_t F_total, in
     return pm_sizes_ok(N, F_total, P, n_verts) ? pm_layout(N, F_total, P, n_verts, nullptr, a) : 0;
 }
 
-// splits of `cols` candidates for `qblocks` workgroups of queries per mesh: the caller's, or enough workgroups for the whole GPU
-// (>= 2048) while every split still streams >= 2 tiles
-static int pm_splits(int32_t splits, int qblocks, int cols, int N) {
-    const int max_split = std::max(1, cols / (2 * PM_TILE));
-    return splits > 0 ? splits : std::max(1, std::min(std::min(max_split, 65535), ceil_div(2048, qblocks * N)));
-}
+// splits of `cols` candidates for `qblocks` workgroups of queries per mesh: the caller's, or >= 2048 workgroups while every split
+// still streams >= 2 tiles
+static int pm_splits(int32_t splits, int qblocks, int cols, int N) { return scan_splits(splits, qblocks * N, cols, PM_TILE, 2, 2048); }
 
 int pm_prepare(PmArgs &a, int max_faces, size_t n_keys, hipStream_t stream) {
-    SMIL_HIP(hipMemsetAsync(a.key, 0xFF, n_keys * sizeof(unsigned long long), stream));
+    if (n_keys) SMIL_HIP(hipMemsetAsync(a.key, 0xFF, n_keys * sizeof(unsigned long long), stream));
     SMIL_HIP(hipMemsetAsync(a.ext, 0, (size_t)a.N * sizeof(unsigned int), stream));
     hipLaunchKernelGGL(k_pm_extent, dim3(ceil_div(std::max(max_faces, a.P), 256), a.N), dim3(256), 0, stream, a);
     SMIL_LAUNCH_CHECK();
@@ -435,12 +404,9 @@ extern "C" int smil_point_mesh_winding(const float *verts, int32_t n_verts, cons
     a.winding = winding;
     const int qblocks = ceil_div(P, PM_BLOCK);
     a.splits = pm_splits(splits, qblocks, max_faces, N);
-    SMIL_HIP(hipMemsetAsync(a.ext, 0, (size_t)N * sizeof(unsigned int), stream));
     SMIL_HIP(hipMemsetAsync(a.acc_p, 0, (size_t)N * P * sizeof(long long), stream));
-    hipLaunchKernelGGL(k_pm_extent, dim3(ceil_div(std::max(max_faces, P), 256), N), dim3(256), 0, stream, a);
-    SMIL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_pm_table, dim3(ceil_div(max_faces, 256), N), dim3(256), 0, stream, a);
-    SMIL_LAUNCH_CHECK();
+    const int rc2 = pm_prepare(a, max_faces, 0, stream);  // (no keys: the splits meet in acc_p)
+    if (rc2 != SMIL_OK) return rc2;
     hipLaunchKernelGGL(k_pm_winding, dim3(qblocks, a.splits, N), dim3(PM_BLOCK), 0, stream, a);
     SMIL_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_pm_winding_finish, dim3(ceil_div(P, 256), N), dim3(256), 0, stream, a);

@@ -9,18 +9,15 @@
 //                   same face (three ds_read_b128 broadcasts per face against ~45 VALU instructions per lane: the LDS is a quarter
 //                   busy).  The lane keeps the LARGEST t over its hits and the face it belongs to - the reference takes torch.max of
 //                   the distances, not the nearest hit.  When the rays do not fill the GPU the face range is split over workgroups;
-//                   the splits merge through a 64-bit atomicMax of {bits of t, face}: every hit has t > t_min >= 0, so the bits order
-//                   like the values and the result does not depend on the order (as k_chamfer_nn's merge, mesh3d.hip; equal t: the
-//                   larger face index, as the scan's >= gives).
+//                   the splits merge in the ray's key, maximum flavour: every hit has t > t_min >= 0 (equal t: the larger face
+//                   index, as the scan's >= gives).  The key, the split's range and count and the staging are scan.h's.
 //  * k_ray_reduce   thread per sample, in ray order: the winning face's t once more in float64 (the float32 search decides WHICH face,
 //                   its value is then the float64 formula's rounded to float32: the cancellation in s x e1 no longer shows in the
 //                   result), the thresholds, the cap and the mean (a float64 sum, rounded once).
 //
 // No float atomics, no synchronisation: two calls on the same inputs give the same bits.  There is no BVH or grid: the exact maximum
 // over ALL faces is what the reference computes.
-#include <algorithm>
-
-#include "common.h"
+#include "scan.h"
 
 #define RC_BLOCK 256
 #define RC_TILE 256   // faces staged in LDS per step (12 KB)
@@ -63,8 +60,8 @@ __global__ void __launch_bounds__(RC_BLOCK) k_ray_cast(RayArgs a) {
     const int n_rays = a.S * a.R;
     const int r = blockIdx.x * RC_BLOCK + threadIdx.x;
     const int rc = r < n_rays ? r : n_rays - 1;
-    const int chunk = ((a.F + a.splits - 1) / a.splits + RC_TILE - 1) / RC_TILE * RC_TILE;
-    const int f_begin = blockIdx.y * chunk, f_end = min(a.F, f_begin + chunk);
+    int f_begin, f_end;
+    scan_split_range(a.F, a.splits, RC_TILE, f_begin, f_end);
     if (f_begin >= f_end) return;  // (block-uniform)
     const int s_id = rc / a.R;
     const float ox = a.origins[3 * (size_t)s_id], oy = a.origins[3 * (size_t)s_id + 1], oz = a.origins[3 * (size_t)s_id + 2];
@@ -73,11 +70,9 @@ __global__ void __launch_bounds__(RC_BLOCK) k_ray_cast(RayArgs a) {
     const float t_min = a.t_min;
     float best = 0.f;
     int best_face = 0;
-    for (int f0 = f_begin; f0 < f_end; f0 += RC_TILE) {
+    for (int f0 = f_begin; f0 < f_end; f0 += RC_TILE) {  // (scan_tiles written out: as a lambda the body costs 24 % of the time)
         const int cnt = min(RC_TILE, f_end - f0);
-        __syncthreads();
-        for (int i = threadIdx.x; i < 3 * cnt; i += RC_BLOCK) tile[i] = a.table[3 * (size_t)f0 + i];
-        __syncthreads();
+        scan_stage(tile, ScanStageRows3<RC_BLOCK>{a.table}, f0, cnt);
         const int skip = own - f0;  // the sample's own face within this tile, or out of range
 #pragma unroll 2
         for (int j = 0; j < cnt; ++j) {
@@ -97,11 +92,7 @@ __global__ void __launch_bounds__(RC_BLOCK) k_ray_cast(RayArgs a) {
             best_face = take ? f0 + j : best_face;
         }
     }
-    if (r < n_rays && best > 0.f) {
-        const unsigned long long kv = ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(uint32_t)best_face;
-        if (a.splits == 1) a.key[r] = kv;
-        else atomicMax(&a.key[r], kv);
-    }
+    if (r < n_rays && best > 0.f) scan_put_max(&a.key[r], a.splits, best, best_face);
 }
 
 __global__ void __launch_bounds__(256) k_ray_reduce(RayArgs a) {
@@ -115,7 +106,7 @@ __global__ void __launch_bounds__(256) k_ray_reduce(RayArgs a) {
         const unsigned long long kv = a.key[r];
         float t = -1.0f;
         if (kv) {  // (a key's face passed k_ray_faces' index check: a face with a bad index is never hit)
-            const int *fi = a.faces + 3 * (size_t)(uint32_t)(kv & 0xFFFFFFFFull);
+            const int *fi = a.faces + 3 * (size_t)scan_key_index(kv);
             const float *p0 = a.verts + 3 * (size_t)fi[0], *p1 = a.verts + 3 * (size_t)fi[1], *p2 = a.verts + 3 * (size_t)fi[2];
             const double d[3] = {a.dirs[3 * r], a.dirs[3 * r + 1], a.dirs[3 * r + 2]};
             const double e1[3] = {(double)p1[0] - p0[0], (double)p1[1] - p0[1], (double)p1[2] - p0[2]};
@@ -165,10 +156,8 @@ extern "C" int smil_ray_diameters(const float *verts, int32_t V, const int32_t *
     a.V = V; a.F = F; a.S = S; a.R = R; a.cap = cap;
     a.t_min = t_min; a.d_lo = d_lo; a.d_hi = d_hi;
     a.ray_t = ray_t; a.diam = diam;
-    // face splits: enough workgroups for the whole GPU (>= 2048) while every split still streams >= 4 tiles
     const int rblocks = ceil_div(S * R, RC_BLOCK);
-    const int max_split = std::max(1, F / (4 * RC_TILE));
-    a.splits = std::max(1, std::min(std::min(max_split, 65535), ceil_div(2048, rblocks)));
+    a.splits = scan_splits(0, rblocks, F, RC_TILE, 4, 2048);  // >= 2048 workgroups while every split still streams >= 4 tiles
     SMIL_HIP(hipMemsetAsync(a.key, 0, (size_t)S * R * sizeof(unsigned long long), stream));
     hipLaunchKernelGGL(k_ray_faces, dim3(ceil_div(F, 256)), dim3(256), 0, stream, a);
     SMIL_LAUNCH_CHECK();
