@@ -6,23 +6,18 @@ joints.
 Needs a GPU; writes profiles/align_probe.json (``--out``).  The parent of these kernels has none to compare with: the torch
 composition is the baseline, and the ratios are recorded as they come out.
 
-Every function is one STEP: a child process of its own under its own time limit (``--step-seconds``), so a step that hangs or
-faults ends alone; the parent never opens the device, and after a step that failed it starts no other.
-
-Method (per step): float32 storage.  Both paths are warmed up at both sizes first.  A window is as many back-to-back calls as fill
-``--window-ms`` (3 to 20000 calls, sized from a first window of 3) between two device events, ended by a synchronise; the kernel's and
-the composition's windows ALTERNATE, ``--windows`` of each, and the median and the spread (min, max) of the per-call time are
-recorded.  The figures are times of the whole Python call - argument checks, mask conversion, output allocation, autograd
-bookkeeping and launch latency included: at these sizes they measure launches and the host, not the device.
+Every function is one STEP under its own time limit (``--step-seconds``), and the kernel's and the composition's windows alternate:
+the runner and the method are those of tools/probelib.py.  Here: float32 storage; both paths are warmed up at both sizes first; a
+window holds 3 to 20000 calls, sized from a first window of 3.  The figures include mask conversion and autograd bookkeeping: at
+these sizes they measure launches and the host, not the device.
 
     python3 tools/align_probe.py
 """
 import argparse
-import json
 import os
-import statistics
-import subprocess
 import sys
+
+import probelib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STEPS = ["similarity_transform", "rigid_transform_robust", "pa_mpjpe"]
@@ -51,15 +46,6 @@ def run_step(name):
 
     dev = torch.device("cuda:0")
 
-    def window(fn, calls):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        ev[0].record()
-        for _ in range(calls):
-            fn()
-        ev[1].record()
-        torch.cuda.synchronize()
-        return ev[0].elapsed_time(ev[1]) / calls
-
     def pair_for(B):
         c = cases.regular(B, J, seed=B, weights=None)
         src, dst, mask = c["src"].float().to(dev), c["dst"].float().to(dev), c["mask"].to(dev)
@@ -83,58 +69,25 @@ def run_step(name):
         return lambda: align.pa_mpjpe(src, dst, mask), lambda: ref.pa_mpjpe(src64, dst64, mask)
 
     pairs = {B: dict(zip(("kernel", "torch"), pair_for(B))) for B in args.batches}
-    for pair in pairs.values():  # every shape of the timed windows, before any of them
-        for fn in pair.values():
-            for _ in range(args.warmup):
-                fn()
-    torch.cuda.synchronize()
+    probelib.warm_up([fn for pair in pairs.values() for fn in pair.values()], args.warmup)  # every shape of the timed windows, before any of them
     for B, pair in pairs.items():
-        calls = {who: int(min(20000, max(3, args.window_ms / max(window(fn, 3), 1e-6)))) for who, fn in pair.items()}
-        times = {"kernel": [], "torch": []}
-        for _ in range(args.windows):
-            for who, fn in pair.items():
-                times[who].append(window(fn, calls[who]))
+        times, calls = probelib.alternate(pair, window_ms=args.window_ms, windows=args.windows, first=3, lo=3, hi=20000)
         row = dict(function=name, mode=MODES[name], B=B, J=J, kernel_calls=calls["kernel"], torch_calls=calls["torch"])
         for who, t in times.items():
-            row[f"{who}_ms"] = statistics.median(t)
-            row[f"{who}_ms_min"], row[f"{who}_ms_max"] = min(t), max(t)
+            row.update({f"{who}_{k}": v for k, v in t.items()})
         row["torch_over_kernel"] = row["torch_ms"] / row["kernel_ms"]
-        print("ROW " + json.dumps(row), flush=True)
-    print("DEVICE " + json.dumps(torch.cuda.get_device_name(0)), flush=True)
+        probelib.emit_row(row)
+    probelib.emit_device(torch.cuda.get_device_name(0))
 
 
 if args.step:
     run_step(args.step)
     sys.exit(0)
 
-rows, failed, device = [], [], None
-for step in STEPS:
-    cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--window-ms", str(args.window_ms), "--windows", str(args.windows),
-           "--warmup", str(args.warmup), "--batches"] + [str(b) for b in args.batches]
-    try:
-        done = subprocess.run(cmd, capture_output=True, text=True, timeout=args.step_seconds)
-        status = done.returncode
-        out = done.stdout
-        if status != 0:
-            sys.stderr.write(done.stderr[-2000:])
-    except subprocess.TimeoutExpired:
-        status, out = "time limit", ""
-    if status != 0:
-        failed.append(dict(step=step, status=status))
-        print(f"{step}: failed ({status}); no further step is started", flush=True)
-        break
-    for line in out.splitlines():
-        if line.startswith("ROW "):
-            rows.append(json.loads(line[4:]))
-            print(line[4:], flush=True)
-        elif line.startswith("DEVICE "):
-            device = json.loads(line[7:])
-
-result = dict(device=device, dtype="float32", baseline="tests/align_ref.py on the device (float64, torch.linalg.svd, one problem at a time)",
-              window_ms=args.window_ms, windows=args.windows, warmup=args.warmup, failed=failed,
-              not_measured=STEPS[len(rows) // max(1, len(args.batches)):], rows=rows)
-os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "w") as f:
-    json.dump(result, f, indent=1)
-print(f"wrote {args.out}")
+forward = ["--window-ms", str(args.window_ms), "--windows", str(args.windows), "--warmup", str(args.warmup), "--batches"] + [str(b) for b in args.batches]
+rows, failed, device, finished = probelib.run_steps(os.path.abspath(__file__), STEPS, forward, args.step_seconds)
+probelib.write_result(args.out, dict(device=device, dtype="float32",
+                                     baseline="tests/align_ref.py on the device (float64, torch.linalg.svd, one problem at a time)",
+                                     window_ms=args.window_ms, windows=args.windows, warmup=args.warmup, failed=failed,
+                                     not_measured=STEPS[finished:], rows=rows))
 sys.exit(1 if failed else 0)

@@ -19,6 +19,7 @@ import os
 import sys
 
 import numpy as np
+import probelib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -32,17 +33,16 @@ ap.add_argument("--long", type=int, default=4099, help="frames of the one long c
 args = ap.parse_args()
 
 if args.compare:
-    a_dir, b_dir = args.compare
-    names_a, names_b = sorted(os.listdir(a_dir)), sorted(os.listdir(b_dir))
-    bad = [("only in one directory", n) for n in sorted(set(names_a) ^ set(names_b))]
-    for n in sorted(set(names_a) & set(names_b)):
-        a, b = np.load(os.path.join(a_dir, n)), np.load(os.path.join(b_dir, n))
-        if not (a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))):
-            bad.append((n, float(np.nanmax(np.abs(a.astype(np.float64) - b.astype(np.float64)))) if a.shape == b.shape else "shape"))
-    print(f"{len(names_a)} / {len(names_b)} arrays, bit for bit: {len(bad)} differ")
+    a, b = (probelib.load_arrays(d) for d in args.compare)
+    only, changed = probelib.differing(a, b)
+    bad = [("only in one directory", n + ".npy") for n in only]
+    for n in changed:
+        x, y = a[n], b[n]
+        bad.append((n + ".npy", float(np.nanmax(np.abs(x.astype(np.float64) - y.astype(np.float64)))) if x.shape == y.shape else "shape"))
+    print(f"{len(a)} / {len(b)} arrays, bit for bit: {len(bad)} differ")
     for x in bad:
         print("DIFFERS", x)
-    sys.exit(1 if bad or not names_a else 0)
+    sys.exit(1 if bad or not a else 0)
 
 import torch  # noqa: E402
 

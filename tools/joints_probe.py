@@ -8,19 +8,17 @@
     chunks, one optimiser step per iteration.  The two do not minimise the same number (window means against a pooled mean): the
     baseline stands for the work such an iteration costs, not for its value.
 
-Needs a GPU; writes profiles/joints_probe.json (``--out``).  Method: every path is warmed up at every size; a window is as many
-back-to-back calls as fill ``--window-ms`` (2 to 500, sized from a first window of 2) between two device events, ended by a
-synchronise; the two paths' windows ALTERNATE, ``--windows`` of each; median, min and max of the per-call time are recorded.  The times
-are those of the whole Python call (allocation, autograd bookkeeping and launches included).
+Needs a GPU; writes profiles/joints_probe.json (``--out``).  Method: that of tools/probelib.py, the two paths' windows alternating.
+Here: a window holds 2 to 500 calls, sized from a first window of 2.
 
     python3 tools/joints_probe.py
 """
 import argparse
 import json
 import os
-import statistics
 import sys
 
+import probelib
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,28 +40,11 @@ dev = torch.device("cuda:0")
 MODELS = {"stick": "SMILy_STICK.npz", "mouse": "SMILy_Mouse_static_joints.npz"}
 
 
-def window(fn, calls):
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    ev[0].record()
-    for _ in range(calls):
-        fn()
-    ev[1].record()
-    torch.cuda.synchronize()
-    return ev[0].elapsed_time(ev[1]) / calls
-
-
 def compare(row, pair):
-    for fn in pair.values():
-        for _ in range(args.warmup):
-            fn()
-    torch.cuda.synchronize()
-    calls = {who: int(min(500, max(2, args.window_ms / max(window(fn, 2), 1e-6)))) for who, fn in pair.items()}
-    times = {who: [] for who in pair}
-    for _ in range(args.windows):
-        for who, fn in pair.items():
-            times[who].append(window(fn, calls[who]))
+    probelib.warm_up(pair.values(), args.warmup)
+    times, calls = probelib.alternate(pair, window_ms=args.window_ms, windows=args.windows, first=2, lo=2, hi=500)
     for who, t in times.items():
-        row[f"{who}_ms"], row[f"{who}_ms_min"], row[f"{who}_ms_max"], row[f"{who}_calls"] = statistics.median(t), min(t), max(t), calls[who]
+        row.update({f"{who}_{k}": v for k, v in t.items()}, **{f"{who}_calls": calls[who]})
     row["baseline_over_joints"] = row["baseline_ms"] / row["joints_ms"]
     row["peak_memory_mb"] = torch.cuda.max_memory_allocated() / 2 ** 20
     print(json.dumps(row), flush=True)
@@ -117,9 +98,5 @@ for name, file in MODELS.items():
         del fitter, opt, p_theta, p_trans, target
         torch.cuda.empty_cache()
 
-result = dict(device=torch.cuda.get_device_name(0), library=_lib.load().smil_version().decode(), window_ms=args.window_ms, windows=args.windows,
-              warmup=args.warmup, rows=rows)
-os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "w") as f:
-    json.dump(result, f, indent=1)
-print(f"wrote {args.out}")
+probelib.write_result(args.out, dict(device=torch.cuda.get_device_name(0), library=_lib.load().smil_version().decode(), window_ms=args.window_ms,
+                                     windows=args.windows, warmup=args.warmup, rows=rows))

@@ -7,10 +7,9 @@
     skins every vertex of every frame to regress the joints.
 
 Rows: STICK at 1 and 4 views, the mouse at 18 views, at every ``--sizes`` frame count (a path that runs out of memory at a size is
-recorded as such).  Needs a GPU; writes profiles/kp2d_probe.json (``--out``).  Method (tools/joints_probe.py): every path is warmed up at
-every size; a window is as many back-to-back calls as fill ``--window-ms`` (2 to 500, sized from a first window of 2) between two
-device events, ended by a synchronise; the paths' windows ALTERNATE, ``--windows`` of each; median, min and max of the per-call time
-are recorded, and the peak memory one call of (a) and of (c) allocates beyond what is resident (``resident_mb``: both fitters).  The times are those of the whole Python call.
+recorded as such).  Needs a GPU; writes profiles/kp2d_probe.json (``--out``).  Method: that of tools/probelib.py, the three paths'
+windows alternating.  Here: a window holds 2 to 500 calls, sized from a first window of 2; also recorded is the peak memory one call
+of (a) and of (c) allocates beyond what is resident (``resident_mb``: both fitters).
 
     python3 tools/kp2d_probe.py
 """
@@ -18,9 +17,9 @@ import argparse
 import json
 import math
 import os
-import statistics
 import sys
 
+import probelib
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -45,28 +44,11 @@ SHAPES = [("stick", "SMILy_STICK.npz", 1), ("stick", "SMILy_STICK.npz", 4), ("mo
 W_JOINT, W_TEMP, WINDOW, LR = 25.0, 500.0, 10, 5e-3
 
 
-def window(fn, calls):
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    ev[0].record()
-    for _ in range(calls):
-        fn()
-    ev[1].record()
-    torch.cuda.synchronize()
-    return ev[0].elapsed_time(ev[1]) / calls
-
-
 def compare(row, paths):
-    for fn in paths.values():
-        for _ in range(args.warmup):
-            fn()
-    torch.cuda.synchronize()
-    calls = {who: int(min(500, max(2, args.window_ms / max(window(fn, 2), 1e-6)))) for who, fn in paths.items()}
-    times = {who: [] for who in paths}
-    for _ in range(args.windows):
-        for who, fn in paths.items():
-            times[who].append(window(fn, calls[who]))
+    probelib.warm_up(paths.values(), args.warmup)
+    times, calls = probelib.alternate(paths, window_ms=args.window_ms, windows=args.windows, first=2, lo=2, hi=500)
     for who, t in times.items():
-        row[f"{who}_ms"], row[f"{who}_ms_min"], row[f"{who}_ms_max"], row[f"{who}_calls"] = statistics.median(t), min(t), max(t), calls[who]
+        row.update({f"{who}_{k}": v for k, v in t.items()}, **{f"{who}_calls": calls[who]})
     return row
 
 
@@ -137,9 +119,5 @@ for name, file, views in SHAPES:
         a = c = smal = opt = p_theta = p_trans = data = target = tgt64 = None
         torch.cuda.empty_cache()
 
-result = dict(device=torch.cuda.get_device_name(0), library=_lib.load().smil_version().decode(), window_ms=args.window_ms, windows=args.windows,
-              warmup=args.warmup, rows=rows)
-os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "w") as f:
-    json.dump(result, f, indent=1)
-print(f"wrote {args.out}")
+probelib.write_result(args.out, dict(device=torch.cuda.get_device_name(0), library=_lib.load().smil_version().decode(), window_ms=args.window_ms,
+                                     windows=args.windows, warmup=args.warmup, rows=rows))

@@ -9,8 +9,9 @@ project.hip that must not change a single bit (kernels whose instruction stream 
 Cases: STICK, the two synthetic models (regressed / static joints), the pose-blend model of tests/golden/lbs_posedirs.npz and
 the mouse; B = 5 (the 1024-thread fused kernels, one frame per workgroup) and B = 300 (the 512-thread ones, workgroups walking
 several frames); 1 and 3 views; shared and per-frame betas; the translation added before and after the joint regression.
-Arrays above four million elements are written as the SHA-256 of their bits.  ``fov_img`` (float atomics in an order that
-varies from run to run) is compared to 2e-5 of its largest entry, everything else with ``np.array_equal``.
+Arrays above four million elements are written as the SHA-256 of their bits.  Everything is compared byte for byte
+(tools/probelib.py); a ``fov_img`` that differs (float atomics in an order that varies from run to run) passes within 2e-5 of its
+largest entry, and is named.
 """
 import argparse
 import hashlib
@@ -18,6 +19,7 @@ import os
 import sys
 
 import numpy as np
+import probelib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -31,25 +33,23 @@ ap.add_argument("--views", default="1,3")
 args = ap.parse_args()
 
 if args.compare:
-    a_dir, b_dir = args.compare
-    names_a, names_b = sorted(os.listdir(a_dir)), sorted(os.listdir(b_dir))
-    bad = [("only in one directory", n) for n in sorted(set(names_a) ^ set(names_b))]
-    n_fov = 0
-    for n in sorted(set(names_a) & set(names_b)):
-        a, b = np.load(os.path.join(a_dir, n)), np.load(os.path.join(b_dir, n))
+    a, b = (probelib.load_arrays(d) for d in args.compare)
+    only, changed = probelib.differing(a, b)
+    bad, took = [("only in one directory", n + ".npy") for n in only], []
+    for n in changed:
+        x, y = a[n], b[n]
         if "fov_img" in n:  # float atomics
-            n_fov += 1
-            err = float(np.abs(a - b).max() / (np.abs(b).max() + 1e-30)) if a.shape == b.shape else np.inf
-            if not err < 2e-5:
-                bad.append((n, err))
-        elif not (a.dtype == b.dtype and np.array_equal(a.view(np.uint32) if a.dtype == np.float32 else a,
-                                                         b.view(np.uint32) if b.dtype == np.float32 else b)):
-            d = np.abs(a.astype(np.float64) - b.astype(np.float64))
-            bad.append((n, float(np.nanmax(d)) if a.shape == b.shape else "shape"))
-    print(f"{len(names_a)} / {len(names_b)} arrays, {n_fov} of them fov_img (2e-5), the others bit for bit: {len(bad)} differ")
+            err = float(np.abs(x - y).max() / (np.abs(y).max() + 1e-30)) if x.shape == y.shape else np.inf
+            (took if err < 2e-5 else bad).append((n + ".npy", err))
+        else:
+            bad.append((n + ".npy", float(np.nanmax(np.abs(x.astype(np.float64) - y.astype(np.float64)))) if x.shape == y.shape else "shape"))
+    n_fov = sum("fov_img" in n for n in set(a) & set(b))
+    print(f"{len(a)} / {len(b)} arrays, {n_fov} of them fov_img (2e-5), the others bit for bit: {len(bad)} differ")
+    for x in took:
+        print("WITHIN 2e-5", x)
     for x in bad:
         print("DIFFERS", x)
-    sys.exit(1 if bad else 0)
+    sys.exit(1 if bad or not a else 0)
 
 import torch  # noqa: E402
 

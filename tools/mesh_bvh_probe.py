@@ -8,21 +8,17 @@ the queries in the caller's order and in Morton order), ``build`` (MeshBVH(meshe
 ``refit``.  Also recorded: the mean and largest number of leaf faces evaluated per point, whether all three answers have equal bits,
 and the number of queries after which a build has paid for itself, build / (brute force - bvh).
 
-Needs a GPU; writes profiles/mesh_bvh_probe.json (``--out``).  Every workload is one STEP: a child process of its own under its own
-time limit, so a step that hangs or faults ends alone; the parent never opens the device, and after a step that failed it starts no
-other.  Method (per step), that of tools/point_mesh_probe.py: ``--warmup`` calls of everything first; a window is as many back-to-back
-calls as fill ``--window-ms`` (3 to 2000, sized from a first window of 3) between two device events, ended by a synchronise; the
-windows of the variants ALTERNATE, ``--windows`` of each, and the median and the spread (min, max) of the per-call time are recorded.
-Nothing here is asserted by a test.
+Needs a GPU; writes profiles/mesh_bvh_probe.json (``--out``).  Every workload is one STEP under its own time limit
+(``--step-seconds``), and the variants' windows alternate: the runner and the method are those of tools/probelib.py.  Here: a window
+holds 3 to 2000 calls, sized from a first window of 3.  Nothing here is asserted by a test.
 
     python3 tools/mesh_bvh_probe.py
 """
 import argparse
-import json
 import os
-import statistics
-import subprocess
 import sys
+
+import probelib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STEPS = ["model_3000", "hull_model_verts", "hull_100k"]
@@ -47,15 +43,6 @@ def run_step(name):
     from smilify_amd.mesh3d import Meshes
 
     dev = torch.device("cuda:0")
-
-    def window(fn, calls):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        ev[0].record()
-        for _ in range(calls):
-            fn()
-        ev[1].record()
-        torch.cuda.synchronize()
-        return ev[0].elapsed_time(ev[1]) / calls
 
     def hull_mesh(G):  # a disc seen by 18 cameras, carved (tools/point_mesh_probe.py's scene)
         S, views = 256, 18
@@ -96,19 +83,11 @@ def run_step(name):
                     bvh_sorted=lambda: trees[True].closest_points(points),
                     build=lambda: mesh3d.MeshBVH(meshes),
                     refit=lambda: spare.refit(meshes))
-    for fn in variants.values():
-        for _ in range(args.warmup):
-            fn()
-    torch.cuda.synchronize()
-    calls = {who: int(min(2000, max(3, args.window_ms / max(window(fn, 3), 1e-6)))) for who, fn in variants.items()}
-    times = {who: [] for who in variants}
-    for _ in range(args.windows):
-        for who, fn in variants.items():
-            times[who].append(window(fn, calls[who]))
+    probelib.warm_up(variants.values(), args.warmup)
+    times, calls = probelib.alternate(variants, window_ms=args.window_ms, windows=args.windows, first=3, lo=3, hi=2000)
     row = dict(workload=name, points=P, faces=F, verts=int(verts.shape[0]), leaf_size=int(engine._lib.BVH_LEAF), calls=calls)
-    for who, ts in times.items():
-        row[f"{who}_ms"] = statistics.median(ts)
-        row[f"{who}_ms_min"], row[f"{who}_ms_max"] = min(ts), max(ts)
+    for who, t in times.items():
+        row.update({f"{who}_{k}": v for k, v in t.items()})
     for who in ("bvh_unsorted", "bvh_sorted"):
         row[f"brute_force_over_{who}"] = row["brute_force_ms"] / row[f"{who}_ms"]
         # beyond the spread: the slowest window of the hierarchy is still faster than the fastest of the brute force
@@ -119,42 +98,19 @@ def run_step(name):
     row["evaluated_faces_per_point_mean"], row["evaluated_faces_per_point_max"] = float(count.mean()), int(count.max())
     want = variants["brute_force"]()
     row["equal_bits"] = all(torch.equal(a, b) for who in ("bvh_unsorted", "bvh_sorted") for a, b in zip(variants[who](), want))
-    print("ROW " + json.dumps(row), flush=True)
-    print("DEVICE " + json.dumps([torch.cuda.get_device_name(0), engine._lib.load().smil_version().decode()]), flush=True)
+    probelib.emit_row(row)
+    probelib.emit_device([torch.cuda.get_device_name(0), engine._lib.load().smil_version().decode()])
 
 
 if args.step:
     run_step(args.step)
     sys.exit(0)
 
-rows, failed, device = [], [], None
-for step in STEPS:
-    cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--window-ms", str(args.window_ms), "--windows", str(args.windows),
-           "--warmup", str(args.warmup), "--grid", str(args.grid)]
-    try:
-        done = subprocess.run(cmd, capture_output=True, text=True, timeout=args.step_seconds)
-        status, out = done.returncode, done.stdout
-        if status != 0:
-            sys.stderr.write(done.stderr[-2000:])
-    except subprocess.TimeoutExpired:
-        status, out = "time limit", ""
-    if status != 0:
-        failed.append(dict(step=step, status=status))
-        print(f"{step}: failed ({status}); no further step is started", flush=True)
-        break
-    for line in out.splitlines():
-        if line.startswith("ROW "):
-            rows.append(json.loads(line[4:]))
-            print(line[4:], flush=True)
-        elif line.startswith("DEVICE "):
-            device = json.loads(line[7:])
-
+forward = ["--window-ms", str(args.window_ms), "--windows", str(args.windows), "--warmup", str(args.warmup), "--grid", str(args.grid)]
+rows, failed, device, finished = probelib.run_steps(os.path.abspath(__file__), STEPS, forward, args.step_seconds)
 result = dict(device=device and device[0], library=device and device[1], dtype="float32",
               baseline="mesh3d.closest_points (the brute force of csrc/point_mesh.hip) in the same run, alternating windows",
               window_ms=args.window_ms, windows=args.windows, warmup=args.warmup, grid=args.grid, failed=failed,
-              not_measured=STEPS[len(rows):], rows=rows)
-os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "w") as f:
-    json.dump(result, f, indent=1)
-print(f"wrote {args.out}")
+              not_measured=STEPS[finished:], rows=rows)
+probelib.write_result(args.out, result)
 sys.exit(1 if failed else 0)

@@ -8,21 +8,17 @@ Workloads: (a) ``model_3000``: 3000 surface samples against the mouse model's me
 the mesh's vertices).  The torch brute force is timed on at most ``--torch-points`` of the points (a full (c) takes minutes); its
 time per point is what the ratio compares, and the row says how many points it ran.
 
-Needs a GPU; writes profiles/point_mesh_probe.json (``--out``).  Every workload is one STEP: a child process of its own under its own
-time limit, so a step that hangs or faults ends alone; the parent never opens the device, and after a step that failed it starts no
-other.  Method (per step): everything is warmed up first; a window is as many back-to-back calls as fill ``--window-ms`` (3 to
-2000, sized from a first window of 3) between two device events, ended by a synchronise; the windows of the variants ALTERNATE,
-``--windows`` of each, and the median and the spread (min, max) of the per-call time are recorded.  Times are those of the whole
-Python call.  Nothing here is asserted by a test.
+Needs a GPU; writes profiles/point_mesh_probe.json (``--out``).  Every workload is one STEP under its own time limit
+(``--step-seconds``), and the variants' windows alternate: the runner and the method are those of tools/probelib.py.  Here: a window
+holds 3 to 2000 calls, sized from a first window of 3.  Nothing here is asserted by a test.
 
     python3 tools/point_mesh_probe.py
 """
 import argparse
-import json
 import os
-import statistics
-import subprocess
 import sys
+
+import probelib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STEPS = ["model_3000", "hull_model_verts", "hull_100k"]
@@ -50,15 +46,6 @@ def run_step(name):
     from smilify_amd.mesh3d import Meshes
 
     dev = torch.device("cuda:0")
-
-    def window(fn, calls):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        ev[0].record()
-        for _ in range(calls):
-            fn()
-        ev[1].record()
-        torch.cuda.synchronize()
-        return ev[0].elapsed_time(ev[1]) / calls
 
     def hull_mesh(G):  # a disc seen by 18 cameras, carved (tools/hull_mesh_probe.py's scene)
         S, views = 256, 18
@@ -114,19 +101,11 @@ def run_step(name):
         return engine.chamfer(points, verts[None].contiguous())
 
     variants = dict(kernel_forward=forward, kernel_forward_backward=forward_backward, torch_brute_force=torch_brute, chamfer_to_vertices=chamfer)
-    for fn in variants.values():
-        for _ in range(args.warmup):
-            fn()
-    torch.cuda.synchronize()
-    calls = {who: int(min(2000, max(3, args.window_ms / max(window(fn, 3), 1e-6)))) for who, fn in variants.items()}
-    times = {who: [] for who in variants}
-    for _ in range(args.windows):
-        for who, fn in variants.items():
-            times[who].append(window(fn, calls[who]))
+    probelib.warm_up(variants.values(), args.warmup)
+    times, calls = probelib.alternate(variants, window_ms=args.window_ms, windows=args.windows, first=3, lo=3, hi=2000)
     row = dict(workload=name, points=P, faces=F, verts=int(verts.shape[0]), torch_points=tp, calls=calls)
-    for who, ts in times.items():
-        row[f"{who}_ms"] = statistics.median(ts)
-        row[f"{who}_ms_min"], row[f"{who}_ms_max"] = min(ts), max(ts)
+    for who, t in times.items():
+        row.update({f"{who}_{k}": v for k, v in t.items()})
     row["torch_per_point_over_kernel_per_point"] = (row["torch_brute_force_ms"] / tp) / (row["kernel_forward_ms"] / P)
     row["kernel_forward_over_chamfer"] = row["kernel_forward_ms"] / row["chamfer_to_vertices_ms"]
     row["pairs_per_second_forward"] = P * F / (row["kernel_forward_ms"] * 1e-3)
@@ -134,44 +113,22 @@ def run_step(name):
     d2, _ = forward()
     brute = torch.cat([o.values for o in torch_brute()])
     row["max_abs_difference_to_torch_sqrt"] = float((d2[0, :tp].sqrt() - brute.sqrt()).abs().max())
-    print("ROW " + json.dumps(row), flush=True)
-    print("DEVICE " + json.dumps([torch.cuda.get_device_name(0), engine._lib.load().smil_version().decode()]), flush=True)
+    probelib.emit_row(row)
+    probelib.emit_device([torch.cuda.get_device_name(0), engine._lib.load().smil_version().decode()])
 
 
 if args.step:
     run_step(args.step)
     sys.exit(0)
 
-rows, failed, device = [], [], None
-for step in STEPS:
-    cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--window-ms", str(args.window_ms), "--windows", str(args.windows),
-           "--warmup", str(args.warmup), "--grid", str(args.grid), "--torch-points", str(args.torch_points)]
-    try:
-        done = subprocess.run(cmd, capture_output=True, text=True, timeout=args.step_seconds)
-        status, out = done.returncode, done.stdout
-        if status != 0:
-            sys.stderr.write(done.stderr[-2000:])
-    except subprocess.TimeoutExpired:
-        status, out = "time limit", ""
-    if status != 0:
-        failed.append(dict(step=step, status=status))
-        print(f"{step}: failed ({status}); no further step is started", flush=True)
-        break
-    for line in out.splitlines():
-        if line.startswith("ROW "):
-            rows.append(json.loads(line[4:]))
-            print(line[4:], flush=True)
-        elif line.startswith("DEVICE "):
-            device = json.loads(line[7:])
-
+forward = ["--window-ms", str(args.window_ms), "--windows", str(args.windows), "--warmup", str(args.warmup), "--grid", str(args.grid),
+           "--torch-points", str(args.torch_points)]
+rows, failed, device, finished = probelib.run_steps(os.path.abspath(__file__), STEPS, forward, args.step_seconds)
 result = dict(device=device and device[0], library=device and device[1], dtype="float32",
               baseline="tests/point_mesh_ref.py closest_on_triangle on the device in float32, all pairs, chunked over the points",
               window_ms=args.window_ms, windows=args.windows, warmup=args.warmup, grid=args.grid, failed=failed,
-              not_measured=STEPS[len(rows):], rows=rows,
+              not_measured=STEPS[finished:], rows=rows,
               tile_cull="measured once behind a flag and dropped by the issue's rule (slower on the unsorted workload): "
                         "DESIGN.md section 4.20; no flag exists")
-os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "w") as f:
-    json.dump(result, f, indent=1)
-print(f"wrote {args.out}")
+probelib.write_result(args.out, result)
 sys.exit(1 if failed else 0)

@@ -23,6 +23,7 @@ import os
 import sys
 
 import numpy as np
+import probelib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -38,49 +39,40 @@ ap.add_argument("--faces-per-pixel", default="100,4")
 args = ap.parse_args()
 
 
-def bits(a):
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
 def rel_diff(a, b):
     return float(np.abs(a.astype(np.float64) - b.astype(np.float64)).max() / (np.abs(a.astype(np.float64)).max() + 1e-300))
 
 
 if args.compare:
-    a_dir, b_dir = args.compare
-    names = sorted(set(os.listdir(a_dir)) | set(os.listdir(b_dir)))
-    bad, took, n_equal, n_noise, worst = [], [], 0, 0, (0.0, 0.0, "")
-    for n in names:
-        if not (os.path.exists(os.path.join(a_dir, n)) and os.path.exists(os.path.join(b_dir, n))):
-            bad.append((n, "only in one directory"))
+    a, b = (probelib.load_arrays(d) for d in args.compare)
+    baseline = [probelib.load_arrays(d) for d in args.baseline or []]
+    only, changed = probelib.differing(a, b)
+    bad, took, worst = [(n + ".npy", "only in one directory") for n in only], [], (0.0, 0.0, "")
+    for n in changed:
+        x, y = a[n], b[n]
+        if x.shape != y.shape or not baseline:
+            bad.append((n + ".npy", "shape" if x.shape != y.shape else rel_diff(x, y)))
             continue
-        a, b = np.load(os.path.join(a_dir, n)), np.load(os.path.join(b_dir, n))
-        if a.dtype == b.dtype and a.shape == b.shape and np.array_equal(bits(a), bits(b)):
-            n_equal += 1
-            continue
-        if a.shape != b.shape or not args.baseline:
-            bad.append((n, "shape" if a.shape != b.shape else rel_diff(a, b)))
-            continue
-        runs = [a] + [np.load(os.path.join(d, n)) for d in args.baseline]
-        own = max(rel_diff(x, y) for i, x in enumerate(runs) for y in runs[i + 1:])
-        new = rel_diff(a, b)
-        small_launch_d_ndc = n.endswith("d_ndc.npy") and ".N64." not in n  # (the clip scenes are three images)
-        if not small_launch_d_ndc or all(np.array_equal(bits(a), bits(x)) for x in runs[1:]) or not new <= own:
-            bad.append((n, f"differs by {new:.3e} of its largest entry; the runs of the first library among themselves by {own:.3e}"))
+        runs = [x] + [r[n] for r in baseline]
+        own = max(rel_diff(p, q) for i, p in enumerate(runs) for q in runs[i + 1:])
+        new = rel_diff(x, y)
+        small_launch_d_ndc = n.endswith("d_ndc") and ".N64." not in n  # (the clip scenes are three images)
+        runs_agree = not any(probelib.differing({n: x}, {n: r})[1] for r in runs[1:])
+        if not small_launch_d_ndc or runs_agree or not new <= own:
+            bad.append((n + ".npy", f"differs by {new:.3e} of its largest entry; the runs of the first library among themselves by {own:.3e}"))
         else:
-            n_noise += 1
-            took.append(f"{n}: {new:.3e} (run-to-run {own:.3e})")
+            took.append(f"{n}.npy: {new:.3e} (run-to-run {own:.3e})")
             if new > worst[0]:
-                worst = (new, own, n)
-    print(f"{len(names)} arrays: {n_equal} bit-equal, {n_noise} d_ndc of launches below 64 images within the first library's own run-to-run "
-          f"difference, {len(bad)} differ")
+                worst = (new, own, n + ".npy")
+    print(f"{len(set(a) | set(b))} arrays: {len(set(a) & set(b)) - len(changed)} bit-equal, {len(took)} d_ndc of launches below 64 images within the "
+          f"first library's own run-to-run difference, {len(bad)} differ")
     for x in took:
         print("RUN-TO-RUN", x)
-    if n_noise:
+    if took:
         print(f"largest accepted difference {worst[0]:.3e} (run-to-run {worst[1]:.3e}) in {worst[2]}")
     for x in bad:
         print("DIFFERS", x)
-    sys.exit(1 if bad else 0)
+    sys.exit(1 if bad or not a else 0)
 
 import torch  # noqa: E402
 

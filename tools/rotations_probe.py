@@ -5,21 +5,18 @@ plus backward, at n = 4096 x 55 rotations (a batch of 4096 poses of a 55-joint m
 Needs a GPU; writes profiles/rotations_probe.json (``--out``).  The parent of these kernels has none to compare with: the torch
 composition is the baseline.
 
-Method: float32 storage.  Every function is warmed up at every size first.  A window is as many back-to-back calls as fill
-``--window-ms`` (20 to 2000, sized from a first window of 10) between two device events, ended by a synchronise; the kernel's and the
-composition's windows ALTERNATE, ``--windows`` of each, and the median and
-the spread (min, max) of the per-call time are recorded.  The figures are times of the whole Python call - argument checks, output
-allocation, autograd bookkeeping and launch latency included - so on the small size they are bounded by the host, not the device; the
-bytes a call must move (inputs read once, outputs written once) are recorded with the rate they imply.
+Method: that of tools/probelib.py, the kernel's and the composition's windows alternating.  Here: float32 storage; a window holds 20
+to 2000 calls, sized from a first window of 10.  On the small size the figures are bounded by the host, not the device; the bytes
+a call must move (inputs read once, outputs written once) are recorded with the rate they imply.
 
     python3 tools/rotations_probe.py
 """
 import argparse
 import json
 import os
-import statistics
 import sys
 
+import probelib
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -48,17 +45,6 @@ FUNCTIONS = {
 }
 
 
-def window(fn, calls):
-    """ms per call over ``calls`` back-to-back calls"""
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    ev[0].record()
-    for _ in range(calls):
-        fn()
-    ev[1].record()
-    torch.cuda.synchronize()
-    return ev[0].elapsed_time(ev[1]) / calls
-
-
 def forward_of(fn, xs):
     return lambda: fn(*xs)
 
@@ -81,28 +67,16 @@ for n in args.sizes:
         xs = [data[k] for k in keys]
         for mode, make in (("forward", forward_of), ("forward_backward", forward_backward_of)):
             pair = {"kernel": make(kernel_fn, xs), "torch": make(torch_fn, xs)}
-            for fn in pair.values():
-                for _ in range(args.warmup):
-                    fn()
-            torch.cuda.synchronize()
-            calls = {who: int(min(2000, max(20, args.window_ms / max(window(fn, 10), 1e-6)))) for who, fn in pair.items()}
-            times = {"kernel": [], "torch": []}
-            for _ in range(args.windows):
-                for who, fn in pair.items():
-                    times[who].append(window(fn, calls[who]))
+            probelib.warm_up(pair.values(), args.warmup)
+            times, calls = probelib.alternate(pair, window_ms=args.window_ms, windows=args.windows, first=10, lo=20, hi=2000)
             moved = 4 * n * values * (2 if mode == "forward_backward" else 1)  # the backward reads and writes the mirror image
             row = dict(function=name, mode=mode, n=n, bytes_moved=moved, kernel_calls=calls["kernel"], torch_calls=calls["torch"])
             for who, t in times.items():
-                row[f"{who}_ms"] = statistics.median(t)
-                row[f"{who}_ms_min"], row[f"{who}_ms_max"] = min(t), max(t)
+                row.update({f"{who}_{k}": v for k, v in t.items()})
             row["kernel_gb_per_s"] = moved / (row["kernel_ms"] * 1e-3) / 1e9
             row["torch_over_kernel"] = row["torch_ms"] / row["kernel_ms"]
             rows.append(row)
             print(json.dumps(row), flush=True)
 
-result = dict(device=torch.cuda.get_device_name(0), library=_lib.load().smil_version().decode(), dtype="float32", window_ms=args.window_ms,
-              windows=args.windows, warmup=args.warmup, rows=rows)
-os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "w") as f:
-    json.dump(result, f, indent=1)
-print(f"wrote {args.out}")
+probelib.write_result(args.out, dict(device=torch.cuda.get_device_name(0), library=_lib.load().smil_version().decode(), dtype="float32",
+                                     window_ms=args.window_ms, windows=args.windows, warmup=args.warmup, rows=rows))

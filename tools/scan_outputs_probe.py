@@ -19,6 +19,7 @@ import os
 import sys
 
 import numpy as np
+import probelib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -29,16 +30,13 @@ ap.add_argument("--compare", nargs=2, metavar="NPZ", help="compare two such file
 args = ap.parse_args()
 
 if args.compare:
-    a, b = (np.load(p) for p in args.compare)
-    bad = [("only in one file", n) for n in sorted(set(a.files) ^ set(b.files))]
-    for n in sorted(set(a.files) & set(b.files)):
-        x, y = a[n], b[n]
-        if not (x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes()):
-            bad.append((n, str(x.dtype), x.shape, y.shape))
-    print(f"{len(a.files)} / {len(b.files)} arrays, byte for byte: {len(bad)} differ")
+    a, b = (probelib.load_arrays(p) for p in args.compare)
+    only, changed = probelib.differing(a, b)
+    bad = [("only in one file", n) for n in only] + [(n, str(a[n].dtype), a[n].shape, b[n].shape) for n in changed]
+    print(f"{len(a)} / {len(b)} arrays, byte for byte: {len(bad)} differ")
     for x in bad:
         print("DIFFERS", x)
-    sys.exit(1 if bad or not a.files else 0)
+    sys.exit(1 if bad or not a else 0)
 
 import torch  # noqa: E402
 

@@ -8,22 +8,18 @@ hull mesh of a 256^3 carve (``VisualHull.extract_mesh``) - the containment quest
 mesh against it.  The torch brute force is timed on at most ``--torch-points`` of the points; its time per point is what the ratio
 compares, and the row says how many points it ran.
 
-Needs a GPU; writes profiles/winding_probe.json (``--out``).  Every workload is one STEP: a child process of its own under its own time
-limit, so a step that hangs or faults ends alone; the parent never opens the device, and after a step that failed it starts no other.
-Method (per step): everything is warmed up first; a window is as many back-to-back calls as fill ``--window-ms`` (3 to 2000, sized from
-a first window of 3) between two device events, ended by a synchronise; the windows of the variants ALTERNATE, ``--windows`` of each, and
-the median and the spread (min, max) of the per-call time are recorded.  Times are those of the whole Python call.  Nothing here is
-asserted by a test, and no time is a gate.
+Needs a GPU; writes profiles/winding_probe.json (``--out``).  Every workload is one STEP under its own time limit
+(``--step-seconds``), and the variants' windows alternate: the runner and the method are those of tools/probelib.py.  Here: a window
+holds 3 to 2000 calls, sized from a first window of 3.  Nothing here is asserted by a test, and no time is a gate.
 
     python3 tools/winding_probe.py
 """
 import argparse
 import datetime
-import json
 import os
-import statistics
-import subprocess
 import sys
+
+import probelib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STEPS = ["model_3000", "hull_model_verts", "hull_100k"]
@@ -51,15 +47,6 @@ def run_step(name):
     from smilify_amd.mesh3d import Meshes
 
     dev = torch.device("cuda:0")
-
-    def window(fn, calls):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        ev[0].record()
-        for _ in range(calls):
-            fn()
-        ev[1].record()
-        torch.cuda.synchronize()
-        return ev[0].elapsed_time(ev[1]) / calls
 
     def hull_mesh(G):  # a disc seen by 18 cameras, carved (tools/point_mesh_probe.py's scene)
         S, views = 256, 18
@@ -108,19 +95,11 @@ def run_step(name):
         return torch.cat([ref._pair_values(torch, v0, e1, e2, nrm, points[0, s:min(s + chunk, tp), None, :]).sum(1) for s in range(0, tp, chunk)])
 
     variants = dict(winding_number=winding, closest_points_kernels=closest, torch_brute_force=torch_brute)
-    for fn in variants.values():
-        for _ in range(args.warmup):
-            fn()
-    torch.cuda.synchronize()
-    calls = {who: int(min(2000, max(3, args.window_ms / max(window(fn, 3), 1e-6)))) for who, fn in variants.items()}
-    times = {who: [] for who in variants}
-    for _ in range(args.windows):
-        for who, fn in variants.items():
-            times[who].append(window(fn, calls[who]))
+    probelib.warm_up(variants.values(), args.warmup)
+    times, calls = probelib.alternate(variants, window_ms=args.window_ms, windows=args.windows, first=3, lo=3, hi=2000)
     row = dict(workload=name, points=P, faces=F, verts=int(verts.shape[0]), torch_points=tp, calls=calls)
-    for who, ts in times.items():
-        row[f"{who}_ms"] = statistics.median(ts)
-        row[f"{who}_ms_min"], row[f"{who}_ms_max"] = min(ts), max(ts)
+    for who, t in times.items():
+        row.update({f"{who}_{k}": v for k, v in t.items()})
     row["winding_over_closest_points"] = row["winding_number_ms"] / row["closest_points_kernels_ms"]
     row["torch_per_point_over_kernel_per_point"] = (row["torch_brute_force_ms"] / tp) / (row["winding_number_ms"] / P)
     row["pairs_per_second"] = P * F / (row["winding_number_ms"] * 1e-3)
@@ -129,43 +108,21 @@ def run_step(name):
     row["max_abs_difference_to_torch"] = float((w[:tp] - torch_brute()).abs().max())
     row["share_inside"] = float((w > 0.5).double().mean())
     row["largest_distance_to_an_integer"] = float((w - w.round()).abs().max())
-    print("ROW " + json.dumps(row), flush=True)
-    print("DEVICE " + json.dumps([torch.cuda.get_device_name(0), engine._lib.load().smil_version().decode()]), flush=True)
+    probelib.emit_row(row)
+    probelib.emit_device([torch.cuda.get_device_name(0), engine._lib.load().smil_version().decode()])
 
 
 if args.step:
     run_step(args.step)
     sys.exit(0)
 
-rows, failed, device = [], [], None
-for step in STEPS:
-    cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--window-ms", str(args.window_ms), "--windows", str(args.windows),
-           "--warmup", str(args.warmup), "--grid", str(args.grid), "--torch-points", str(args.torch_points)]
-    try:
-        done = subprocess.run(cmd, capture_output=True, text=True, timeout=args.step_seconds)
-        status, out = done.returncode, done.stdout
-        if status != 0:
-            sys.stderr.write(done.stderr[-2000:])
-    except subprocess.TimeoutExpired:
-        status, out = "time limit", ""
-    if status != 0:
-        failed.append(dict(step=step, status=status))
-        print(f"{step}: failed ({status}); no further step is started", flush=True)
-        break
-    for line in out.splitlines():
-        if line.startswith("ROW "):
-            rows.append(json.loads(line[4:]))
-            print(line[4:], flush=True)
-        elif line.startswith("DEVICE "):
-            device = json.loads(line[7:])
-
+forward = ["--window-ms", str(args.window_ms), "--windows", str(args.windows), "--warmup", str(args.warmup), "--grid", str(args.grid),
+           "--torch-points", str(args.torch_points)]
+rows, failed, device, finished = probelib.run_steps(os.path.abspath(__file__), STEPS, forward, args.step_seconds)
 result = dict(device=device and device[0], library=device and device[1], dtype="float32", date=datetime.date.today().isoformat(),
               baseline="tests/winding_ref.py _pair_values on the device in float32, all pairs, chunked over the points, float sum",
               compared_with="engine.point_mesh_distance (k_pm_extent, k_pm_table, k_pm_points, k_pm_finish) on the same inputs",
               window_ms=args.window_ms, windows=args.windows, warmup=args.warmup, grid=args.grid, failed=failed,
-              not_measured=STEPS[len(rows):], rows=rows)
-os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "w") as f:
-    json.dump(result, f, indent=1)
-print(f"wrote {args.out}")
+              not_measured=STEPS[finished:], rows=rows)
+probelib.write_result(args.out, result)
 sys.exit(1 if failed else 0)
